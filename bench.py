@@ -12,8 +12,17 @@ sharded by image) is reported beside it under "nll", and the large-batch data-
 parallel train step (configs[4]: B=4096 over 8 GPUs, i.e. 512 images per GPU,
 k=50) under "large_batch" -- weak scaling at that per-GPU share.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...    (one process per GPU)
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(`value`, `ms_per_step`: the K timed steps alone).  --dump-outputs DIR writes
+what the timed steps computed (dump_outputs below) as DIR/<name>.npy: inputs,
+weights and device noise are seeded, so two builds run with the same arguments
+can be compared output for output.  --full adds every other leg to the line:
+the same steps as one call each, the per-kernel roofline figures, the large-
+batch step, the k=5000 NLL, get_training_statistics, configs[0] and the CPU
+baselines (each can be left out with its --no-* option).
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, this process starts
 the N ranks itself (torch.distributed.run as a child process, before any GPU
@@ -346,11 +355,32 @@ def launch_ranks(n, argv, script=None):
     return 0
 
 
+def dump_outputs(path, model, losses):
+    """What a caller of the timed path holds after its last step, as
+    path/<name>.npy (float32, about 6.5 MB for the 2L model): `losses`, the
+    per-step losses the timed train_steps calls returned (the last entry is the
+    last step's), and the model state that step left: `weights` and `gradients`
+    (flat, in get_weights / get_gradients order), `adam_m` and `adam_v`."""
+    os.makedirs(path, exist_ok=True)
+    m, v, _ = model.get_optimizer_state()
+    arrays = dict(losses=losses,
+                  weights=np.concatenate([w.ravel() for w in model.get_weights()]),
+                  gradients=np.concatenate([g.ravel() for g in model.get_gradients()]),
+                  adam_m=m, adam_v=v)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed steps computed (losses, weights, gradients, Adam moments) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg (per-call steps, per-kernel roofline, large "
+                         "batch, NLL, training statistics, configs[0], CPU baselines) and add them to the result line")
     ap.add_argument("--nll-images", type=int, default=10000)
     ap.add_argument("--nll-k", type=int, default=5000)
     ap.add_argument("--no-nll", action="store_true")
@@ -420,13 +450,16 @@ def main():
 
     def run(n, off=0):
         # fit's batch loop (E:82): consecutive batches of the resident set, one
-        # library call per contiguous run (iwae_train_steps: up to 32 steps per graph)
+        # library call per contiguous run (iwae_train_steps: up to 32 steps per graph);
+        # returns what the calls returned: the per-step losses, still on the device
+        got = []
         while n > 0:
             o = off % nb
             m = min(n, nb - o)
-            model.train_steps(xd[o * B_PER_GPU:(o + m) * B_PER_GPU], B_PER_GPU, sync=False)
+            got.append(model.train_steps(xd[o * B_PER_GPU:(o + m) * B_PER_GPU], B_PER_GPU, sync=False))
             n -= m
             off += m
+        return got
 
     def run_calls(n, off=0):
         # the same steps as one train_step call each (F:221 per call)
@@ -455,7 +488,7 @@ def main():
     barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    run(args.steps, args.warmup)
+    timed_losses = run(args.steps, args.warmup)
     model._stream.synchronize()
     torch.cuda.synchronize()
     barrier()
@@ -472,6 +505,49 @@ def main():
     rows = world * B_PER_GPU * K * args.steps
     value = rows / el
     ms_per_step = 1e3 * el / args.steps
+    # what the timed steps computed, read before any other leg touches the model
+    losses = np.concatenate([t.cpu().numpy() for t in timed_losses])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, losses)
+
+    def result_line(loss, **legs):
+        out = {
+            "metric": "train images*k/sec and k=5000 test-NLL images/sec, 1-8 MI355X",
+            "value": round(value, 1),
+            "unit": "image*samples/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 5),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "fp32 (bf16x3 split products)",
+            "precision": PRECISION,
+            "data": "synthetic",
+            "config": {"workload": "IWAE train step (fwd+bound+bwd+Adam), k=50, 2 stochastic layers "
+                                   "784-200-200-100-100-50, batch 20 per GPU (BASELINE configs[1])",
+                       "global_batch": B_PER_GPU * world, "k": K, "parallelism": f"dp{world}",
+                       "noise": "device Philox", "graphs": not args.no_graphs,
+                       "loop": "fit's batch loop (E:82): consecutive batches through Flexible_Model.train_steps "
+                               "(iwae_train_steps, up to 32 captured steps per graph launch); the timed call's "
+                               "graphs are captured before the clock starts (iwae_train_steps_prepare)",
+                       "graph_captures_in_timed_region": captures_timed},
+            "loss": round(loss, 4),
+            "full": args.full,
+            "rccl_world": rccl_world,
+        }
+        out.update(legs)
+        print(json.dumps(out), flush=True)
+
+    if not args.full:
+        # a plain run ends here: the headline figure and the last timed step's loss
+        if rank == 0:
+            result_line(float(losses[-1]))
+        if world > 1:
+            dist.destroy_process_group()
+        return
+    # ---- every other leg (--full)
     # the same number of steps as one train_step call each (host issue + one graph per step)
     run_calls(min(args.warmup, 10), args.warmup + args.steps)
     model._stream.synchronize()
@@ -732,41 +808,9 @@ def main():
             cpu_c0 = cpu_baseline_configs0(max(2.0, args.cpu_seconds / 3))
 
     if rank == 0:
-        out = {
-            "metric": "train images*k/sec and k=5000 test-NLL images/sec, 1-8 MI355X",
-            "value": round(value, 1),
-            "unit": "image*samples/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 5),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "fp32 (bf16x3 split products)",
-            "precision": PRECISION,
-            "data": "synthetic",
-            "config": {"workload": "IWAE train step (fwd+bound+bwd+Adam), k=50, 2 stochastic layers "
-                                   "784-200-200-100-100-50, batch 20 per GPU (BASELINE configs[1])",
-                       "global_batch": B_PER_GPU * world, "k": K, "parallelism": f"dp{world}",
-                       "noise": "device Philox", "graphs": not args.no_graphs,
-                       "loop": "fit's batch loop (E:82): consecutive batches through Flexible_Model.train_steps "
-                               "(iwae_train_steps, up to 32 captured steps per graph launch); the timed call's "
-                               "graphs are captured before the clock starts (iwae_train_steps_prepare)",
-                       "graph_captures_in_timed_region": captures_timed},
-            "loss": round(loss, 4),
-            "train_step_calls": per_call,
-            "rccl_world": rccl_world,
-            "nll": nll,
-            "large_batch": large,
-            "training_statistics": stats,
-            "configs0_train": c0,
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-            "cpu_baseline_nll": cpu_nll,
-            "cpu_baseline_configs0": cpu_c0,
-        }
-        print(json.dumps(out), flush=True)
+        result_line(loss, train_step_calls=per_call, nll=nll, large_batch=large, training_statistics=stats,
+                    configs0_train=c0, roofline=roofline, cpu_baseline=cpu, cpu_baseline_nll=cpu_nll,
+                    cpu_baseline_configs0=cpu_c0)
     if world > 1:
         dist.destroy_process_group()
 

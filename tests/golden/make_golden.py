@@ -68,6 +68,9 @@ def make(name, he, hd, le, ld, x_dim, B, k, k1, k2, seed):
         if x_dim <= 64 or loss in FULL_GRADS_784:
             out[f"{loss}.grad_loss"] = (-O.flatten_params(spec, g)).astype(np.float32)
     out["logpx"] = O.log_px_per_image(params, spec, x, k, eps=eps)
+    if x_dim > 64:      # the full gradients in a file of their own: each fixture file stays under 1 MiB
+        grads = {kk: out.pop(kk) for kk in [kk for kk in out if kk.endswith(".grad_loss")]}
+        np.savez_compressed(os.path.join(HERE, f"{name}_grads.npz"), **grads)
     np.savez_compressed(os.path.join(HERE, f"{name}.npz"), **out)
     print(name, {kk: float(v) for kk, v in out.items() if kk.endswith(".J")})
 

@@ -8,7 +8,7 @@ mkdir -p $O
 for rep in 1 2; do
 for cfg in "$@"; do
   T=""; for kv in $cfg; do [ "$kv" != "base" ] && T="$T --tune $kv"; done
-  timeout -k 10 200 python -u bench.py --no-cpu --no-nll --no-stats --no-c0 $T > $O/ab.jsonl 2> $O/ab.err || exit $?
+  timeout -k 10 200 python -u bench.py --full --no-cpu --no-nll --no-stats --no-c0 $T > $O/ab.jsonl 2> $O/ab.err || exit $?
   python -c "import json,sys;d=json.loads(open('$O/ab.jsonl').read().splitlines()[-1]);print('$cfg', d['ms_per_step'], d['train_step_calls']['ms_per_step'], d['large_batch']['ms_per_step'])" | tee -a $O/ab.txt
 done
 done

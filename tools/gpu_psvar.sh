@@ -16,7 +16,7 @@ for rep in 1 2; do
     IWAE_HIP_LIB=dbgx/libps_$v.so timeout -k 10 120 python -u tools/train_large.py 512 40 2>/dev/null | tee -a $O/lb.txt || exit $?
   done
   for v in base TC; do
-    IWAE_HIP_LIB=dbgx/libps_$v.so timeout -k 10 200 python -u bench.py --no-cpu --no-nll --no-stats --no-c0 --no-large-batch > $O/b.jsonl 2> $O/b.err || exit $?
+    IWAE_HIP_LIB=dbgx/libps_$v.so timeout -k 10 200 python -u bench.py --full --no-cpu --no-nll --no-stats --no-c0 --no-large-batch > $O/b.jsonl 2> $O/b.err || exit $?
     python -c "import json;d=json.loads(open('$O/b.jsonl').read().splitlines()[-1]);print('$v', d['ms_per_step'], d['train_step_calls']['ms_per_step'])" | tee -a $O/b20.txt
   done
 done

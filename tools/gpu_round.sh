@@ -11,5 +11,5 @@ tail -5 $O/pytest.log
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 timeout -k 10 120 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || exit $?
 tail -2 $O/smoke.log
-timeout -k 10 400 python -u bench.py > $O/bench.jsonl 2> $O/bench.err || exit $?
+timeout -k 10 400 python -u bench.py --full > $O/bench.jsonl 2> $O/bench.err || exit $?
 tail -1 $O/bench.jsonl

@@ -11,7 +11,7 @@ tail -2 $O/pytest_gpu.log
 for rep in 1 2 3; do
   for lib in "" tools/dbgx/libkm0.so; do
     if [ -n "$lib" ]; then export IWAE_HIP_LIB=$lib; else unset IWAE_HIP_LIB; fi
-    timeout -k 10 150 python -u bench.py --steps 300 --warmup 20 --no-cpu --no-nll > $O/b.json 2> $O/b.err || exit $?
+    timeout -k 10 150 python -u bench.py --full --steps 300 --warmup 20 --no-cpu --no-nll > $O/b.json 2> $O/b.err || exit $?
     python -c "import json; d=json.loads(open('$O/b.json').read().strip().splitlines()[-1]); print('${lib:-in-tree}', d['ms_per_step'], d['configs0_train']['ms_per_step'], (d.get('large_batch') or {}).get('ms_per_step'))"
   done
 done

@@ -10,12 +10,12 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 O=gpurun_out/${1:-round}
 mkdir -p $O
-timeout -k 10 400 python -u bench.py > $O/bench.jsonl 2> $O/bench.err || exit $?
+timeout -k 10 400 python -u bench.py --full > $O/bench.jsonl 2> $O/bench.err || exit $?
 tail -c 400 $O/bench.jsonl
-timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 --no-cpu > $O/bench_driver.jsonl 2> $O/bench_driver.err || exit $?
+timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 --no-cpu > $O/bench_driver.jsonl 2> $O/bench_driver.err || exit $?
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- \
-  python -u bench.py --no-cpu > $O/bench_prof.jsonl 2> $O/bench_prof.err || exit $?
-PMC_OUT=$O/pmc bash tools/pmc_passes.sh python -u bench.py --steps 20 --warmup 5 --no-nll --no-cpu --no-c0 \
+  python -u bench.py --full --no-cpu > $O/bench_prof.jsonl 2> $O/bench_prof.err || exit $?
+PMC_OUT=$O/pmc bash tools/pmc_passes.sh python -u bench.py --full --steps 20 --warmup 5 --no-nll --no-cpu --no-c0 \
   --no-large-batch --no-stats || exit $?
 J=$O/pmc_traffic.json
 python tools/pmc_to_json.py $O/pmc "tc_kernel<" $J "tc_kernel forward (train engine, bf16x3)" rank:0 &&

@@ -1,7 +1,7 @@
 #!/bin/bash
 # rocprofv3 PMC passes (one counter group per run, kernel-trace only; no
 # sys/runtime traces beside --pmc) over a command given as arguments, e.g.
-#   bash tools/pmc_passes.sh python -u bench.py --steps 20 --warmup 5 --no-nll --no-cpu
+#   bash tools/pmc_passes.sh python -u bench.py --full --steps 20 --warmup 5 --no-nll --no-cpu
 # Outputs gpurun_out/pmc/<pass>/..._counter_collection.csv
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"

@@ -12,7 +12,7 @@ if [ "${BUILD:-0}" = 1 ]; then
 fi
 mkdir -p gpurun_out/abl
 for d in $MASKS; do
-  IWAE_HIP_LIB=tools/_dbg/libiwae_abl$d.so timeout -k 10 120 python -u bench.py --steps 100 --warmup 10 --no-cpu --no-nll \
+  IWAE_HIP_LIB=tools/_dbg/libiwae_abl$d.so timeout -k 10 120 python -u bench.py --full --steps 100 --warmup 10 --no-cpu --no-nll \
     --no-large-batch --no-c0 > gpurun_out/abl/d$d.json 2> gpurun_out/abl/d$d.err || exit $?
   python -c "import json; d=json.loads(open('gpurun_out/abl/d$d.json').read().strip().splitlines()[-1]); k=d['roofline']['kernels']; print('mask=$d', d['ms_per_step'], {n[:12]: v['avg_us'] for n, v in k.items()})"
 done
