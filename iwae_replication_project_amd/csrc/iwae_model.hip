@@ -88,6 +88,144 @@ struct Plan {
   int piwae = 0;
 };
 
+// Tuning knobs (iwae_set_tuning; ids, ranges and the measurements behind the
+// defaults: include/iwae.h).
+struct Tune {
+  int engine = 1;                    // train step on the row-chain engine when it applies
+  int engine_img = 1;                // ... with the first encoder layer's l2 / head on its image-row jobs
+  int engine_img_bwd = 1;            // ... their backward on the image-row job at small batches too
+  int engine_fold0 = 0;              // ... its l2 / head folded into the forward jobs at small batches
+  int tc_xcd = 1;                    // XCD-aware job placement of the engine launches
+  int tc_bound = 1;                  // the train step's bound inside the engine's backward launch
+  int tc_rt = 1;                     // row tiles of 16 per engine workgroup below wide_rows
+  long long wide_rows = 4097;        // sample rows from which the engine runs 32 / 64-row workgroups
+  int wide_rt = 2;                   // engine row tiles per workgroup of the backward launches from
+                                     // wide_rows (1, 2 or 4; the forward launch: 4)
+  int img_rows_fwd = 0, img_rows_bwd = 0;   // image-row jobs I / I': rows per workgroup (0: auto)
+  int x_direct = 1;                  // large-batch engine step: the input GEMM reads the caller's x (gemm_direct)
+  int piwae_one = 1;                 // PIWAE: one unit-weight backward chain serves both weightings
+  int upd = 1;                       // fused weight-gradient + Adam + FX update launch
+  long long upd_rows = 4096;         // ... up to this many sample rows per step
+  int upd_slabs = 1;                 // ... and beyond upd_rows its split-K gradient pass into the slabs
+  long long upd_slab_wg = 512;       // sample-row workgroups of that pass
+  int upd_waves = 16;                // update kernel workgroups: 16 waves (four per SIMD), 8 or 4
+  int upd_apply = 1;                 // large batches: the update kernel sums the slabs, Adam, FX / GX (one launch)
+  int tcu = 1;                       // job I' and the fused update in one launch (tcu_kernel) where it fits
+  int tcu_wt = 1;                    // the combined launch's hand-off write-through (launch_tcu decides)
+  int tcu_wait_test = 0;             // fault injection: every combined-launch wait gives up
+  int dw_wide = 1;                   // the slab pass run by the 208 x 128-block weight-gradient kernel (iwae_dwgrad.hip;
+                                     // B = 512: 107 vs 152 us for the update kernel's pass, step 0.513 -> 0.473 ms)
+  long long dw_target = 768;         // split-K target workgroups per layer of the grouped weight-gradient GEMMs
+  int dw_wg = 256;                   // large-batch weight-gradient pass: workgroups its row chunks aim at
+  int dw_alpha = 150;                // ... its cost model: a k step's fixed cost in MFMA tiles (measured: a
+                                     // k step costs ~2 us whatever its tiles; alpha 0 / 45 / 90 / 200: 174 / 127 / 108 / 106 us)
+  int smallm_rows = 32;              // first encoder layer on the few-row launches up to this many images (0: never)
+  long long out_x3_rows = 8192;      // sample rows from which a train step runs the output layer's GEMMs on bf16x3 (0: never)
+  int ld_align = 4;                  // workspace row strides: multiples of this many floats (4 or 32)
+  int mg_waves = 8;                  // mega_fwd_kernel workgroup: 8 waves (64 rows) or 4 (32 rows, 2 per CU)
+  long long nll_rows = 1LL << 20;    // sample rows per NLL chunk (measured fastest: 2^17-2^20 within 10 %)
+  int nll_imgs = 0;                  // images per NLL chunk when the caller passes chunk 0 (0: nll_rows / k)
+  int nring = 1;                     // NLL: the weight-ring kernel (nring_kernel) where its shapes apply
+  int nring_train = 1;               // train-step forward on it (train mode) ...
+  long long nr_train_rows = 4096;    // ... from this many sample rows
+  int nring_bwd = 3;                 // large-batch train step: the output MLP's backward on nrb_kernel
+                                     // (2: on the side stream beside the engine's backward launch;
+                                     // 3: then the encoder / prior backward on nre_kernel too)
+};
+
+// the input-layer launch of a captured train step: it reads the caller's x
+// directly and is re-pointed at each call's x (hipGraphExecKernelNodeSetParams)
+struct XLaunch {
+  int kind = 0;                      // 0: smallm_kernel (SmArgs), 1: gemm_kernel (GemmArgs)
+  SmArgs sm{};
+  GemmArgs gm{};
+};
+
+// Valid only during a train step or its capture (do_train, do_train_steps);
+// StepScope puts every field back to these values when the call leaves.
+struct StepState {
+  bool in_train_step = false;        // weight-operand GEMMs of a train step stay exact f32
+  bool out_x3 = false;               // ... except the output layer's two GEMMs of a large-batch step (bf16x3)
+  const float* x_user = nullptr;     // caller's x read directly by the first kernel
+  float* loss_out = nullptr;         // loss destination (part of the graph key)
+  bool capturing = false;
+  hipGraphNode_t cap_x_node = nullptr;   // the captured input-layer launch and its arguments
+  XLaunch cap_x_args{};
+  bool piwae_ks = false;             // the weight gradients apply the per-layer PIWAE weighting
+  bool defer_launch = false;         // tc_run / run_update record their launch in Pending instead
+};
+
+// the launches recorded under defer_launch, issued by launch_pending
+struct Pending {
+  bool tc_have = false, upd_have = false;
+  TcArgs tc{};
+  int tc_rt = 1;
+  size_t tc_lds = 0;
+  UpdArgs upd{};
+  unsigned upd_mask = 0;             // update jobs that read job I''s output (the first encoder layer's)
+  int upd_cons = 0;                  // their tiles
+};
+
+// live kernel timing (HIP events around every launch of one GEMM class)
+struct Prof {
+  int kind = -1, epi = -1;
+  std::vector<hipEvent_t> ev;
+  size_t used = 0;
+  double flop = 0.0;
+  // last launch of the profiled GEMM class (replayed back to back by iwae_profile_replay)
+  bool have = false;
+  GemmArgs args{};
+  GemmKind k = GEMM_FWD; GemmEpi e = EPI_STORE;
+  int tile = 0, splits = 1; bool ks = false;
+  double flop1 = 0.0;
+  bool is_tc = false;                // the recorded launch is an engine launch (kind 10 / 11)
+  // memory-bound launches (kind 12 Adam, 13 bound, 14 FX refresh): the
+  // launch as a closure and its algorithmic bytes (reported in place of FLOP)
+  std::function<hipError_t(hipStream_t)> mem;
+  float* scratch = nullptr;          // side-effect targets of a replayed bound launch
+  float* adam = nullptr;             // parameters / m / v copies a replayed Adam launch updates
+  size_t adam_bytes = 0;
+  TcArgs tc{};
+  int tc_rt = 1;
+  size_t tc_lds = 0;
+};
+
+// launch counters (iwae_debug_count)
+struct Counters {
+  long long mega = 0, mega_eps = 0;  // 0, 1: mega_fwd_kernel launches (all / injected noise)
+  long long tc = 0;                  // 2: train-engine launches (tc_kernel)
+  long long nring = 0;               // 3: nring_kernel launches
+  long long nring_train = 0;         // 4: ... of them train-step forwards
+  long long nrb = 0, nre = 0;        // 5, 6: nrb_kernel / nre_kernel launches
+  long long captures = 0;            // 7: train-step graphs captured (single and multi-step)
+  long long tcu = 0;                 // 9: combined job I' + update launches (tcu_kernel)
+};
+
+// row-chain train engine plan (device resident, per shape; iwae_train.hip)
+struct TcRec {
+  TcPlan* dev = nullptr;
+  int rt = 1, nb[kTcMaxJobs] = {};
+  int row_step = 0;                  // rows per workgroup (image-row launches; 0: 16 rt)
+  size_t lds = 0;
+  int acc_off = 0;                   // float offset of the per-row accumulators in LDS
+  double flop = 0.0;                 // algorithmic FLOPs of one launch (weight products, no bias rows)
+  unsigned kinds = 0;                // op kinds of the plan's jobs (TcArgs::kinds)
+};
+
+// a captured train step (or several: iwae_train_steps)
+struct GraphRec {
+  hipGraphExec_t exec = nullptr;
+  hipGraph_t graph = nullptr;
+  // one input-layer launch per captured step that reads the caller's x (a
+  // single train step: one entry, or none when x was staged)
+  std::vector<hipGraphNode_t> xs_node;
+  std::vector<XLaunch> xs_args;
+  std::vector<const float*> xs_cap;
+  // multi-step graphs: the last node, the losses' copy, re-pointed at each call's loss_dev
+  hipGraphNode_t loss_node = nullptr;
+  float* loss_cap = nullptr;
+};
+
 }  // namespace
 
 struct iwae_handle {
@@ -104,6 +242,18 @@ struct iwae_handle {
   int o1 = -1, o2 = -1, o3 = -1;
   std::vector<KerasDense> keras;
   long long nparam_int = 0, nparam_keras = 0;
+  int n_cu = 256;                    // compute units of the device (hipDeviceAttributeMultiprocessorCount)
+  // modes (iwae_set_path / _precision / _graphs) and knobs (iwae_set_tuning)
+  int path = 0;                      // 0 auto, 1 layer-wise kernels, 2 fused row-block kernels
+  int x3 = 1;                        // tiled GEMMs: 1 bf16x3 products (default), 0 exact f32 MFMA
+  int nll_fused = 1;                 // NLL: fused k-sample forward (mega_fwd_kernel) when it fits
+  bool use_graphs = false;
+  Tune tune;
+  // per-call state
+  StepState step;
+  Pending pend;
+  Prof prof;
+  Counters count;
   // persistent device state
   float* params = nullptr;
   size_t params_bytes = 0;   // allocation incl. the zero tail the row-block weight fetch may over-read
@@ -119,14 +269,21 @@ struct iwae_handle {
   __bf16* fx_lo = nullptr;
   long long fx_elems = 0;
   long long fx_version = 0;
-  bool in_train_step = false;        // weight-operand GEMMs of a train step stay exact f32
-  bool out_x3 = false;               // ... except the output layer's two GEMMs of a large-batch step (bf16x3)
-  long long out_x3_rows = 8192;      // sample rows from which a train step takes that exception (0: never)
+  bool adam_splits = false;          // the Adam launch being built also rewrites the split copies
   DevState* ds = nullptr;
   uint64_t seed = 0x5eed5eedULL;       // Philox key actually used (derived from user_seed, noise_stream)
   uint64_t user_seed = 0x5eed5eedULL;
   uint64_t noise_stream = 0;
   std::map<uint64_t, uint64_t> stream_pos;   // saved Philox counter of the streams not selected
+  NrUnit* nr_units = nullptr;        // nring_kernel's unit table (device, built once: FX offsets are fixed per model)
+  NrUnit* nrb_units = nullptr;       // nrb_kernel's
+  NrUnit* nre_units = nullptr;       // nre_kernel's (nring_bwd 3: the encoder / prior backward on the ring too)
+  unsigned* tcu_ctr = nullptr;       // tcu_kernel's in-launch counters (UpdWait::ctr; zero between launches)
+  unsigned* err_host = nullptr;      // host-mapped error word a kernel sets when an in-launch wait gives up
+  unsigned* err_dev = nullptr;       // ... its device address (UpdWait::err)
+  float* loss_slots = nullptr;       // multi-step graphs: step j's loss (kGraphSteps floats), then
+                                     // [kGraphSteps, 2 kGraphSteps): where a graph's copy node writes
+                                     // when the call wants no losses
   // data parallelism (iwae_dp_init)
   int dp_rank = 0, dp_world = 1;
   bool dp_weighted = false;            // forward_backward writes B_local * grad and B_local at grad[nparam_int]
@@ -152,140 +309,23 @@ struct iwae_handle {
   int fslab_S = 0;
   float* oslab = nullptr;            // split-K slabs of the output layer's dX (fused path)
   int oslab_S = 0;
-  int path = 0;                      // 0 auto, 1 layer-wise kernels, 2 fused row-block kernels
-  int x3 = 1;                        // tiled GEMMs: 1 bf16x3 products (default), 0 exact f32 MFMA
-  int nll_fused = 1;                 // NLL: fused k-sample forward (mega_fwd_kernel) when it fits
-  int mg_waves = 8;                  // mega_fwd_kernel workgroup: 8 waves (64 rows) or 4 (32 rows, 2 per CU)
-  int nring = 1;                     // NLL: the weight-ring kernel (nring_kernel) where its shapes apply
-  int nring_train = 1;               // train-step forward on it (train mode) ...
-  long long nr_train_rows = 4096;    // ... from this many sample rows
-  NrUnit* nr_units = nullptr;        // its unit table (device, built once: FX offsets are fixed per model)
-  int nr_nunits = 0;
-  long long n_nring = 0;             // nring_kernel launches, iwae_debug_count
-  long long n_nring_train = 0;       // ... of them train-step forwards
-  int nring_bwd = 3;                 // large-batch train step: the output MLP's backward on nrb_kernel
-                                     // (2: on the side stream beside the engine's backward launch;
-                                     // 3: then the encoder / prior backward on nre_kernel too)
-  int upd_waves = 16;                // update kernel workgroups: 16 waves (four per SIMD), 8 or 4
-  int wide_rt = 2;                   // engine row tiles per workgroup of the backward launches from
-                                     // wide_rows (1, 2 or 4; the forward launch: 4)
-  NrUnit* nrb_units = nullptr;       // its unit table (device, built once)
-  NrUnit* nre_units = nullptr;       // nre_kernel's (nring_bwd 3: the encoder / prior backward on the ring too)
-  long long n_nre = 0;
-  long long n_nrb = 0;               // nrb_kernel launches, iwae_debug_count
   bool masked = false;               // active-unit masks in force (iwae_nll_masked only)
-  long long n_mega = 0, n_mega_eps = 0;  // mega_fwd_kernel launches (all / injected noise), iwae_debug_count
-  long long n_tc = 0;                    // train-engine launches (tc_kernel), iwae_debug_count(h, 2)
-  long long n_captures = 0;              // train-step graphs captured (single and multi-step), iwae_debug_count(h, 7)
-  long long n_tcu = 0;                   // combined job I' + update launches (tcu_kernel), iwae_debug_count(h, 9)
   const float* mask[IWAE_MAX_LAYERS] = {};
-  // row-chain train engine plans (device resident, per shape; iwae_train.hip)
-  struct TcRec {
-    TcPlan* dev = nullptr;
-    int rt = 1, nb[kTcMaxJobs] = {};
-    int row_step = 0;                  // rows per workgroup (image-row launches; 0: 16 rt)
-    size_t lds = 0;
-    int acc_off = 0;                 // float offset of the per-row accumulators in LDS
-    double flop = 0.0;               // algorithmic FLOPs of one launch (weight products, no bias rows)
-    unsigned kinds = 0;              // op kinds of the plan's jobs (TcArgs::kinds)
-  };
-  std::map<std::vector<long long>, TcRec> tc_plans;
-  int engine = 1;                    // train step on the row-chain engine when it applies (iwae_set_path)
-  int engine_img = 1;                // ... with the first encoder layer's l2 / head on its image-row jobs
-  int engine_fold0 = 0;              // ... its l2 / head folded into the forward jobs at small batches
-  int engine_img_bwd = 1;            // ... their backward on the image-row job at small batches too
-  int tc_xcd = 1;                    // XCD-aware job placement of the engine launches
-  int tc_bound = 1;                  // the train step's bound inside the engine's backward launch
-  bool adam_splits = false;          // the Adam launch being built also rewrites the split copies
-  int upd = 1;                       // fused weight-gradient + Adam + FX update launch
-  long long upd_rows = 4096;         // ... up to this many sample rows per step
-  int upd_slabs = 1;                 // ... and beyond upd_rows its split-K gradient pass into the slabs
-  long long upd_slab_wg = 512;       // sample-row workgroups of that pass
-  int dw_wide = 1;                   // ... run by the 208 x 128-block weight-gradient kernel (iwae_dwgrad.hip;
-                                     // B = 512: 107 vs 152 us for the update kernel's pass, step 0.513 -> 0.473 ms)
-  long long dw_target = 768;         // split-K target workgroups per layer of the grouped weight-gradient GEMMs
-  int smallm_rows = 32;              // first encoder layer on the few-row launches up to this many images (0: never)
-  long long nll_rows = 1LL << 20;    // sample rows per NLL chunk (measured fastest: 2^17-2^20 within 10 %)
-  int nll_imgs = 0;                  // images per NLL chunk when the caller passes chunk 0 (0: nll_rows / k)
-  int dw_wg = 256;                   // large-batch weight-gradient pass: workgroups its row chunks aim at
-  int dw_alpha = 150;                // ... its cost model: a k step's fixed cost in MFMA tiles (measured: a
-                                     // k step costs ~2 us whatever its tiles; alpha 0 / 45 / 90 / 200: 174 / 127 / 108 / 106 us)
-  int img_rows_fwd = 0, img_rows_bwd = 0;   // image-row jobs I / I': rows per workgroup (0: auto)
-  int x_direct = 1;                  // large-batch engine step: the input GEMM reads the caller's x (gemm_direct)
-  int tcu = 1;                       // job I' and the fused update in one launch (tcu_kernel) where it fits
-  int upd_apply = 1;                 // large batches: the update kernel sums the slabs, Adam, FX / GX (one launch)
-  unsigned* tcu_ctr = nullptr;       // its in-launch counters (UpdWait::ctr; zero between launches)
-  unsigned* err_host = nullptr;      // host-mapped error word a kernel sets when an in-launch wait gives up
-  unsigned* err_dev = nullptr;       // ... its device address (UpdWait::err)
-  int tcu_wt = 1;                    // the combined launch's hand-off write-through (knob TCU_WT; launch_tcu decides)
-  int tcu_wait_test = 0;             // fault injection (knob TCU_WAIT_TEST): every combined-launch wait gives up
-  int n_cu = 256;                    // compute units of the device (hipDeviceAttributeMultiprocessorCount)
-  bool defer_launch = false;         // (during a step) tc_run / run_update record their launch instead
-  bool pend_tc_have = false, pend_upd_have = false;
-  TcArgs pend_tc{};
-  int pend_tc_rt = 1;
-  size_t pend_tc_lds = 0;
-  UpdArgs pend_upd{};
-  unsigned pend_upd_mask = 0;        // update jobs that read job I''s output (the first encoder layer's)
-  int pend_upd_cons = 0;             // their tiles
-  int piwae_one = 1;                 // PIWAE: one unit-weight backward chain serves both weightings (knob)
-  bool piwae_ks = false;             // (during a step) the weight gradients apply the per-layer PIWAE weighting
-  int tc_rt = 1;                     // row tiles of 16 per engine workgroup below wide_rows
-  int ld_align = 4;                  // workspace row strides: multiples of this many floats (4 or 32)
-  long long wide_rows = 4097;        // sample rows from which the engine runs 32 / 64-row workgroups
-  // graphs
-  bool use_graphs = false;
-  // a captured train step; its first kernel reads the caller's x directly
-  // (x_node: that launch, re-pointed with hipGraphExecKernelNodeSetParams)
-  // the input-layer launch of a captured train step, re-pointed at each call's x
-  struct XLaunch {
-    int kind = 0;                      // 0: smallm_kernel (SmArgs), 1: gemm_kernel (GemmArgs)
-    SmArgs sm{};
-    GemmArgs gm{};
-  };
-  struct GraphRec {
-    hipGraphExec_t exec = nullptr;
-    hipGraph_t graph = nullptr;
-    hipGraphNode_t x_node = nullptr;
-    XLaunch x_args{};
-    const float* x_cap = nullptr;
-    // multi-step graphs (iwae_train_steps): one input-layer launch per captured step
-    std::vector<hipGraphNode_t> xs_node;
-    std::vector<XLaunch> xs_args;
-    std::vector<const float*> xs_cap;
-    hipGraphNode_t loss_node = nullptr;  // its last node: the losses' copy, re-pointed at each call's loss_dev
-    float* loss_cap = nullptr;
-  };
-  std::map<std::vector<long long>, GraphRec> graphs;
-  const float* x_user = nullptr;       // train step: caller's x read directly by the first kernel
-  bool capturing = false;
-  hipGraphNode_t cap_x_node = nullptr;
-  XLaunch cap_x_args{};
-  // live kernel timing (HIP events around every launch of one GEMM class)
-  float* loss_out = nullptr;           // train-step loss destination (part of the graph key)
-  float* loss_slots = nullptr;         // multi-step graphs: step j's loss (kGraphSteps floats), then
-                                       // [kGraphSteps, 2 kGraphSteps): where a graph's copy node writes
-                                       // when the call wants no losses
-  int prof_kind = -1, prof_epi = -1;
-  std::vector<hipEvent_t> prof_ev;
-  size_t prof_used = 0;
-  double prof_flop = 0.0;
-  // last launch of the profiled GEMM class (replayed back to back by iwae_profile_replay)
-  bool prof_have = false;
-  GemmArgs prof_args{};
-  GemmKind prof_k = GEMM_FWD; GemmEpi prof_e = EPI_STORE;
-  int prof_tile = 0, prof_splits = 1; bool prof_ks = false;
-  double prof_flop1 = 0.0;
-  bool prof_is_tc = false;             // the recorded launch is an engine launch (prof_kind 10 / 11)
-  // memory-bound launches (prof_kind 12 Adam, 13 bound, 14 FX refresh): the
-  // launch as a closure and its algorithmic bytes (reported in place of FLOP)
-  std::function<hipError_t(hipStream_t)> prof_mem;
-  float* prof_scratch = nullptr;       // side-effect targets of a replayed bound launch
-  float* prof_adam = nullptr;          // parameters / m / v copies a replayed Adam launch updates
-  size_t prof_adam_bytes = 0;
-  TcArgs prof_tc{};
-  int prof_tc_rt = 1;
-  size_t prof_tc_lds = 0;
+  std::map<std::vector<long long>, TcRec> tc_plans;     // engine plans per shape
+  std::map<std::vector<long long>, GraphRec> graphs;    // captured train steps per graph key
+};
+
+// Resets the handle's per-step state when a train-step call leaves, on every
+// exit.  (The flags engine_train_body sets -- piwae_ks, defer_launch, the
+// pending launches -- are read only by the launches of that same step, and
+// nothing runs between its return and the driver's: one guard at the drivers
+// restores what the body's own guards used to.)
+struct StepScope {
+  iwae_handle* h;
+  ~StepScope() {
+    h->step = StepState();
+    h->pend.tc_have = h->pend.upd_have = false;
+  }
 };
 
 #define HIPCHK(expr)                                                           \
@@ -336,19 +376,29 @@ static StochL add_stoch(iwae_handle* h, int fin, int H, int d, int rows_kind) {
   h->keras.push_back({s.head, d, d});
   return s;
 }
-static void destroy_graph(iwae_handle::GraphRec& g) {
+static void destroy_graph(GraphRec& g) {
   if (g.exec) (void)hipGraphExecDestroy(g.exec);
   if (g.graph) (void)hipGraphDestroy(g.graph);
   g.exec = nullptr;
   g.graph = nullptr;
 }
 
-
-static void free_workspace(iwae_handle* h) {
+// drop every captured train step: something they captured (a kernel argument,
+// a path decision) is about to change
+static void invalidate_graphs(iwae_handle* h) {
   for (auto& kv : h->graphs) destroy_graph(kv.second);
   h->graphs.clear();
-  for (auto& kv : h->tc_plans) (void)hipFree(kv.second.dev);    // they point into the arena
+}
+
+// drop the engine plans (built per shape for the current knobs; they point into the arena)
+static void invalidate_tc_plans(iwae_handle* h) {
+  for (auto& kv : h->tc_plans) (void)hipFree(kv.second.dev);
   h->tc_plans.clear();
+}
+
+static void free_workspace(iwae_handle* h) {
+  invalidate_graphs(h);
+  invalidate_tc_plans(h);
   if (h->arena) (void)hipFree(h->arena);
   h->arena = nullptr;
   h->arena_bytes = 0;
@@ -373,7 +423,7 @@ static int ensure_capacity(iwae_handle* h, int Bimg, int rows, bool train) {
   struct Pending { Mat* m; size_t o; };
   std::vector<std::pair<float**, size_t>> vecs;
   std::vector<Pending> mats;
-  const int la = h->ld_align;
+  const int la = h->tune.ld_align;
   auto mat = [&](Mat& m, int nrows, int width) {
     m.ld = (width + la - 1) / la * la;
     mats.push_back({&m, take((size_t)nrows * m.ld)});
@@ -452,7 +502,7 @@ static int ensure_capacity(iwae_handle* h, int Bimg, int rows, bool train) {
     for (auto& d : h->dense) {
       const long long R = d.rows_kind == 0 ? Bimg : rows;
       const long long tiles = cdiv(d.fin + 1, 64) * cdiv(d.fout, 64);
-      long long S = std::max(1LL, cdiv(h->dw_target, tiles));   // split-K target workgroups per layer
+      long long S = std::max(1LL, cdiv(h->tune.dw_target, tiles));   // split-K target workgroups per layer
       // at most 16 slabs (the Adam kernel sums up to 16 with all loads in flight;
       // more slabs only add write + read traffic at large batch)
       S = std::min(S, std::min(16LL, std::max(1LL, cdiv(R, 64))));
@@ -496,12 +546,12 @@ static int ensure_capacity(iwae_handle* h, int Bimg, int rows, bool train) {
 
 // --------------------------------------------------------------- GEMMs
 // pre-split B operand (weights) for a bf16x3 GEMM: only outside the train step
-static bool use_split_b(const iwae_handle* h) { return h->x3 && !h->in_train_step; }
+static bool use_split_b(const iwae_handle* h) { return h->x3 && !h->step.in_train_step; }
 // split-weight (bf16x3) operand for Dense d: every tiled GEMM outside the train
 // step; inside it only the output layer of a large-batch step, whose split copy
 // the step refreshes first (run_wsplit_seg)
 static bool split_b_for(const iwae_handle* h, const DenseL& d) {
-  return use_split_b(h) || (h->out_x3 && &d == &h->dense[h->o3]);
+  return use_split_b(h) || (h->step.out_x3 && &d == &h->dense[h->o3]);
 }
 
 static int choose_tile(long long M, long long N, int splits) {
@@ -509,34 +559,34 @@ static int choose_tile(long long M, long long N, int splits) {
 }
 
 static bool prof_match(iwae_handle* h, GemmKind kind, GemmEpi epi) {
-  return h->prof_kind == (int)kind && h->prof_epi == (int)epi;
+  return h->prof.kind == (int)kind && h->prof.epi == (int)epi;
 }
 
 static void prof_note(iwae_handle* h, GemmKind kind, GemmEpi epi, int tile, int splits, bool ks, const GemmArgs& a,
                       double flop) {
   if (!prof_match(h, kind, epi)) return;
-  h->prof_have = true; h->prof_args = a; h->prof_k = kind; h->prof_e = epi;
-  h->prof_tile = tile; h->prof_splits = splits; h->prof_ks = ks; h->prof_flop1 = flop;
+  h->prof.have = true; h->prof.args = a; h->prof.k = kind; h->prof.e = epi;
+  h->prof.tile = tile; h->prof.splits = splits; h->prof.ks = ks; h->prof.flop1 = flop;
 }
 
 static int prof_begin(iwae_handle* h, GemmKind kind, GemmEpi epi, double flop) {
   if (!prof_match(h, kind, epi)) return IWAE_OK;
-  if (h->prof_used + 2 > h->prof_ev.size()) {
+  if (h->prof.used + 2 > h->prof.ev.size()) {
     for (int i = 0; i < 256; ++i) {
       hipEvent_t e;
       HIPCHK(hipEventCreate(&e));
-      h->prof_ev.push_back(e);
+      h->prof.ev.push_back(e);
     }
   }
-  HIPCHK(hipEventRecord(h->prof_ev[h->prof_used], h->stream));
-  h->prof_flop += flop;
+  HIPCHK(hipEventRecord(h->prof.ev[h->prof.used], h->stream));
+  h->prof.flop += flop;
   return IWAE_OK;
 }
 
 static int prof_end(iwae_handle* h, GemmKind kind, GemmEpi epi) {
   if (!prof_match(h, kind, epi)) return IWAE_OK;
-  HIPCHK(hipEventRecord(h->prof_ev[h->prof_used + 1], h->stream));
-  h->prof_used += 2;
+  HIPCHK(hipEventRecord(h->prof.ev[h->prof.used + 1], h->stream));
+  h->prof.used += 2;
   return IWAE_OK;
 }
 
@@ -793,20 +843,20 @@ static int run_bound(iwae_handle* h, const Plan& P, bool train, float sign, floa
   }
   const BoundArgs b = make_bound_args(h, P, train, sign, value_out, adam_tick, engine);
   HIPCHK(launch_bound(h->stream, b));
-  if (h->prof_kind == 13 && !h->prof_have) {
+  if (h->prof.kind == 13 && !h->prof.have) {
     // replays write the loss, Philox base and Adam step into scratch instead
-    if (!h->prof_scratch) HIPCHK(hipMalloc(&h->prof_scratch, 64 * sizeof(float)));
-    HIPCHK(hipMemsetAsync(h->prof_scratch, 0, 64 * sizeof(float), h->stream));
+    if (!h->prof.scratch) HIPCHK(hipMalloc(&h->prof.scratch, 64 * sizeof(float)));
+    HIPCHK(hipMemsetAsync(h->prof.scratch, 0, 64 * sizeof(float), h->stream));
     BoundArgs r = b;
-    r.loss = h->prof_scratch;
-    r.rng_base = reinterpret_cast<uint64_t*>(h->prof_scratch + 8);
-    r.adam_step = b.adam_step ? reinterpret_cast<decltype(b.adam_step)>(h->prof_scratch + 16) : nullptr;
-    r.ticket = reinterpret_cast<unsigned*>(h->prof_scratch + 24);
-    h->prof_mem = [r](hipStream_t st) { return launch_bound(st, r); };
+    r.loss = h->prof.scratch;
+    r.rng_base = reinterpret_cast<uint64_t*>(h->prof.scratch + 8);
+    r.adam_step = b.adam_step ? reinterpret_cast<decltype(b.adam_step)>(h->prof.scratch + 16) : nullptr;
+    r.ticket = reinterpret_cast<unsigned*>(h->prof.scratch + 24);
+    h->prof.mem = [r](hipStream_t st) { return launch_bound(st, r); };
     const double rows = (double)P.Bimg * P.kS;
     // logq, logp, the row's 4 partial-sum floats in; lw, dlw, dpx out; contrib per image
-    h->prof_flop1 = rows * (2 + 4 + 1 + (b.dlw ? 1 : 0) + (b.dpx ? 1 : 0)) * 4.0 + (double)P.Bimg * 4.0;
-    h->prof_have = true;
+    h->prof.flop1 = rows * (2 + 4 + 1 + (b.dlw ? 1 : 0) + (b.dpx ? 1 : 0)) * 4.0 + (double)P.Bimg * 4.0;
+    h->prof.have = true;
   }
   return IWAE_OK;
 }
@@ -928,13 +978,13 @@ static int run_fx(iwae_handle* h) {
   }
   a.total = tot;
   HIPCHK(launch_fx_refresh(h->stream, a));
-  if (h->prof_kind == 14 && !h->prof_have) {
-    h->prof_mem = [a](hipStream_t st) { return launch_fx_refresh(st, a); };
+  if (h->prof.kind == 14 && !h->prof.have) {
+    h->prof.mem = [a](hipStream_t st) { return launch_fx_refresh(st, a); };
     double chunks = 0.0;                  // 8 parameters in, 8 bf16 per plane out
     for (int i = 0; i < a.nseg; ++i)
       chunks += ((double)a.seg[i].fx_tiles * a.seg[i].fx_steps + (double)a.seg[i].gx_tiles * a.seg[i].gx_steps) * 64;
-    h->prof_flop1 = chunks * (8 * 4.0 + 2 * 16.0);
-    h->prof_have = true;
+    h->prof.flop1 = chunks * (8 * 4.0 + 2 * 16.0);
+    h->prof.have = true;
   }
   return IWAE_OK;
 }
@@ -974,28 +1024,28 @@ static int run_adam(iwae_handle* h, bool read_slabs, bool write_grad, bool do_ad
   a.grad_scale_override = scale_override;
   a.tick = tick;
   HIPCHK(launch_adam(h->stream, a, mx));
-  if (h->prof_kind == 12 && do_adam && !h->prof_have) {
+  if (h->prof.kind == 12 && do_adam && !h->prof.have) {
     AdamArgs r = a;
     r.tick = false;                  // replays repeat this step's update (same t)
     // ... on scratch copies of the parameters and moments: the model is untouched
     const size_t pb = (size_t)h->nparam_int * sizeof(float);
-    if (h->prof_adam_bytes < 3 * pb) {
-      if (h->prof_adam) HIPCHK(hipFree(h->prof_adam));
-      h->prof_adam = nullptr;
-      HIPCHK(hipMalloc(&h->prof_adam, 3 * pb));
-      h->prof_adam_bytes = 3 * pb;
+    if (h->prof.adam_bytes < 3 * pb) {
+      if (h->prof.adam) HIPCHK(hipFree(h->prof.adam));
+      h->prof.adam = nullptr;
+      HIPCHK(hipMalloc(&h->prof.adam, 3 * pb));
+      h->prof.adam_bytes = 3 * pb;
     }
-    HIPCHK(hipMemcpyAsync(h->prof_adam, h->params, pb, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->prof_adam + h->nparam_int, h->adam_m, pb, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->prof_adam + 2 * h->nparam_int, h->adam_v, pb, hipMemcpyDeviceToDevice, h->stream));
-    r.param = h->prof_adam; r.m = h->prof_adam + h->nparam_int; r.v = h->prof_adam + 2 * h->nparam_int;
+    HIPCHK(hipMemcpyAsync(h->prof.adam, h->params, pb, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->prof.adam + h->nparam_int, h->adam_m, pb, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->prof.adam + 2 * h->nparam_int, h->adam_v, pb, hipMemcpyDeviceToDevice, h->stream));
+    r.param = h->prof.adam; r.m = h->prof.adam + h->nparam_int; r.v = h->prof.adam + 2 * h->nparam_int;
     // (the gradient buffer is rewritten with the same values)
-    h->prof_mem = [r, mx](hipStream_t st) { return launch_adam(st, r, mx); };
+    h->prof.mem = [r, mx](hipStream_t st) { return launch_adam(st, r, mx); };
     double bytes = 0.0;
     for (int i = 0; i < a.nseg; ++i)      // p, m, v in; p, m, v (+ g) out; the slabs in
       bytes += (double)a.seg[i].n * 4.0 * (6 + (write_grad ? 1 : 0) + (read_slabs ? a.seg[i].splits : 1));
-    h->prof_flop1 = bytes;
-    h->prof_have = true;
+    h->prof.flop1 = bytes;
+    h->prof.have = true;
   }
   return IWAE_OK;
 }
@@ -1008,6 +1058,19 @@ static int copy_x(iwae_handle* h, const Plan& P, const float* x) {
     HIPCHK(hipMemcpy2DAsync(h->x_in.p + (size_t)P.B * h->x_in.ld, (size_t)h->x_in.ld * sizeof(float), x,
                             wbytes, wbytes, P.B, hipMemcpyDeviceToDevice, h->stream));
   }
+  return IWAE_OK;
+}
+
+// The node the capture on the handle's stream enqueued last (null unless it
+// is exactly one): the launch or copy just issued, kept to re-point on replay.
+static int last_captured_node(iwae_handle* h, hipGraphNode_t* node) {
+  hipStreamCaptureStatus cs;
+  unsigned long long cid;
+  hipGraph_t cg;
+  const hipGraphNode_t* deps = nullptr;
+  size_t nd = 0;
+  HIPCHK(hipStreamGetCaptureInfo_v2(h->stream, &cs, &cid, &cg, &deps, &nd));
+  *node = nd == 1 ? deps[0] : nullptr;
   return IWAE_OK;
 }
 
@@ -1087,7 +1150,7 @@ static int smallm(iwae_handle* h, const Mat& A, int rows, const DenseL& d, bool 
   return IWAE_OK;
 }
 static bool smallm_ok(const iwae_handle* h, int rows) {
-  if (rows > std::min(h->smallm_rows, 32)) return false;      // (0: never the few-row launches)
+  if (rows > std::min(h->tune.smallm_rows, 32)) return false;      // (0: never the few-row launches)
   for (int di : {h->enc[0].l1, h->enc[0].l2, h->enc[0].head})
     if (h->dense[di].fin + 1 > 1024 || h->dense[di].fout > 1024) return false;
   return true;
@@ -1125,8 +1188,8 @@ static int enc0_forward(iwae_handle* h, const Plan& P, bool l1_only = false) {
     // input layer: from the caller's x when given (it also fills x_in for the
     // later readers: Bernoulli epilogue, weight gradient), else from x_in
     SmArgs a{};
-    if (h->x_user) {
-      a.A = h->x_user; a.lda = h->xdim;
+    if (h->step.x_user) {
+      a.A = h->step.x_user; a.lda = h->xdim;
       a.a_ones = h->xdim; a.a_bytes = (unsigned)((size_t)P.Bimg * h->xdim * sizeof(float));
       a.a_copy = h->x_in.p; a.a_copy_ld = h->x_in.ld;
     } else {
@@ -1143,22 +1206,13 @@ static int enc0_forward(iwae_handle* h, const Plan& P, bool l1_only = false) {
       a.C = h->eb[0].y1.p; a.ldc = h->eb[0].y1.ld;
       a.act = 1;
     }
-    // remember the launch that reads x: replays re-point it at the caller's next x
-    auto note_x = [&](int kind) -> int {
-      if (!(h->capturing && h->x_user)) return IWAE_OK;
-      hipStreamCaptureStatus cs;
-      unsigned long long cid;
-      hipGraph_t cg;
-      const hipGraphNode_t* deps = nullptr;
-      size_t nd = 0;
-      HIPCHK(hipStreamGetCaptureInfo_v2(h->stream, &cs, &cid, &cg, &deps, &nd));
-      h->cap_x_node = nd == 1 ? deps[0] : nullptr;
-      h->cap_x_args.kind = kind;
-      h->cap_x_args.sm = a;
-      return IWAE_OK;
-    };
     HIPCHK(launch_smallm(h->stream, a));
-    CHK(note_x(0));
+    if (h->step.capturing && h->step.x_user) {
+      // remember the launch that reads x: replays re-point it at the caller's next x
+      CHK(last_captured_node(h, &h->step.cap_x_node));
+      h->step.cap_x_args.kind = 0;
+      h->step.cap_x_args.sm = a;
+    }
     if (l1_only) return IWAE_OK;
     const DenseL& d2 = h->dense[S0.l2];
     SmArgs b{};
@@ -1180,7 +1234,7 @@ static int enc0_forward(iwae_handle* h, const Plan& P, bool l1_only = false) {
   {
     const DenseL& d = h->dense[h->enc[0].l1];
     GemmArgs a{};
-    a.x3 = h->in_train_step ? 0 : h->x3;
+    a.x3 = h->step.in_train_step ? 0 : h->x3;
     a.A = h->x_in.p; a.lda = h->x_in.ld;
     a.B = h->params + d.off; a.ldb = d.ldw;
     a.C = h->fslab; a.ldc = h->eb[0].y1.ld;
@@ -1189,25 +1243,19 @@ static int enc0_forward(iwae_handle* h, const Plan& P, bool l1_only = false) {
     a.kchunk = (int)enc0_kchunk(h, P.Bimg);
     const int S = (int)cdiv(a.K, a.kchunk);
     a.c_split_stride = (long long)P.Bimg * a.ldc;
-    if (h->x_user) {
+    if (h->step.x_user) {
       // the caller's x with a virtual ones column; the column-0 workgroups
       // fill x_in for the later readers (ring forward pixels, weight gradients)
-      a.A = h->x_user; a.lda = h->xdim;
+      a.A = h->step.x_user; a.lda = h->xdim;
       a.a_ones = h->xdim; a.a_copy = h->x_in.p; a.a_copy_ld = h->x_in.ld;
     }
     CHK(prof_begin(h, GEMM_FWD, EPI_STORE, 2.0 * P.Bimg * d.fout * d.fin));
     HIPCHK(launch_gemm(h->stream, GEMM_FWD, EPI_STORE, 0, S, false, a));
     CHK(prof_end(h, GEMM_FWD, EPI_STORE));
-    if (h->capturing && h->x_user) {
-      hipStreamCaptureStatus cs;
-      unsigned long long cid;
-      hipGraph_t cg;
-      const hipGraphNode_t* deps = nullptr;
-      size_t nd = 0;
-      HIPCHK(hipStreamGetCaptureInfo_v2(h->stream, &cs, &cid, &cg, &deps, &nd));
-      h->cap_x_node = nd == 1 ? deps[0] : nullptr;
-      h->cap_x_args.kind = 1;
-      h->cap_x_args.gm = a;
+    if (h->step.capturing && h->step.x_user) {
+      CHK(last_captured_node(h, &h->step.cap_x_node));
+      h->step.cap_x_args.kind = 1;
+      h->step.cap_x_args.gm = a;
     }
     if (l1_only) return IWAE_OK;
     // (2) rest of encoder layer 0 on the images: tanh(sum) -> l2 -> head (P0)
@@ -1449,7 +1497,7 @@ static int fused_encoder_bwd(iwae_handle* h, const Plan& P, const float* dlw, in
 // the row scale of layer di's dZ in the weight gradients: ks as given, or under
 // piwae_unit the layer's weighting
 static const float* dz_scale(const iwae_handle* h, int di, const float* ks) {
-  if (!h->piwae_ks) return ks;
+  if (!h->step.piwae_ks) return ks;
   if (di == h->o1 || di == h->o2 || di == h->o3) return h->dpx;
   for (int i = 0; i < h->L - 1; ++i)
     if (di == h->dec[i].l1 || di == h->dec[i].l2 || di == h->dec[i].head) return h->dlw;
@@ -1521,7 +1569,7 @@ static bool upd_tiles_ok(const iwae_handle* h) {
   return tiles <= kUpdMaxTiles && (int)h->dense.size() <= kUpdMaxJobs;
 }
 static bool use_update(const iwae_handle* h, const Plan& P) {
-  if (!h->upd || !h->x3 || (long long)P.Bimg * P.kS > h->upd_rows) return false;
+  if (!h->tune.upd || !h->x3 || (long long)P.Bimg * P.kS > h->tune.upd_rows) return false;
   long long tiles = 0;
   for (const DenseL& d : h->dense) tiles += cdiv(d.fin + 1, 64) * cdiv(d.fout, 64);
   return tiles <= kUpdMaxTiles && (int)h->dense.size() <= kUpdMaxJobs;
@@ -1534,7 +1582,7 @@ static bool use_update(const iwae_handle* h, const Plan& P) {
 // rows into the split-K slabs the Adam launch sums (the weight-gradient GEMMs'
 // role); about two workgroups per CU of sample-row tiles
 static bool use_update_slabs(const iwae_handle* h, const Plan& P) {
-  return h->upd_slabs && h->x3 && h->slabs && (long long)P.Bimg * P.kS > h->upd_rows &&
+  return h->tune.upd_slabs && h->x3 && h->slabs && (long long)P.Bimg * P.kS > h->tune.upd_rows &&
          (int)h->dense.size() <= kUpdMaxJobs;
 }
 
@@ -1586,7 +1634,7 @@ static int run_update(iwae_handle* h, const Plan& P, bool adam, int bucket = 0, 
     long long st_tiles = 0;                      // sample-row tiles: nsplit of them per CU pair
     for (const WJ& w : js)
       if (w.rows == M) st_tiles += cdiv(h->dense[w.di].fin + 1, 64) * cdiv(h->dense[w.di].fout, 64);
-    const long long target = h->upd_slab_wg;     // sample-row workgroups of the pass
+    const long long target = h->tune.upd_slab_wg;     // sample-row workgroups of the pass
     nsplit = (int)std::max(1LL, (target + st_tiles / 2) / std::max(1LL, st_tiles));
     a.search = 1;
   }
@@ -1636,43 +1684,43 @@ static int run_update(iwae_handle* h, const Plan& P, bool adam, int bucket = 0, 
   a.state = &h->ds->adam; a.do_adam = (adam || apply) && !slabs ? 1 : 0;
   a.gscale = slabs ? 1.f : gscale; a.tail = (slabs || apply) ? nullptr : tail; a.tail_val = gscale;
   a.apply = apply ? (from_slabs ? 2 : 1) : 0; a.scale_dev = scale_dev;
-  a.waves = h->upd_waves;
-  if (h->defer_launch && st == h->stream && !slabs && !apply) {
+  a.waves = h->tune.upd_waves;
+  if (h->step.defer_launch && st == h->stream && !slabs && !apply) {
     // recorded for a combined launch (tcu_kernel) with job I': the first
     // encoder layer's jobs are the ones that wait for it
-    h->pend_upd = a; h->pend_upd_have = true;
-    h->pend_upd_mask = 0; h->pend_upd_cons = 0;
+    h->pend.upd = a; h->pend.upd_have = true;
+    h->pend.upd_mask = 0; h->pend.upd_cons = 0;
     for (int j = 0; j < a.njobs; ++j) {
       const int di = js[j].di;
       if (di == h->enc[0].l1 || di == h->enc[0].l2 || di == h->enc[0].head) {
-        h->pend_upd_mask |= 1u << j;
-        h->pend_upd_cons += a.job[j].tiles_m * a.job[j].tiles_n;
+        h->pend.upd_mask |= 1u << j;
+        h->pend.upd_cons += a.job[j].tiles_m * a.job[j].tiles_n;
       }
     }
   } else {
     HIPCHK(launch_update(st, a));
   }
   if (a.do_adam) h->params_version++;
-  if (h->prof_kind == 15 && adam && !h->prof_have) {
+  if (h->prof.kind == 15 && adam && !h->prof.have) {
     // replays repeat this step's update on scratch copies of the parameters,
     // moments and fragment-major copies: the model is untouched
     const size_t pb = (size_t)h->nparam_int * sizeof(float), fb = (size_t)h->fx_elems * 2 * sizeof(__bf16);
-    if (h->prof_adam_bytes < 3 * pb + fb) {
-      if (h->prof_adam) HIPCHK(hipFree(h->prof_adam));
-      h->prof_adam = nullptr;
-      HIPCHK(hipMalloc(&h->prof_adam, 3 * pb + fb));
-      h->prof_adam_bytes = 3 * pb + fb;
+    if (h->prof.adam_bytes < 3 * pb + fb) {
+      if (h->prof.adam) HIPCHK(hipFree(h->prof.adam));
+      h->prof.adam = nullptr;
+      HIPCHK(hipMalloc(&h->prof.adam, 3 * pb + fb));
+      h->prof.adam_bytes = 3 * pb + fb;
     }
-    HIPCHK(hipMemcpyAsync(h->prof_adam, h->params, pb, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->prof_adam + h->nparam_int, h->adam_m, pb, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->prof_adam + 2 * h->nparam_int, h->adam_v, pb, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->prof.adam, h->params, pb, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->prof.adam + h->nparam_int, h->adam_m, pb, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->prof.adam + 2 * h->nparam_int, h->adam_v, pb, hipMemcpyDeviceToDevice, h->stream));
     UpdArgs r = a;
-    r.param = h->prof_adam; r.m = h->prof_adam + h->nparam_int; r.v = h->prof_adam + 2 * h->nparam_int;
-    r.fx_hi = reinterpret_cast<__bf16*>(h->prof_adam + 3 * h->nparam_int);
+    r.param = h->prof.adam; r.m = h->prof.adam + h->nparam_int; r.v = h->prof.adam + 2 * h->nparam_int;
+    r.fx_hi = reinterpret_cast<__bf16*>(h->prof.adam + 3 * h->nparam_int);
     r.fx_lo = r.fx_hi + h->fx_elems;
-    h->prof_mem = [r](hipStream_t st) { return launch_update(st, r); };
-    h->prof_flop1 = flop;
-    h->prof_have = true;
+    h->prof.mem = [r](hipStream_t st) { return launch_update(st, r); };
+    h->prof.flop1 = flop;
+    h->prof.have = true;
   }
   return IWAE_OK;
 }
@@ -1720,12 +1768,12 @@ static int run_dw(iwae_handle* h, const Plan& P) {
     J.nib = (int)cdiv(J.mt, J.wide ? 8 : 13); J.mtb = (int)cdiv(J.mt, J.nib);
     J.njb = (int)cdiv(J.nt, J.wide ? 16 : 8); J.ntb = (int)cdiv(J.nt, J.njb);
     // a k step's cost in tile units: its MFMA tiles + a fixed cost
-    cost[q] = (double)J.mtb * J.ntb + (double)h->dw_alpha;
+    cost[q] = (double)J.mtb * J.ntb + (double)h->tune.dw_alpha;
     W += cost[q] * J.nib * J.njb * (double)cdiv(js[q].rows, 32);
   }
   // block-k-steps of tiles per workgroup; the grid must not exceed one workgroup
   // per CU (8 XCDs x 32): a second round would double the pass
-  double target = W / (double)h->dw_wg;
+  double target = W / (double)h->tune.dw_wg;
   for (int tries = 0; tries < 64; ++tries) {
     long long n = 0;
     for (size_t q = 0; q < js.size(); ++q) {
@@ -1735,7 +1783,7 @@ static int run_dw(iwae_handle* h, const Plan& P) {
       const long long chunk = cdiv(cdiv(js[q].rows, S), 32) * 32;
       n += (long long)a.job[q].nib * a.job[q].njb * cdiv(js[q].rows, chunk);
     }
-    if (n <= h->dw_wg) break;
+    if (n <= h->tune.dw_wg) break;
     target *= 1.02;
   }
   int items = 0;
@@ -1773,7 +1821,7 @@ static int run_dw(iwae_handle* h, const Plan& P) {
 constexpr int kTcMaxLayers = 3;      // op-table capacity: 4 ops per stochastic layer and direction
 
 static bool use_engine(const iwae_handle* h, const Plan& P) {
-  if (!h->engine || !h->x3 || h->path == 1 || h->path == 2 || h->masked) return false;
+  if (!h->tune.engine || !h->x3 || h->path == 1 || h->path == 2 || h->masked) return false;
   if (P.kl) return false;       // VAE_V1's analytic KL: fused row-block path
   if (h->L > kTcMaxLayers || h->enc[0].d > 2048) return false;   // (image-row backward: d / 4 column quads)
   const long long rows = (long long)P.Bimg * P.kS;
@@ -1870,7 +1918,7 @@ static void tc_fold_first_layer(iwae_handle* h, const Plan& P, TcBuild& B) {
 }
 
 static bool use_fold0(const iwae_handle* h, const Plan& P) {
-  return h->engine_fold0 && smallm_ok(h, P.Bimg) && h->L >= 1;
+  return h->tune.engine_fold0 && smallm_ok(h, P.Bimg) && h->L >= 1;
 }
 
 static std::vector<long long> tc_key(const Plan& P, int which) {
@@ -1886,7 +1934,7 @@ static int tc_prepare_one(iwae_handle* h, const Plan& P, int which) {
   const int L = h->L, kS = P.kS;
   auto r32 = [](int x) { return (x + 31) & ~31; };
   // wide workgroups (32 / 64 sample rows, two-set weight pipeline) for large batches
-  const bool wide = (which <= 1 || which >= 4) && (long long)P.Bimg * kS >= h->wide_rows;
+  const bool wide = (which <= 1 || which >= 4) && (long long)P.Bimg * kS >= h->tune.wide_rows;
   std::vector<TcBuild> jobs;
   const bool fold0 = which == 0 && use_fold0(h, P);
   auto ldF = [&](int di) { return h->dense[di].ldF; };
@@ -2086,12 +2134,12 @@ static int tc_prepare_one(iwae_handle* h, const Plan& P, int which) {
   // image rows: one image per workgroup (latency-bound chains of a few rows), up to 256 workgroups
   // (knobs img_rows_fwd / img_rows_bwd: rows per workgroup of job I / I' instead)
   int row_step = img ? (int)std::max<long long>(1, cdiv(P.Bimg, 256)) : 0;
-  if (which == 2 && h->img_rows_fwd > 0) row_step = h->img_rows_fwd;
-  if (which == 3 && h->img_rows_bwd > 0) row_step = h->img_rows_bwd;
+  if (which == 2 && h->tune.img_rows_fwd > 0) row_step = h->tune.img_rows_fwd;
+  if (which == 3 && h->tune.img_rows_bwd > 0) row_step = h->tune.img_rows_bwd;
   // rows per workgroup: 16 (four-set pipeline) below wide_rows, else the
   // widest the LDS allows (two-set pipeline)
-  const int want = wide ? (which == 0 ? 4 : h->wide_rt) : h->tc_rt;
-  iwae_handle::TcRec rec;
+  const int want = wide ? (which == 0 ? 4 : h->tune.wide_rt) : h->tune.tc_rt;
+  TcRec rec;
   for (int rt : {4, 2, 1}) {
     if (rt > want) continue;
     size_t mx = 0;
@@ -2153,7 +2201,7 @@ static int tc_run(iwae_handle* h, const Plan& P, const EpsSet& E, int which, con
                   const float* dlw = nullptr, const float* dpx = nullptr, bool unit = false) {
   auto it = h->tc_plans.find(tc_key(P, which));
   if (it == h->tc_plans.end()) return fail(h, IWAE_EINVAL, "engine plan missing");
-  const iwae_handle::TcRec& rec = it->second;
+  const TcRec& rec = it->second;
   TcArgs a;
   std::memset(&a, 0, sizeof(a));
   a.plan = rec.dev;
@@ -2171,7 +2219,7 @@ static int tc_run(iwae_handle* h, const Plan& P, const EpsSet& E, int which, con
   // fills more than the chip keeps the plain order)
   int njobs = 0;
   for (int j = 0; j < kTcMaxJobs; ++j) njobs += rec.nb[j] > 0;
-  if (h->tc_xcd && njobs > 1 && tot <= 256) {
+  if (h->tune.tc_xcd && njobs > 1 && tot <= 256) {
     int cnt[kTcMaxJobs] = {};
     for (int q = 0; q < kTcMaxJobs; ++q) cnt[q] = rec.nb[q] > 0;      // one XCD per job first
     for (int x = njobs; x < 8; ++x) {                                   // then the most loaded job
@@ -2202,63 +2250,74 @@ static int tc_run(iwae_handle* h, const Plan& P, const EpsSet& E, int which, con
     // this launch does not read: nothing samples in the backward)
     a.bnd = *bnd;
     a.bnd_rows = 1;
-    a.bnd_block = h->tc_xcd && a.xcd_slots > 0 ? 8 * a.xcd_slots : tot;
+    a.bnd_block = h->tune.tc_xcd && a.xcd_slots > 0 ? 8 * a.xcd_slots : tot;
     a.bnd_ld = r4(P.kS);
     a.bnd_lds = rec.acc_off + (2 + 4 * 8) * 16 * rec.rt;
     a.rng_base = nullptr;
   }
-  const bool prof = which <= 1 && h->prof_kind == 10 + which;
-  h->n_tc++;
-  if (h->defer_launch) {
+  const bool prof = which <= 1 && h->prof.kind == 10 + which;
+  h->count.tc++;
+  if (h->step.defer_launch) {
     // recorded for a combined launch (tcu_kernel); launch_pending issues it
-    h->pend_tc = a; h->pend_tc_rt = rec.rt; h->pend_tc_lds = rec.lds; h->pend_tc_have = true;
+    h->pend.tc = a; h->pend.tc_rt = rec.rt; h->pend.tc_lds = rec.lds; h->pend.tc_have = true;
     return IWAE_OK;
   }
   if (prof) {
-    if (h->prof_used + 2 > h->prof_ev.size()) {
+    if (h->prof.used + 2 > h->prof.ev.size()) {
       for (int i = 0; i < 256; ++i) {
         hipEvent_t e;
         HIPCHK(hipEventCreate(&e));
-        h->prof_ev.push_back(e);
+        h->prof.ev.push_back(e);
       }
     }
-    HIPCHK(hipEventRecord(h->prof_ev[h->prof_used], h->stream));
+    HIPCHK(hipEventRecord(h->prof.ev[h->prof.used], h->stream));
   }
   HIPCHK(launch_tc(h->stream, a, rec.rt, rec.lds));
   if (prof) {
-    HIPCHK(hipEventRecord(h->prof_ev[h->prof_used + 1], h->stream));
-    h->prof_used += 2;
-    h->prof_flop += rec.flop;
-    h->prof_have = true; h->prof_is_tc = true;
-    h->prof_tc = a; h->prof_tc_rt = rec.rt; h->prof_tc_lds = rec.lds; h->prof_flop1 = rec.flop;
+    HIPCHK(hipEventRecord(h->prof.ev[h->prof.used + 1], h->stream));
+    h->prof.used += 2;
+    h->prof.flop += rec.flop;
+    h->prof.have = true; h->prof.is_tc = true;
+    h->prof.tc = a; h->prof.tc_rt = rec.rt; h->prof.tc_lds = rec.lds; h->prof.flop1 = rec.flop;
     if (bnd) {
       // replays write the loss, Philox base and Adam step into scratch
-      if (!h->prof_scratch) HIPCHK(hipMalloc(&h->prof_scratch, 64 * sizeof(float)));
-      h->prof_tc.bnd.loss = h->prof_scratch;
-      h->prof_tc.bnd.rng_base = reinterpret_cast<uint64_t*>(h->prof_scratch + 8);
-      h->prof_tc.bnd.adam_step = bnd->adam_step ? reinterpret_cast<long long*>(h->prof_scratch + 16) : nullptr;
+      if (!h->prof.scratch) HIPCHK(hipMalloc(&h->prof.scratch, 64 * sizeof(float)));
+      h->prof.tc.bnd.loss = h->prof.scratch;
+      h->prof.tc.bnd.rng_base = reinterpret_cast<uint64_t*>(h->prof.scratch + 8);
+      h->prof.tc.bnd.adam_step = bnd->adam_step ? reinterpret_cast<long long*>(h->prof.scratch + 16) : nullptr;
     }
   }
   return IWAE_OK;
 }
 
-static float* train_loss_ptr(iwae_handle* h) { return h->loss_out ? h->loss_out : &h->ds->scalars[0]; }
+static float* train_loss_ptr(iwae_handle* h) { return h->step.loss_out ? h->step.loss_out : &h->ds->scalars[0]; }
 
 // End of a train step / forward_backward: sum the weight-gradient slabs into the
 // gradient buffer and (adam) step.  Data parallel (iwae_dp_init): the buffer gets
 // B_local * g and B_local in its tail element; with the library communicator the
 // n + 4 floats are summed over the ranks right here (ncclAllReduce on the step's
 // stream, inside the captured graph) and Adam scales by 1 / sum_r B_r.
+// sum count floats of the gradient buffer from offset over the ranks, in place, on the step's stream
+static int allreduce_grad(iwae_handle* h, long long offset, long long count, const char* what) {
+  if (ncclAllReduce(h->grad + offset, h->grad + offset, (size_t)count, ncclFloat32, ncclSum, h->comm, h->stream) !=
+      ncclSuccess)
+    return fail(h, IWAE_EHIP, std::string("ncclAllReduce of the gradient") + what + " failed");
+  return IWAE_OK;
+}
+
+// Data parallel: the slabs summed into B_local * g (B_local in the tail), then
+// (all_reduce: a step that applies Adam) the n + 4 floats summed over the ranks.
+static int dp_reduce_slabs(iwae_handle* h, const Plan& P, bool all_reduce) {
+  CHK(run_adam(h, true, true, false, (float)P.B, false, nullptr, h->grad + h->nparam_int));
+  if (!all_reduce) return IWAE_OK;
+  if (!h->comm) return fail(h, IWAE_EINVAL, "data parallel without a library communicator");
+  return allreduce_grad(h, 0, h->nparam_int + 4, "");
+}
+
 static int finish_step(iwae_handle* h, const Plan& P, bool adam) {
   if (!h->dp_weighted) return run_adam(h, true, true, adam, 1.f, false);
-  float* tail = h->grad + h->nparam_int;
-  CHK(run_adam(h, true, true, false, (float)P.B, false, nullptr, tail));
-  if (!adam) return IWAE_OK;
-  if (!h->comm) return fail(h, IWAE_EINVAL, "data parallel without a library communicator");
-  if (ncclAllReduce(h->grad, h->grad, (size_t)h->nparam_int + 4, ncclFloat32, ncclSum, h->comm, h->stream) !=
-      ncclSuccess)
-    return fail(h, IWAE_EHIP, "ncclAllReduce of the gradient failed");
-  return run_adam(h, false, true, true, 0.f, false, tail);
+  CHK(dp_reduce_slabs(h, P, adam));
+  return adam ? run_adam(h, false, true, true, 0.f, false, h->grad + h->nparam_int) : IWAE_OK;
 }
 
 // The bound inside the engine's backward launch (no bound launch): up to 256
@@ -2270,7 +2329,7 @@ static bool piwae_unit(const iwae_handle* h, const Plan& P, bool ring);
 // the weight gradients and the image-row job)
 static bool use_tc_bound(iwae_handle* h, const Plan& P, bool ring) {
   // (one spare workgroup runs the whole bound: up to 64 images, 8 per wave)
-  if (!h->tc_bound || P.kS > 256 || P.Bimg > 64 || P.need_bce || P.kl || h->prof_kind == 13) return false;
+  if (!h->tune.tc_bound || P.kS > 256 || P.Bimg > 64 || P.need_bce || P.kl || h->prof.kind == 13) return false;
   if (P.piwae && !piwae_unit(h, P, ring)) return false;
   auto it = h->tc_plans.find(tc_key(P, 1));
   if (it == h->tc_plans.end()) return false;
@@ -2292,7 +2351,7 @@ static bool nring_train_backward_enc(iwae_handle* h, const Plan& P, bool& ran);
 // the row-chain engine runs the backward (not the ring kernels) and the image-
 // row job takes the first encoder layer's backward.
 static bool piwae_unit(const iwae_handle* h, const Plan& P, bool ring) {
-  return P.piwae && !ring && (h->engine_img_bwd || (h->engine_img && !smallm_ok(h, P.Bimg))) && h->piwae_one;
+  return P.piwae && !ring && (h->tune.engine_img_bwd || (h->tune.engine_img && !smallm_ok(h, P.Bimg))) && h->tune.piwae_one;
 }
 // Issue the launches tc_run / run_update recorded under defer_launch: job I'
 // and the fused update as ONE tcu_kernel launch when every workgroup of it is
@@ -2300,61 +2359,61 @@ static bool piwae_unit(const iwae_handle* h, const Plan& P, bool ring) {
 // per CU: the update's 147 KiB of LDS), else as the two launches they would
 // have been.
 static int launch_pending(iwae_handle* h) {
-  const bool tc = h->pend_tc_have, up = h->pend_upd_have;
-  h->pend_tc_have = h->pend_upd_have = false;
+  const bool tc = h->pend.tc_have, up = h->pend.upd_have;
+  h->pend.tc_have = h->pend.upd_have = false;
   if (tc && up) {
-    const TcArgs& a = h->pend_tc;
-    const UpdArgs& u = h->pend_upd;
+    const TcArgs& a = h->pend.tc;
+    const UpdArgs& u = h->pend.upd;
     const int n_tc = a.block_start[kTcMaxJobs];
     const int grid = ((n_tc + 7) & ~7) + 8 * (u.per_xcd + u.per_xcd2);
     bool one_split = true;                         // (tcu_kernel's update has no split-K path)
     for (int j = 0; j < u.njobs; ++j) one_split = one_split && u.job[j].nsplit <= 1;
-    const bool ok = h->pend_tc_rt == 1 && a.xcd_slots == 0 && a.bnd_block < 0 && !u.search && !u.apply &&
-                    one_split && grid <= h->n_cu && n_tc > 0 && h->pend_upd_cons > 0;
+    const bool ok = h->pend.tc_rt == 1 && a.xcd_slots == 0 && a.bnd_block < 0 && !u.search && !u.apply &&
+                    one_split && grid <= h->n_cu && n_tc > 0 && h->pend.upd_cons > 0;
     if (ok) {
       UpdWait w;
-      w.ctr = h->tcu_ctr; w.err = h->err_dev; w.wait_mask = h->pend_upd_mask;
-      w.n_prod = n_tc; w.n_cons = h->pend_upd_cons;
+      w.ctr = h->tcu_ctr; w.err = h->err_dev; w.wait_mask = h->pend.upd_mask;
+      w.n_prod = n_tc; w.n_cons = h->pend.upd_cons;
       // (fault injection: wait for a producer that does not exist, briefly)
-      w.n_expect = n_tc + (h->tcu_wait_test ? 1 : 0);
-      w.max_spins = h->tcu_wait_test ? 4096u : (1u << 24);
+      w.n_expect = n_tc + (h->tune.tcu_wait_test ? 1 : 0);
+      w.max_spins = h->tune.tcu_wait_test ? 4096u : (1u << 24);
       // write-through hand-off where every waiting tile takes the update's
       // one-iteration path (its dZ loads are the sc1 ones): launch_tcu keeps it
       // only on the write-through instantiation
-      w.wt = h->tcu_wt;
+      w.wt = h->tune.tcu_wt;
       for (int j = 0; j < u.njobs; ++j)
         if ((w.wait_mask >> j) & 1u) w.wt = w.wt && u.job[j].rows > 0 && u.job[j].rows <= kUpdRowsPerIter;
-      const size_t lds = std::max(h->pend_tc_lds, upd_lds_bytes());
+      const size_t lds = std::max(h->pend.tc_lds, upd_lds_bytes());
       HIPCHK(launch_tcu(h->stream, a, u, w, lds));
-      h->n_tcu++;
-      if (h->prof_kind == 16 && !h->prof_have && u.do_adam) {
+      h->count.tcu++;
+      if (h->prof.kind == 16 && !h->prof.have && u.do_adam) {
         // live timing (iwae_profile_replay): replays repeat this launch with the
         // update part on scratch copies of the parameters, moments and
         // fragment-major copies (job I' rewrites its own outputs): the model is untouched
         const size_t pb = (size_t)h->nparam_int * sizeof(float), fb = (size_t)h->fx_elems * 2 * sizeof(__bf16);
-        if (h->prof_adam_bytes < 3 * pb + fb) {
-          if (h->prof_adam) HIPCHK(hipFree(h->prof_adam));
-          h->prof_adam = nullptr;
-          HIPCHK(hipMalloc(&h->prof_adam, 3 * pb + fb));
-          h->prof_adam_bytes = 3 * pb + fb;
+        if (h->prof.adam_bytes < 3 * pb + fb) {
+          if (h->prof.adam) HIPCHK(hipFree(h->prof.adam));
+          h->prof.adam = nullptr;
+          HIPCHK(hipMalloc(&h->prof.adam, 3 * pb + fb));
+          h->prof.adam_bytes = 3 * pb + fb;
         }
-        HIPCHK(hipMemcpyAsync(h->prof_adam, h->params, pb, hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(h->prof_adam + h->nparam_int, h->adam_m, pb, hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(h->prof_adam + 2 * h->nparam_int, h->adam_v, pb, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->prof.adam, h->params, pb, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->prof.adam + h->nparam_int, h->adam_m, pb, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->prof.adam + 2 * h->nparam_int, h->adam_v, pb, hipMemcpyDeviceToDevice, h->stream));
         UpdArgs r = u;
-        r.param = h->prof_adam; r.m = h->prof_adam + h->nparam_int; r.v = h->prof_adam + 2 * h->nparam_int;
-        r.fx_hi = reinterpret_cast<__bf16*>(h->prof_adam + 3 * h->nparam_int);
+        r.param = h->prof.adam; r.m = h->prof.adam + h->nparam_int; r.v = h->prof.adam + 2 * h->nparam_int;
+        r.fx_hi = reinterpret_cast<__bf16*>(h->prof.adam + 3 * h->nparam_int);
         r.fx_lo = r.fx_hi + h->fx_elems;
         const TcArgs ta = a;
-        h->prof_mem = [ta, r, w, lds](hipStream_t st) { return launch_tcu(st, ta, r, w, lds); };
-        h->prof_flop1 = 0.0;
-        h->prof_have = true;
+        h->prof.mem = [ta, r, w, lds](hipStream_t st) { return launch_tcu(st, ta, r, w, lds); };
+        h->prof.flop1 = 0.0;
+        h->prof.have = true;
       }
       return IWAE_OK;
     }
   }
-  if (tc) HIPCHK(launch_tc(h->stream, h->pend_tc, h->pend_tc_rt, h->pend_tc_lds));
-  if (up) HIPCHK(launch_update(h->stream, h->pend_upd));
+  if (tc) HIPCHK(launch_tc(h->stream, h->pend.tc, h->pend.tc_rt, h->pend.tc_lds));
+  if (up) HIPCHK(launch_update(h->stream, h->pend.upd));
   return IWAE_OK;
 }
 
@@ -2365,7 +2424,7 @@ static int engine_train_body(iwae_handle* h, const Plan& P, const EpsSet& E, boo
   // us against 12 + 21 us and the step 142.4 vs 139.9 us), above that the
   // image-row engine jobs (B = 512: 0.954 vs 0.985 ms per step against the
   // split-K GEMM + row-block kernels)
-  const bool img = h->engine_img && !smallm_ok(h, P.Bimg);
+  const bool img = h->tune.engine_img && !smallm_ok(h, P.Bimg);
   if (img) {
     // first encoder layer: input Dense (few-row / split-K), then its image-row engine job
     CHK(enc0_forward(h, P, true));
@@ -2393,7 +2452,7 @@ static int engine_train_body(iwae_handle* h, const Plan& P, const EpsSet& E, boo
     // (nring_bwd 3, the encoder / prior backward on nre_kernel too: sequential,
     // 0.574-0.577 vs 0.582-0.583 ms with nrb_kernel on the side stream -- the
     // two ring kernels hold a CU's LDS each and cannot share one)
-    const bool side = ring && h->nring_bwd == 2 && h->L >= 2;
+    const bool side = ring && h->tune.nring_bwd == 2 && h->L >= 2;
     if (side) {
       HIPCHK(hipEventRecord(h->ev_fork, h->stream));
       HIPCHK(hipStreamWaitEvent(h->side_stream, h->ev_fork, 0));
@@ -2426,33 +2485,27 @@ static int engine_train_body(iwae_handle* h, const Plan& P, const EpsSet& E, boo
   const bool unit = piwae_unit(h, P, ring);
   const float* enc_dlw = P.piwae ? h->dlw2 : nullptr;
   if (P.piwae && !unit) CHK(tc_run(h, P, E, 4, nullptr, h->dlw2, h->dpx2));
-  h->piwae_ks = unit;
-  struct KsReset {
-    iwae_handle* h;
-    ~KsReset() { h->piwae_ks = false; }
-  } ks_reset{h};
+  h->step.piwae_ks = unit;
   // (a second stream for the first encoder layer's backward beside the other
   // weight gradients measured slower inside the captured graph: sequential).
   // Its image-row job also at small batches (B = 20: step 128.1 -> 126.4 us
   // against the row-block Gaussian backward + two few-row launches)
-  const bool img_bwd = img || h->engine_img_bwd;
+  const bool img_bwd = img || h->tune.engine_img_bwd;
   // job I' and the fused update as one launch (tcu_kernel): recorded here,
   // issued by launch_pending below.  From 256 sample rows: below, the update's
   // sample-row tiles are too short to cover job I' and the in-launch hand-off
   // costs more than the launch boundary (configs[0], 100 rows: 0.0958 vs
   // 0.0968 ms per step as two launches; profiles/r06j_tcu_rows_ab.txt)
-  const bool tcu = img_bwd && h->tcu && use_update(h, P) && !h->dp_weighted && (h->prof_kind < 0 || h->prof_kind == 16) &&
+  const bool tcu = img_bwd && h->tune.tcu && use_update(h, P) && !h->dp_weighted && (h->prof.kind < 0 || h->prof.kind == 16) &&
                    (long long)P.Bimg * P.kS >= 256;
-  struct DeferReset {
-    iwae_handle* h;
-    ~DeferReset() { h->defer_launch = false; h->pend_tc_have = h->pend_upd_have = false; }
-  } defer_reset{h};
-  h->defer_launch = tcu;
+  h->step.defer_launch = tcu;
   if (img_bwd) CHK(tc_run(h, P, E, 3, nullptr, enc_dlw, nullptr, unit));
   else CHK(fused_encoder_bwd(h, P, P.piwae ? h->dlw2 : h->dlw, 0));
   if (use_update(h, P) && h->dp_weighted) {
     // data parallel: the fused gradient pass (B_local * g, B_local in the
-    // tail), the all-reduce, then Adam and the fragment-major copies
+    // tail), the all-reduce, then Adam and the fragment-major copies.  (Not
+    // dp_reduce_slabs: the gradients come from two update launches on two
+    // streams and are reduced in two buckets, not from one sum of the slabs.)
     float* tail = h->grad + h->nparam_int;
     if (!adam) return run_update(h, P, false, 0, nullptr, (float)P.B, tail);
     if (!h->comm) return fail(h, IWAE_EINVAL, "data parallel without a library communicator");
@@ -2470,12 +2523,9 @@ static int engine_train_body(iwae_handle* h, const Plan& P, const EpsSet& E, boo
     CHK(run_update(h, P, false, 2, h->side_stream, (float)P.B, nullptr));
     HIPCHK(hipEventRecord(h->ev_join, h->side_stream));
     CHK(run_update(h, P, false, 1, nullptr, (float)P.B, tail));
-    if (ncclAllReduce(h->grad + o0, h->grad + o0, (size_t)(h->nparam_int - o0) + 4, ncclFloat32, ncclSum, h->comm,
-                      h->stream) != ncclSuccess)
-      return fail(h, IWAE_EHIP, "ncclAllReduce of the gradient (output MLP bucket) failed");
+    CHK(allreduce_grad(h, o0, h->nparam_int - o0 + 4, " (output MLP bucket)"));
     HIPCHK(hipStreamWaitEvent(h->stream, h->ev_join, 0));
-    if (ncclAllReduce(h->grad, h->grad, (size_t)o0, ncclFloat32, ncclSum, h->comm, h->stream) != ncclSuccess)
-      return fail(h, IWAE_EHIP, "ncclAllReduce of the gradient failed");
+    CHK(allreduce_grad(h, 0, o0, ""));
     CHK(run_update(h, P, true, 0, nullptr, 1.f, nullptr, false, true, tail));
     h->fx_version = h->params_version;
     return IWAE_OK;
@@ -2483,28 +2533,23 @@ static int engine_train_body(iwae_handle* h, const Plan& P, const EpsSet& E, boo
   if (use_update(h, P)) {
     // weight gradients, Adam and the fragment-major copies in one launch
     CHK(run_update(h, P, adam));
-    h->defer_launch = false;
+    h->step.defer_launch = false;
     CHK(launch_pending(h));
     if (adam) h->fx_version = h->params_version;
     return IWAE_OK;
   }
-  if (use_update_slabs(h, P) && h->dw_wide) CHK(run_dw(h, P));
+  if (use_update_slabs(h, P) && h->tune.dw_wide) CHK(run_dw(h, P));
   else if (use_update_slabs(h, P)) CHK(run_update(h, P, false, 0, nullptr, 1.f, nullptr, true));
   else CHK(weight_grads(h, P, true, true, h->dpx));
-  if (h->dp_weighted && adam && h->upd && upd_tiles_ok(h)) {
-    // data parallel: the slabs summed into B_local * g (+ tail), the
-    // all-reduce, then Adam + the FX / GX copies in one update launch
-    float* tail = h->grad + h->nparam_int;
-    CHK(run_adam(h, true, true, false, (float)P.B, false, nullptr, tail));
-    if (!h->comm) return fail(h, IWAE_EINVAL, "data parallel without a library communicator");
-    if (ncclAllReduce(h->grad, h->grad, (size_t)h->nparam_int + 4, ncclFloat32, ncclSum, h->comm, h->stream) !=
-        ncclSuccess)
-      return fail(h, IWAE_EHIP, "ncclAllReduce of the gradient failed");
-    CHK(run_update(h, P, true, 0, nullptr, 1.f, nullptr, false, true, tail));
+  if (h->dp_weighted && adam && h->tune.upd && upd_tiles_ok(h)) {
+    // data parallel: as finish_step, but Adam + the FX / GX copies in one
+    // update launch (apply mode) in place of the Adam and FX-refresh launches
+    CHK(dp_reduce_slabs(h, P, true));
+    CHK(run_update(h, P, true, 0, nullptr, 1.f, nullptr, false, true, h->grad + h->nparam_int));
     h->fx_version = h->params_version;
     return IWAE_OK;
   }
-  if (adam && !h->dp_weighted && h->upd && h->upd_apply && upd_tiles_ok(h) && h->slabs) {
+  if (adam && !h->dp_weighted && h->tune.upd && h->tune.upd_apply && upd_tiles_ok(h) && h->slabs) {
     // the slabs summed, Adam and the fragment-major copies in one launch (the
     // update kernel's apply mode) in place of adam_kernel + fx_refresh_kernel
     CHK(run_update(h, P, true, 0, nullptr, 1.f, nullptr, false, true, nullptr, true));
@@ -2542,8 +2587,8 @@ static int train_body(iwae_handle* h, const Plan& P, const EpsSet& E, bool adam)
   if (use_engine(h, P)) return engine_train_body(h, P, E, adam);
   // large batches: the output layer's forward (Bernoulli) and dX GEMMs on bf16x3
   // products of a split copy refreshed here, after the previous step's Adam
-  h->out_x3 = h->x3 && h->out_x3_rows > 0 && (long long)P.Bimg * P.kS >= h->out_x3_rows;
-  if (h->out_x3) CHK(run_wsplit_seg(h, h->o3));
+  h->step.out_x3 = h->x3 && h->tune.out_x3_rows > 0 && (long long)P.Bimg * P.kS >= h->tune.out_x3_rows;
+  if (h->step.out_x3) CHK(run_wsplit_seg(h, h->o3));
   if (use_fused(h, P)) return fused_train_body(h, P, E, adam);
   CHK(forward_core(h, P, E, true));
   CHK(run_bound(h, P, true, -1.f, train_loss_ptr(h), adam));
@@ -2562,11 +2607,11 @@ static int train_body(iwae_handle* h, const Plan& P, const EpsSet& E, bool adam)
 // launches' 32 images) reads the caller's x itself: a virtual ones column at
 // x_dim (a multiple of 4 floats), and it fills x_in for the later readers.
 static bool gemm_direct(const iwae_handle* h, const Plan& P) {
-  return h->x_direct && use_engine(h, P) && !smallm_ok(h, P.Bimg) && h->xdim % 4 == 0;
+  return h->tune.x_direct && use_engine(h, P) && !smallm_ok(h, P.Bimg) && h->xdim % 4 == 0;
 }
 
 // re-point a captured input-layer launch at x
-static hipError_t repoint_x(hipGraphExec_t exec, hipGraphNode_t node, const iwae_handle::XLaunch& xa, const float* x) {
+static hipError_t repoint_x(hipGraphExec_t exec, hipGraphNode_t node, const XLaunch& xa, const float* x) {
   hipKernelNodeParams kp;
   hipError_t e = hipGraphKernelNodeGetParams(node, &kp);
   if (e != hipSuccess) return e;
@@ -2580,6 +2625,92 @@ static hipError_t repoint_x(hipGraphExec_t exec, hipGraphNode_t node, const iwae
   return hipGraphExecKernelNodeSetParams(exec, node, &kp);
 }
 
+// re-point step j's input-layer launch at the batch x + j * xstride, where it moved
+static int repoint_batches(iwae_handle* h, GraphRec& g, const float* x, long long xstride) {
+  for (size_t j = 0; j < g.xs_node.size(); ++j) {
+    const float* xj = x + (long long)j * xstride;
+    if (g.xs_cap[j] == xj) continue;
+    HIPCHK(repoint_x(g.exec, g.xs_node[j], g.xs_args[j], xj));
+    g.xs_cap[j] = xj;
+  }
+  return IWAE_OK;
+}
+
+// Graph key of a train-step graph: kind (0 forward_backward, 1 train step, 2
+// multi-step), the loss config (p, alpha, beta by their bits) and the batch,
+// with the kind's own entries (rest) before the float bits.
+static std::vector<long long> graph_key(long long kind, const iwae_loss_config* lc, int B,
+                                        std::initializer_list<long long> rest) {
+  std::vector<long long> key = {kind, lc->loss, B, lc->k, lc->k1, lc->k2};
+  key.insert(key.end(), rest);
+  for (float f : {lc->p, lc->alpha, lc->beta}) {
+    int bits;
+    std::memcpy(&bits, &f, 4);
+    key.push_back(bits);
+  }
+  return key;
+}
+
+// Capture body on the handle's stream into an executable graph stored under
+// key (counted in n_captures, iwae_debug_count id 7).  body issues the work
+// and fills the record's re-pointable nodes; when it or the capture fails no
+// graph is left behind.
+static int capture_graph(iwae_handle* h, const std::vector<long long>& key,
+                         const std::function<int(GraphRec&)>& body, GraphRec** out) {
+  GraphRec g;
+  h->step.capturing = true;
+  HIPCHK(hipStreamBeginCapture(h->stream, hipStreamCaptureModeRelaxed));
+  const int rc = body(g);
+  const hipError_t ec = hipStreamEndCapture(h->stream, &g.graph);
+  h->step.capturing = false;
+  if (rc != IWAE_OK || ec != hipSuccess) {
+    if (ec == hipSuccess) destroy_graph(g);
+    if (rc != IWAE_OK) return rc;
+    HIPCHK(ec);
+  }
+  hipError_t ei = hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0);
+  if (ei != hipSuccess) g.exec = nullptr;
+  // the executable graph's device-side setup now (prepare_only included), not
+  // inside the first replay of the call that is timed
+  else ei = hipGraphUpload(g.exec, h->stream);
+  if (ei != hipSuccess) {
+    destroy_graph(g);
+    HIPCHK(ei);
+  }
+  h->count.captures++;
+  *out = &h->graphs.emplace(key, std::move(g)).first->second;
+  return IWAE_OK;
+}
+
+// One train step inside a capture.  Where its first kernel reads the caller's
+// x (x_user), that launch goes into the record for re-pointing.
+static int capture_step(iwae_handle* h, const Plan& P, const EpsSet& E, bool adam, GraphRec& g) {
+  h->step.cap_x_node = nullptr;
+  CHK(train_body(h, P, E, adam));
+  if (!h->step.x_user) return IWAE_OK;
+  if (!h->step.cap_x_node) return fail(h, IWAE_EHIP, "train-step capture: input-layer launch not found");
+  g.xs_node.push_back(h->step.cap_x_node);
+  g.xs_args.push_back(h->step.cap_x_args);
+  g.xs_cap.push_back(h->step.x_user);
+  return IWAE_OK;
+}
+
+// What an engine step reads that must exist before it (and before a capture):
+// current fragment-major copies (the step itself refreshes them after its
+// Adam), the engine plans of this shape and the ring kernels' unit tables.
+static int prepare_engine(iwae_handle* h, const Plan& P) {
+  CHK(ensure_fx(h));
+  CHK(tc_prepare(h, P));
+  NrLaunch nr;
+  NrbLaunch nb;
+  NreLaunch ne;
+  if (nring_plan(h, nr) && nrb_plan(h, nb) && h->L >= 2) {
+    CHK(tc_prepare_one(h, P, 5));
+    (void)nre_plan(h, ne);
+  }
+  return IWAE_OK;
+}
+
 static int do_train(iwae_handle* h, const iwae_loss_config* lc, const float* x, int B,
                     const float* const* eps, int n_eps, float* loss_dev, bool adam) {
   if (!x) return fail(h, IWAE_EINVAL, "x is NULL");
@@ -2591,185 +2722,68 @@ static int do_train(iwae_handle* h, const iwae_loss_config* lc, const float* x, 
   EpsSet E;
   CHK(parse_eps(h, P, eps, n_eps, E));
   CHK(ensure_capacity(h, P.Bimg, P.Bimg * P.kS, true));
+  const bool engine = use_engine(h, P);
+  if (engine) CHK(prepare_engine(h, P));
   // the fused step's first kernel reads the caller's x itself (and fills x_in);
   // every other path stages x into x_in first
-  const bool engine = use_engine(h, P);
-  if (engine) {
-    // fragment-major copies current before the step; the step itself refreshes them after its Adam
-    CHK(ensure_fx(h));
-    CHK(tc_prepare(h, P));
-    NrLaunch nr;                        // the ring kernels' unit tables: allocated here, not inside a capture
-    NrbLaunch nb;
-    NreLaunch ne;
-    if (nring_plan(h, nr) && nrb_plan(h, nb) && h->L >= 2) {
-      CHK(tc_prepare_one(h, P, 5));
-      (void)nre_plan(h, ne);
-    }
-  }
   const bool direct = P.Bimg == P.B && (((engine || use_fused(h, P)) && smallm_ok(h, P.Bimg)) || gemm_direct(h, P));
   if (!direct) CHK(copy_x(h, P, x));
-  h->x_user = direct ? x : nullptr;
+  StepScope scope{h};
+  h->step.x_user = direct ? x : nullptr;
   const bool philox = (E.a[0] == nullptr);
-  h->loss_out = loss_dev;
-  h->in_train_step = true;
-  struct Reset {
-    iwae_handle* h;
-    ~Reset() { h->in_train_step = false; h->out_x3 = false; h->x_user = nullptr; h->capturing = false; }
-  } reset_flag{h};
-  if (h->use_graphs && philox && h->prof_kind < 0) {
-    std::vector<long long> key = {adam ? 1 : 0, lc->loss, B, lc->k, lc->k1, lc->k2, (long long)(uintptr_t)loss_dev,
-                                  direct ? 1 : 0, engine ? 1 : 0};
-    float fk[3] = {lc->p, lc->alpha, lc->beta};
-    for (float f : fk) {
-      int bits;
-      std::memcpy(&bits, &f, 4);
-      key.push_back(bits);
-    }
-    auto it = h->graphs.find(key);
-    if (it == h->graphs.end()) {
-      hipGraph_t graph;
-      h->capturing = true;
-      h->cap_x_node = nullptr;
-      HIPCHK(hipStreamBeginCapture(h->stream, hipStreamCaptureModeRelaxed));
-      int rc = train_body(h, P, E, adam);
-      hipError_t ec = hipStreamEndCapture(h->stream, &graph);
-      h->capturing = false;
-      if (rc != IWAE_OK || ec != hipSuccess) {
-        if (ec == hipSuccess && graph) (void)hipGraphDestroy(graph);
-        if (rc != IWAE_OK) return rc;
-        HIPCHK(ec);
-      }
-      iwae_handle::GraphRec g;
-      g.graph = graph;
-      hipError_t ei = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
-      if (ei != hipSuccess) g.exec = nullptr;
-      // the executable graph's device-side setup now, not inside its first replay
-      else ei = hipGraphUpload(g.exec, h->stream);
-      if (ei != hipSuccess) {
-        destroy_graph(g);
-        HIPCHK(ei);
-      }
-      h->n_captures++;
-      if (direct) {
-        if (!h->cap_x_node) {
-          destroy_graph(g);
-          return fail(h, IWAE_EHIP, "train-step capture: input-layer launch not found");
-        }
-        g.x_node = h->cap_x_node;
-        g.x_args = h->cap_x_args;
-        g.x_cap = x;
-      }
-      it = h->graphs.emplace(key, g).first;
-    }
-    iwae_handle::GraphRec& g = it->second;
-    if (g.x_node && g.x_cap != x) {
-      // re-point the input-layer launch at this call's x
-      HIPCHK(repoint_x(g.exec, g.x_node, g.x_args, x));
-      g.x_cap = x;
-    }
-    HIPCHK(hipGraphLaunch(g.exec, h->stream));
-    // the replayed Adam moved the parameters: the split (bf16x3) copies the
-    // evaluation paths read are stale from here (run_adam's bump only ran at capture)
-    if (adam) {
-      h->params_version++;
-      if (engine) h->fx_version = h->params_version;   // the replayed step refreshed the fragment-major copies
-    }
-  } else {
-    CHK(train_body(h, P, E, adam));
+  h->step.loss_out = loss_dev;
+  h->step.in_train_step = true;
+  if (!(h->use_graphs && philox && h->prof.kind < 0)) return train_body(h, P, E, adam);
+  const auto key = graph_key(adam ? 1 : 0, lc, B, {(long long)(uintptr_t)loss_dev, direct ? 1 : 0, engine ? 1 : 0});
+  auto it = h->graphs.find(key);
+  GraphRec* g = it == h->graphs.end() ? nullptr : &it->second;
+  if (!g) CHK(capture_graph(h, key, [&](GraphRec& r) { return capture_step(h, P, E, adam, r); }, &g));
+  CHK(repoint_batches(h, *g, x, 0));
+  HIPCHK(hipGraphLaunch(g->exec, h->stream));
+  // the replayed Adam moved the parameters: the split (bf16x3) copies the
+  // evaluation paths read are stale from here (run_adam's bump only ran at capture)
+  if (adam) {
+    h->params_version++;
+    if (engine) h->fx_version = h->params_version;   // the replayed step refreshed the fragment-major copies
   }
   return IWAE_OK;
 }
 
-// consecutive Philox train steps on the batches x + i * B * x_dim (fit's loop,
-// E:82): graphs of up to kGraphSteps captured steps, so consecutive steps run
-// without the per-graph launch gap; step j of a graph reads its own batch (its
-// input-layer launch re-pointed when the batch moves) and writes its loss to
-// loss_slots[j], copied to loss_dev + i by the graph's last node.  Anything the
-// multi-step graph does not cover (no graphs, staged x, data parallel, live
-// profiling) runs as nsteps single steps.
 static constexpr int kGraphSteps = 32;
 
-// The graph of S consecutive steps from batch xi (captured on first use; a
-// capture is counted in n_captures, iwae_debug_count id 7).
+// The graph of S consecutive steps from batch xi, captured on first use.
 static int steps_graph(iwae_handle* h, const iwae_loss_config* lc, const Plan& P, const EpsSet& E, int B, int S,
-                       const float* xi, iwae_handle::GraphRec** out) {
-  const long long xstride = (long long)B * h->xdim;
-  std::vector<long long> key = {2, lc->loss, B, lc->k, lc->k1, lc->k2, S, 1};
-  float fk[3] = {lc->p, lc->alpha, lc->beta};
-  for (float f : fk) {
-    int bits;
-    std::memcpy(&bits, &f, 4);
-    key.push_back(bits);
-  }
+                       const float* xi, GraphRec** out) {
+  const auto key = graph_key(2, lc, B, {S, 1});
   auto it = h->graphs.find(key);
-  if (it == h->graphs.end()) {
-    iwae_handle::GraphRec g;
-    hipGraph_t graph = nullptr;
-    h->capturing = true;
-    HIPCHK(hipStreamBeginCapture(h->stream, hipStreamCaptureModeRelaxed));
-    int rc = IWAE_OK;
-    for (int j = 0; j < S && rc == IWAE_OK; ++j) {
-      h->x_user = xi + j * xstride;
-      h->loss_out = h->loss_slots + j;
-      h->cap_x_node = nullptr;
-      rc = train_body(h, P, E, true);
-      g.xs_node.push_back(h->cap_x_node);
-      g.xs_args.push_back(h->cap_x_args);
-      g.xs_cap.push_back(h->x_user);
-    }
-    if (rc == IWAE_OK) {
-      // the losses' copy as the graph's last node (a copy after the graph was a
-      // launch of its own: +9 us gap and 4 us per call, profiles/r05q_train_step_timeline.txt);
-      // captured into the no-losses sink, re-pointed per call
-      g.loss_cap = h->loss_slots + kGraphSteps;
-      hipError_t em = hipMemcpyAsync(g.loss_cap, h->loss_slots, S * sizeof(float), hipMemcpyDeviceToDevice, h->stream);
-      hipStreamCaptureStatus cs;
-      unsigned long long cid;
-      hipGraph_t cg;
-      const hipGraphNode_t* deps = nullptr;
-      size_t nd = 0;
-      if (em == hipSuccess) em = hipStreamGetCaptureInfo_v2(h->stream, &cs, &cid, &cg, &deps, &nd);
-      if (em != hipSuccess) rc = fail(h, IWAE_EHIP, "multi-step capture: the losses' copy");
-      else g.loss_node = nd == 1 ? deps[0] : nullptr;
-    }
-    const hipError_t ec = hipStreamEndCapture(h->stream, &graph);
-    h->capturing = false;
-    if (rc != IWAE_OK || ec != hipSuccess) {
-      if (ec == hipSuccess && graph) (void)hipGraphDestroy(graph);
-      if (rc != IWAE_OK) return rc;
-      HIPCHK(ec);
-    }
-    g.graph = graph;
-    hipError_t ei = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
-    if (ei != hipSuccess) g.exec = nullptr;
-    // the executable graph's device-side setup now (prepare_only included), not
-    // inside the first replay of the call that is timed
-    else ei = hipGraphUpload(g.exec, h->stream);
-    if (ei != hipSuccess) {
-      destroy_graph(g);
-      HIPCHK(ei);
-    }
-    for (hipGraphNode_t n : g.xs_node)
-      if (!n) {
-        destroy_graph(g);
-        return fail(h, IWAE_EHIP, "multi-step capture: input-layer launch not found");
-      }
-    if (!g.loss_node) {
-      destroy_graph(g);
-      return fail(h, IWAE_EHIP, "multi-step capture: the losses' copy node not found");
-    }
-    h->n_captures++;
-    it = h->graphs.emplace(key, g).first;
+  if (it != h->graphs.end()) {
+    *out = &it->second;
+    return IWAE_OK;
   }
-  *out = &it->second;
-  return IWAE_OK;
+  return capture_graph(h, key, [&](GraphRec& g) -> int {
+    for (int j = 0; j < S; ++j) {
+      h->step.x_user = xi + j * (long long)B * h->xdim;
+      h->step.loss_out = h->loss_slots + j;
+      CHK(capture_step(h, P, E, true, g));
+    }
+    // the losses' copy as the graph's last node (a copy after the graph was a
+    // launch of its own: +9 us gap and 4 us per call, profiles/r05q_train_step_timeline.txt);
+    // captured into the no-losses sink, re-pointed per call
+    g.loss_cap = h->loss_slots + kGraphSteps;
+    if (hipMemcpyAsync(g.loss_cap, h->loss_slots, S * sizeof(float), hipMemcpyDeviceToDevice, h->stream) !=
+            hipSuccess ||
+        last_captured_node(h, &g.loss_node) != IWAE_OK)
+      return fail(h, IWAE_EHIP, "multi-step capture: the losses' copy");
+    if (!g.loss_node) return fail(h, IWAE_EHIP, "multi-step capture: the losses' copy node not found");
+    return IWAE_OK;
+  }, out);
 }
 
 // consecutive Philox train steps on the batches x + i * B * x_dim (fit's loop,
 // E:82): graphs of up to kGraphSteps captured steps, so consecutive steps run
 // without the per-graph launch gap; step j of a graph reads its own batch (its
 // input-layer launch re-pointed when the batch moves) and writes its loss to
-// loss_slots[j], copied to loss_dev + i after the graph.  Data parallel with
+// loss_slots[j], copied to loss_dev + i by the graph's last node.  Data parallel with
 // the library communicator: each captured step carries its all-reduces.
 // Anything the multi-step graph does not cover (no graphs, staged x, data
 // parallel without the library communicator, live profiling) runs as nsteps
@@ -2782,7 +2796,7 @@ static int do_train_steps(iwae_handle* h, const iwae_loss_config* lc, const floa
   if (nsteps < 0) return fail(h, IWAE_EINVAL, "nsteps must be >= 0");
   if (nsteps == 0) return IWAE_OK;
   const long long xstride = (long long)B * h->xdim;
-  const bool multi = nsteps > 1 && h->use_graphs && h->prof_kind < 0 && (!h->dp_weighted || h->comm);
+  const bool multi = nsteps > 1 && h->use_graphs && h->prof.kind < 0 && (!h->dp_weighted || h->comm);
   // (single steps write the loss to the handle's scalar, then copy it: one
   // captured graph per shape, not one per loss address)
   auto single = [&]() -> int {
@@ -2805,30 +2819,15 @@ static int do_train_steps(iwae_handle* h, const iwae_loss_config* lc, const floa
   // paths decide their split-copy refreshes on the host at capture time)
   const bool direct = P.Bimg == P.B && ((engine && smallm_ok(h, P.Bimg)) || gemm_direct(h, P));
   if (!direct) return single();
-  {
-    CHK(ensure_fx(h));
-    CHK(tc_prepare(h, P));
-    NrLaunch nr;
-    NrbLaunch nb;
-    NreLaunch ne;
-    if (nring_plan(h, nr) && nrb_plan(h, nb) && h->L >= 2) {
-      CHK(tc_prepare_one(h, P, 5));
-      (void)nre_plan(h, ne);
-    }
-  }
+  CHK(prepare_engine(h, P));
   if (!h->loss_slots) HIPCHK(hipMalloc(&h->loss_slots, 2 * kGraphSteps * sizeof(float)));
-  h->in_train_step = true;
+  StepScope scope{h};
+  h->step.in_train_step = true;
   const long long pv = h->params_version, wv = h->wsplit_version, fv = h->fx_version;
-  struct Reset {
-    iwae_handle* h;
-    ~Reset() {
-      h->in_train_step = false; h->out_x3 = false; h->x_user = nullptr; h->capturing = false; h->loss_out = nullptr;
-    }
-  } reset_flag{h};
   for (int i0 = 0, S = 0; i0 < nsteps; i0 += S) {
     S = std::min(kGraphSteps, nsteps - i0);
     const float* xi = x + i0 * xstride;
-    iwae_handle::GraphRec* gp = nullptr;
+    GraphRec* gp = nullptr;
     CHK(steps_graph(h, lc, P, E, B, S, xi, &gp));
     if (prepare_only) {
       // a capture bumps the host's parameter versions as if it had run: undo
@@ -2837,13 +2836,8 @@ static int do_train_steps(iwae_handle* h, const iwae_loss_config* lc, const floa
       h->fx_version = fv;
       continue;
     }
-    iwae_handle::GraphRec& g = *gp;
-    for (int j = 0; j < S; ++j) {
-      const float* xj = xi + j * xstride;
-      if (g.xs_cap[j] == xj) continue;
-      HIPCHK(repoint_x(g.exec, g.xs_node[j], g.xs_args[j], xj));
-      g.xs_cap[j] = xj;
-    }
+    GraphRec& g = *gp;
+    CHK(repoint_batches(h, g, xi, xstride));
     float* ldst = loss_dev ? loss_dev + i0 : h->loss_slots + kGraphSteps;
     if (g.loss_cap != ldst) {
       HIPCHK(hipGraphExecMemcpyNodeSetParams1D(g.exec, g.loss_node, ldst, h->loss_slots, S * sizeof(float),
@@ -2855,6 +2849,22 @@ static int do_train_steps(iwae_handle* h, const iwae_loss_config* lc, const floa
     h->fx_version = h->params_version;   // every replayed step refreshed the fragment-major copies
   }
   return IWAE_OK;
+}
+
+// Tail of the three ring planners: the unit table uploaded once (device,
+// built once: FX / GX offsets are fixed per model) and the launch pointed at
+// it and at the fragment-major copies.
+template <class Launch>
+static bool ring_plan_tail(iwae_handle* h, NrUnit*& dev, int cap, const std::vector<NrUnit>& units, Launch& R) {
+  if (!dev) {
+    if (hipMalloc(&dev, cap * sizeof(NrUnit)) != hipSuccess) return false;
+    if (hipMemcpy(dev, units.data(), units.size() * sizeof(NrUnit), hipMemcpyHostToDevice) != hipSuccess)
+      return false;
+  }
+  R.units = dev;
+  R.fx_hi = h->fx_hi; R.fx_lo = h->fx_lo;
+  R.fx_bytes = (unsigned)(h->fx_elems * (long long)sizeof(__bf16));
+  return true;
 }
 
 // ---------------------------------------------------------------- ABI
@@ -2981,7 +2991,7 @@ void iwae_destroy(iwae_handle* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   free_workspace(h);
   if (h->comm) (void)ncclCommDestroy(h->comm);
-  for (auto e : h->prof_ev) (void)hipEventDestroy(e);
+  for (auto e : h->prof.ev) (void)hipEventDestroy(e);
   if (h->params) (void)hipFree(h->params);
   if (h->adam_m) (void)hipFree(h->adam_m);
   if (h->adam_v) (void)hipFree(h->adam_v);
@@ -2995,8 +3005,8 @@ void iwae_destroy(iwae_handle* h) {
   if (h->nre_units) (void)hipFree(h->nre_units);
   if (h->wsplit_hi) (void)hipFree(h->wsplit_hi);
   if (h->fx_hi) (void)hipFree(h->fx_hi);
-  if (h->prof_scratch) (void)hipFree(h->prof_scratch);
-  if (h->prof_adam) (void)hipFree(h->prof_adam);
+  if (h->prof.scratch) (void)hipFree(h->prof.scratch);
+  if (h->prof.adam) (void)hipFree(h->prof.adam);
   if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
   if (h->side_stream) (void)hipStreamDestroy(h->side_stream);
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
@@ -3049,8 +3059,7 @@ static uint64_t splitmix64(uint64_t z) {
 // sharded NLL between steps keeps drawing fresh noise).
 static void derive_key(iwae_handle* h) {
   h->seed = h->noise_stream == 0 ? h->user_seed : splitmix64(h->user_seed ^ splitmix64(h->noise_stream));
-  for (auto& kv : h->graphs) destroy_graph(kv.second);   // the key is a captured kernel argument
-  h->graphs.clear();
+  invalidate_graphs(h);                  // the key is a captured kernel argument
 }
 
 int iwae_set_noise_stream(iwae_handle* h, unsigned long long stream) {
@@ -3087,8 +3096,7 @@ int iwae_set_path(iwae_handle* h, int path) {
     return fail(h, IWAE_EINVAL, "path must be 0 (auto), 1 (layer-wise), 2 (fused row-block) or 3 (engine)");
   h->path = path;
   h->nll_fused = path != 1;             // layer-wise everywhere when asked for
-  for (auto& kv : h->graphs) destroy_graph(kv.second);
-  h->graphs.clear();
+  invalidate_graphs(h);
   return IWAE_OK;
 }
 
@@ -3096,8 +3104,7 @@ int iwae_set_precision(iwae_handle* h, int mode) {
   if (!h) return IWAE_EINVAL;
   if (mode != 0 && mode != 1) return fail(h, IWAE_EINVAL, "precision must be 0 (f32 MFMA) or 1 (bf16x3)");
   h->x3 = mode;
-  for (auto& kv : h->graphs) destroy_graph(kv.second);
-  h->graphs.clear();
+  invalidate_graphs(h);
   return IWAE_OK;
 }
 
@@ -3114,63 +3121,61 @@ int iwae_set_tuning(iwae_handle* h, int knob, long long value) {
   // the plan tables that some knobs free below
   HIPCHK(hipStreamSynchronize(h->stream));
   switch (knob) {
-    case IWAE_KNOB_ENGINE: h->engine = on; break;
-    case IWAE_KNOB_TC_IMG: h->engine_img = on; break;
-    case IWAE_KNOB_TC_IMGBWD: h->engine_img_bwd = on; break;
-    case IWAE_KNOB_TC_FOLD0: h->engine_fold0 = on; break;
-    case IWAE_KNOB_TC_XCD: h->tc_xcd = on; break;
-    case IWAE_KNOB_TC_BOUND: h->tc_bound = on; break;
+    case IWAE_KNOB_ENGINE: h->tune.engine = on; break;
+    case IWAE_KNOB_TC_IMG: h->tune.engine_img = on; break;
+    case IWAE_KNOB_TC_IMGBWD: h->tune.engine_img_bwd = on; break;
+    case IWAE_KNOB_TC_FOLD0: h->tune.engine_fold0 = on; break;
+    case IWAE_KNOB_TC_XCD: h->tune.tc_xcd = on; break;
+    case IWAE_KNOB_TC_BOUND: h->tune.tc_bound = on; break;
     case IWAE_KNOB_TC_RT:
       if (value != 1 && value != 2 && value != 4) return fail(h, IWAE_EINVAL, "TC_RT must be 1, 2 or 4");
-      h->tc_rt = (int)value;
+      h->tune.tc_rt = (int)value;
       break;
-    case IWAE_KNOB_UPD: h->upd = on; break;
-    case IWAE_KNOB_TCU_WAIT_TEST: h->tcu_wait_test = on; break;
-    case IWAE_KNOB_TCU_WT: h->tcu_wt = on; break;
-    case IWAE_KNOB_UPD_ROWS: h->upd_rows = std::max(0LL, value); break;
-    case IWAE_KNOB_UPD_SLABS: h->upd_slabs = on; break;
-    case IWAE_KNOB_UPD_SLAB_WG: h->upd_slab_wg = std::max(1LL, value); break;
+    case IWAE_KNOB_UPD: h->tune.upd = on; break;
+    case IWAE_KNOB_TCU_WAIT_TEST: h->tune.tcu_wait_test = on; break;
+    case IWAE_KNOB_TCU_WT: h->tune.tcu_wt = on; break;
+    case IWAE_KNOB_UPD_ROWS: h->tune.upd_rows = std::max(0LL, value); break;
+    case IWAE_KNOB_UPD_SLABS: h->tune.upd_slabs = on; break;
+    case IWAE_KNOB_UPD_SLAB_WG: h->tune.upd_slab_wg = std::max(1LL, value); break;
     case IWAE_KNOB_DW_TARGET:
-      h->dw_target = std::max(1LL, value);
+      h->tune.dw_target = std::max(1LL, value);
       free_workspace(h);                 // the slab layout depends on it
       break;
-    case IWAE_KNOB_SMALLM_ROWS: h->smallm_rows = (int)std::max(0LL, std::min(value, 32LL)); break;
-    case IWAE_KNOB_OUT_X3_ROWS: h->out_x3_rows = std::max(0LL, value); break;
+    case IWAE_KNOB_SMALLM_ROWS: h->tune.smallm_rows = (int)std::max(0LL, std::min(value, 32LL)); break;
+    case IWAE_KNOB_OUT_X3_ROWS: h->tune.out_x3_rows = std::max(0LL, value); break;
     case IWAE_KNOB_MG_WAVES:
       if (value != 4 && value != 8) return fail(h, IWAE_EINVAL, "MG_WAVES must be 4 or 8");
-      h->mg_waves = (int)value;
+      h->tune.mg_waves = (int)value;
       break;
-    case IWAE_KNOB_NLL_ROWS: h->nll_rows = std::max(1LL, value); break;
-    case IWAE_KNOB_NLL_IMGS: h->nll_imgs = (int)std::max(0LL, std::min(value, 1LL << 20)); break;
-    case IWAE_KNOB_WIDE_ROWS: h->wide_rows = std::max(0LL, value); break;
-    case IWAE_KNOB_DW_WIDE: h->dw_wide = on; break;
-    case IWAE_KNOB_DW_WG: h->dw_wg = (int)std::max(8LL, std::min(value, 4096LL)); break;
-    case IWAE_KNOB_PIWAE_ONE: h->piwae_one = on; break;
-    case IWAE_KNOB_DW_ALPHA: h->dw_alpha = (int)std::max(0LL, std::min(value, 1000LL)); break;
-    case IWAE_KNOB_IMG_ROWS_FWD: h->img_rows_fwd = (int)std::max(0LL, std::min(value, 16LL)); break;
-    case IWAE_KNOB_IMG_ROWS_BWD: h->img_rows_bwd = (int)std::max(0LL, std::min(value, 16LL)); break;
-    case IWAE_KNOB_X_DIRECT: h->x_direct = on; break;
-    case IWAE_KNOB_TCU: h->tcu = on; break;
-    case IWAE_KNOB_UPD_APPLY: h->upd_apply = on; break;
-    case IWAE_KNOB_NRING: h->nring = on; break;
-    case IWAE_KNOB_NRING_TRAIN: h->nring_train = on; break;
-    case IWAE_KNOB_NRING_TRAIN_ROWS: h->nr_train_rows = std::max(0LL, value); break;
-    case IWAE_KNOB_NRING_BWD: h->nring_bwd = (int)std::min<long long>(std::max(0LL, value), 3); break;
-    case IWAE_KNOB_UPD_WAVES: h->upd_waves = value == 4 ? 4 : value >= 16 ? 16 : 8; break;
-    case IWAE_KNOB_WIDE_RT: h->wide_rt = value >= 4 ? 4 : value <= 1 ? 1 : 2; break;
+    case IWAE_KNOB_NLL_ROWS: h->tune.nll_rows = std::max(1LL, value); break;
+    case IWAE_KNOB_NLL_IMGS: h->tune.nll_imgs = (int)std::max(0LL, std::min(value, 1LL << 20)); break;
+    case IWAE_KNOB_WIDE_ROWS: h->tune.wide_rows = std::max(0LL, value); break;
+    case IWAE_KNOB_DW_WIDE: h->tune.dw_wide = on; break;
+    case IWAE_KNOB_DW_WG: h->tune.dw_wg = (int)std::max(8LL, std::min(value, 4096LL)); break;
+    case IWAE_KNOB_PIWAE_ONE: h->tune.piwae_one = on; break;
+    case IWAE_KNOB_DW_ALPHA: h->tune.dw_alpha = (int)std::max(0LL, std::min(value, 1000LL)); break;
+    case IWAE_KNOB_IMG_ROWS_FWD: h->tune.img_rows_fwd = (int)std::max(0LL, std::min(value, 16LL)); break;
+    case IWAE_KNOB_IMG_ROWS_BWD: h->tune.img_rows_bwd = (int)std::max(0LL, std::min(value, 16LL)); break;
+    case IWAE_KNOB_X_DIRECT: h->tune.x_direct = on; break;
+    case IWAE_KNOB_TCU: h->tune.tcu = on; break;
+    case IWAE_KNOB_UPD_APPLY: h->tune.upd_apply = on; break;
+    case IWAE_KNOB_NRING: h->tune.nring = on; break;
+    case IWAE_KNOB_NRING_TRAIN: h->tune.nring_train = on; break;
+    case IWAE_KNOB_NRING_TRAIN_ROWS: h->tune.nr_train_rows = std::max(0LL, value); break;
+    case IWAE_KNOB_NRING_BWD: h->tune.nring_bwd = (int)std::min<long long>(std::max(0LL, value), 3); break;
+    case IWAE_KNOB_UPD_WAVES: h->tune.upd_waves = value == 4 ? 4 : value >= 16 ? 16 : 8; break;
+    case IWAE_KNOB_WIDE_RT: h->tune.wide_rt = value >= 4 ? 4 : value <= 1 ? 1 : 2; break;
     case IWAE_KNOB_LD_ALIGN:
       if (value != 4 && value != 8 && value != 16 && value != 32)
         return fail(h, IWAE_EINVAL, "LD_ALIGN must be 4, 8, 16 or 32");
-      h->ld_align = (int)value;
+      h->tune.ld_align = (int)value;
       free_workspace(h);
       break;
     default: return fail(h, IWAE_EINVAL, "unknown tuning knob " + std::to_string(knob));
   }
   // captured steps and engine plans were built for the previous setting
-  for (auto& kv : h->graphs) destroy_graph(kv.second);
-  h->graphs.clear();
-  for (auto& kv : h->tc_plans) (void)hipFree(kv.second.dev);
-  h->tc_plans.clear();
+  invalidate_graphs(h);
+  invalidate_tc_plans(h);
   return IWAE_OK;
 }
 
@@ -3332,8 +3337,7 @@ int iwae_bind_grad_buffer(iwae_handle* h, float* g, long long n) {
   if (g && n < need)
     return fail(h, IWAE_EINVAL, "data parallel: the grad buffer needs " + std::to_string(need) + " floats");
   h->grad = g ? g : h->grad_own;
-  for (auto& kv : h->graphs) destroy_graph(kv.second);
-  h->graphs.clear();
+  invalidate_graphs(h);
   return IWAE_OK;
 }
 
@@ -3378,8 +3382,7 @@ int iwae_dp_init(iwae_handle* h, int rank, int world, const void* uid) {
   h->dp_rank = rank;
   h->dp_world = world;
   h->dp_weighted = weighted;
-  for (auto& kv : h->graphs) destroy_graph(kv.second);
-  h->graphs.clear();
+  invalidate_graphs(h);
   return iwae_set_noise_stream(h, (unsigned long long)rank);
 }
 
@@ -3520,9 +3523,9 @@ static bool mega_plan(iwae_handle* h, MgLaunch& M, int& rt, int& waves, size_t& 
   // and the [8][R] reduction scratch as floats.  Row stride s dwords (ld = 2s):
   // s = 8 mod 16 makes the fragment reads (ds_read_b128) conflict-free; s = 4
   // mod 8 (2-way) is the fallback when that does not fit.
-  // 8-wave workgroups of 64 / 32 / 16 rows, or (h->mg_waves == 4) 4-wave
+  // 8-wave workgroups of 64 / 32 / 16 rows, or (h->tune.mg_waves == 4) 4-wave
   // workgroups of 32 rows, two per CU
-  waves = h->mg_waves == 4 ? 4 : 8;
+  waves = h->tune.mg_waves == 4 ? 4 : 8;
   for (int c : {4, 2, 1}) {
     if (waves == 4 && c != 2) continue;
     const int R = 16 * c;
@@ -3557,7 +3560,7 @@ static bool mega_plan(iwae_handle* h, MgLaunch& M, int& rt, int& waves, size_t& 
 static bool nring_plan(iwae_handle* h, NrLaunch& R) {
   const int L = h->L;
   std::memset(&R, 0, sizeof(R));
-  if (!h->nring || (L != 1 && L != 2) || h->xdim > 800) return false;
+  if (!h->tune.nring || (L != 1 && L != 2) || h->xdim > 800) return false;
   std::vector<NrUnit> units;
   auto stage = [&](int si, int di, int N, int next_k) {
     const DenseL& d = h->dense[di];
@@ -3595,16 +3598,7 @@ static bool nring_plan(iwae_handle* h, NrLaunch& R) {
   R.xdim = h->xdim;
   R.nunits = (int)units.size();
   if (!ok || !nring_shape_ok(R)) return false;
-  if (!h->nr_units) {
-    if (hipMalloc(&h->nr_units, kNrMaxUnits * sizeof(NrUnit)) != hipSuccess) return false;
-    if (hipMemcpy(h->nr_units, units.data(), units.size() * sizeof(NrUnit), hipMemcpyHostToDevice) != hipSuccess)
-      return false;
-    h->nr_nunits = (int)units.size();
-  }
-  R.units = h->nr_units;
-  R.fx_hi = h->fx_hi; R.fx_lo = h->fx_lo;
-  R.fx_bytes = (unsigned)(h->fx_elems * (long long)sizeof(__bf16));
-  return true;
+  return ring_plan_tail(h, h->nr_units, kNrMaxUnits, units, R);
 }
 
 // The train step's forward (the engine's forward launch: job E and the output
@@ -3616,7 +3610,7 @@ static bool nring_plan(iwae_handle* h, NrLaunch& R) {
 static bool nring_train_forward(iwae_handle* h, const Plan& P, const EpsSet& E, bool& ran) {
   ran = false;
   const long long rows = (long long)P.Bimg * P.kS;
-  if (!h->nring_train || !h->x3 || rows < h->nr_train_rows || P.kS < 43 || P.need_bce || use_fold0(h, P) ||
+  if (!h->tune.nring_train || !h->x3 || rows < h->tune.nr_train_rows || P.kS < 43 || P.need_bce || use_fold0(h, P) ||
       P.Bsplit != P.Bimg)
     return true;
   if (E.a[0] && (h->L >= 2 && !E.a[1])) return true;
@@ -3642,7 +3636,7 @@ static bool nring_train_forward(iwae_handle* h, const Plan& P, const EpsSet& E, 
   for (int i = 0; i < 8; ++i) NR.eps[i] = i < L ? E.a[i] : nullptr;
   NR.eps_N = P.Bimg; NR.eps_i0 = 0; NR.eps_s0 = 0;
   if (launch_nring(h->stream, NR) != hipSuccess) return false;
-  ++h->n_nring_train;
+  ++h->count.nring_train;
   ran = true;
   return true;
 }
@@ -3654,7 +3648,7 @@ static bool nring_train_forward(iwae_handle* h, const Plan& P, const EpsSet& E, 
 // is not instantiated (the engine's job O' runs instead).
 static bool nrb_plan(iwae_handle* h, NrbLaunch& R) {
   std::memset(&R, 0, sizeof(R));
-  if (!h->nring_bwd || !h->x3) return false;
+  if (!h->tune.nring_bwd || !h->x3) return false;
   const DenseL& d3 = h->dense[h->o3];
   const DenseL& d2 = h->dense[h->o2];
   const DenseL& d1 = h->dense[h->o1];
@@ -3675,15 +3669,7 @@ static bool nrb_plan(iwae_handle* h, NrbLaunch& R) {
     units.push_back(NrUnit{piece(d1.gx_off + (long long)t * d1.gx_steps * 512), d1.gx_steps | (1 << 8)});
   R.nunits = (int)units.size();
   if (!nrb_shape_ok(R)) return false;
-  if (!h->nrb_units) {
-    if (hipMalloc(&h->nrb_units, kNrbMaxUnits * sizeof(NrUnit)) != hipSuccess) return false;
-    if (hipMemcpy(h->nrb_units, units.data(), units.size() * sizeof(NrUnit), hipMemcpyHostToDevice) != hipSuccess)
-      return false;
-  }
-  R.units = h->nrb_units;
-  R.fx_hi = h->fx_hi; R.fx_lo = h->fx_lo;
-  R.fx_bytes = (unsigned)(h->fx_elems * (long long)sizeof(__bf16));
-  return true;
+  return ring_plan_tail(h, h->nrb_units, kNrbMaxUnits, units, R);
 }
 
 // The output MLP's backward of a large-batch train step (the engine's job O')
@@ -3692,7 +3678,7 @@ static bool nrb_plan(iwae_handle* h, NrbLaunch& R) {
 // writes (ob.dY2, ob.dY1, dh_out[0]).  ran = false: the engine runs job O'.
 static bool nring_train_backward(iwae_handle* h, const Plan& P, bool fwd_ring, bool& ran, hipStream_t st) {
   ran = false;
-  if (!fwd_ring || !h->nring_bwd) return true;
+  if (!fwd_ring || !h->tune.nring_bwd) return true;
   NrbLaunch NB;
   if (!nrb_plan(h, NB)) return true;
   NB.rows = P.Bimg * P.kS;
@@ -3702,7 +3688,7 @@ static bool nring_train_backward(iwae_handle* h, const Plan& P, bool fwd_ring, b
   NB.dY2 = h->ob.dY2.p; NB.ld_dY2 = h->ob.dY2.ld; NB.dY1 = h->ob.dY1.p; NB.ld_dY1 = h->ob.dY1.ld;
   NB.dh = h->dh_out[0].p; NB.ld_dh = h->dh_out[0].ld;
   if (launch_nrb(st, NB) != hipSuccess) return false;
-  ++h->n_nrb;
+  ++h->count.nrb;
   ran = true;
   return true;
 }
@@ -3712,7 +3698,7 @@ static bool nring_train_backward(iwae_handle* h, const Plan& P, bool fwd_ring, b
 // each, its k steps).  2-layer paper shape only; false: the engine's job E'.
 static bool nre_plan(iwae_handle* h, NreLaunch& R) {
   std::memset(&R, 0, sizeof(R));
-  if (h->nring_bwd != 3 || !h->x3 || h->L != 2) return false;
+  if (h->tune.nring_bwd != 3 || !h->x3 || h->L != 2) return false;
   const int di[6] = {h->dec[0].head, h->dec[0].l2, h->dec[0].l1, h->enc[1].head, h->enc[1].l2, h->enc[1].l1};
   std::vector<NrUnit> units;
   for (int i = 0; i < 6; ++i) {
@@ -3730,15 +3716,7 @@ static bool nre_plan(iwae_handle* h, NreLaunch& R) {
   R.dp = h->dec[0].d; R.de = h->enc[1].d;
   R.Hp = h->dense[h->dec[0].l2].fout; R.He = h->dense[h->enc[1].l2].fout;
   if (!nre_shape_ok(R)) return false;
-  if (!h->nre_units) {
-    if (hipMalloc(&h->nre_units, kNrMaxUnits * sizeof(NrUnit)) != hipSuccess) return false;
-    if (hipMemcpy(h->nre_units, units.data(), units.size() * sizeof(NrUnit), hipMemcpyHostToDevice) != hipSuccess)
-      return false;
-  }
-  R.units = h->nre_units;
-  R.fx_hi = h->fx_hi; R.fx_lo = h->fx_lo;
-  R.fx_bytes = (unsigned)(h->fx_elems * (long long)sizeof(__bf16));
-  return true;
+  return ring_plan_tail(h, h->nre_units, kNrMaxUnits, units, R);
 }
 
 // The engine's job E' on nre_kernel (after nrb_kernel, which needs nothing of
@@ -3761,7 +3739,7 @@ static bool nring_train_backward_enc(iwae_handle* h, const Plan& P, bool& ran) {
   out(h->eb[1].dP, R.edP, R.ld_edP); out(h->eb[1].dY2, R.edY2, R.ld_edY2); out(h->eb[1].dY1, R.edY1, R.ld_edY1);
   out(h->dh_enc[0], R.dh_enc, R.ld_dh_enc);
   if (launch_nre(h->stream, R) != hipSuccess) return false;
-  ++h->n_nre;
+  ++h->count.nre;
   ran = true;
   return true;
 }
@@ -3785,9 +3763,9 @@ static int nll_core(iwae_handle* h, const float* x, int N, int k, int chunk, flo
   if (!x) return fail(h, IWAE_EINVAL, "x is NULL");
   if (N <= 0 || k <= 0) return fail(h, IWAE_EINVAL, "N and k must be positive");
   // 2^20 sample rows per chunk (measured fastest: 2^17-2^20 within 10 %, smaller slower)
-  const long long nll_rows = h->nll_rows;
+  const long long nll_rows = h->tune.nll_rows;
   const long long target_rows = std::max<long long>(nll_rows, k);
-  if (chunk <= 0) chunk = h->nll_imgs;
+  if (chunk <= 0) chunk = h->tune.nll_imgs;
   int imgs = chunk > 0 ? chunk : (int)std::max<long long>(1, target_rows / k);
   imgs = std::min(imgs, N);
   const int kS = (int)std::min<long long>(k, std::max<long long>(1, target_rows / imgs));
@@ -3845,12 +3823,12 @@ static int nll_core(iwae_handle* h, const float* x, int N, int k, int chunk, flo
           NR.P0 = MG.P0; NR.ldP0 = MG.ldP0; NR.x = MG.x; NR.ldx = MG.ldx;
           NR.seed = MG.seed; NR.rng_base = MG.rng_base; NR.lw = MG.lw;
           HIPCHK(launch_nring(h->stream, NR));
-          ++h->n_nring;
+          ++h->count.nring;
         } else {
           HIPCHK(launch_mega_fwd(h->stream, MG, mg_rt, mg_waves, mg_lds));
         }
-        ++h->n_mega;
-        if (eps) ++h->n_mega_eps;
+        ++h->count.mega;
+        if (eps) ++h->count.mega_eps;
         a.lw = h->lw;
       } else {
         CHK(forward_core(h, P, E, false));
@@ -4032,21 +4010,21 @@ double iwae_workspace_bytes(const iwae_handle* h) { return h ? (double)h->arena_
 long long iwae_debug_count(const iwae_handle* h, int what) {
   if (!h) return -1;
   switch (what) {
-    case 0: return h->n_mega;
-    case 1: return h->n_mega_eps;
-    case 2: return h->n_tc;
-    case 3: return h->n_nring;
-    case 4: return h->n_nring_train;
-    case 5: return h->n_nrb;
-    case 6: return h->n_nre;
-    case 7: return h->n_captures;
+    case 0: return h->count.mega;
+    case 1: return h->count.mega_eps;
+    case 2: return h->count.tc;
+    case 3: return h->count.nring;
+    case 4: return h->count.nring_train;
+    case 5: return h->count.nrb;
+    case 6: return h->count.nre;
+    case 7: return h->count.captures;
     case 8: {                           // tcu_kernel spin give-ups so far (synchronous read)
       unsigned v[4] = {};
       if (hipStreamSynchronize(h->stream) != hipSuccess ||
           hipMemcpy(v, h->tcu_ctr, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return -1;
       return v[2];
     }
-    case 9: return h->n_tcu;
+    case 9: return h->count.tcu;
     default: return -1;
   }
 }
@@ -4054,28 +4032,28 @@ long long iwae_debug_count(const iwae_handle* h, int what) {
 int iwae_profile_gemm(iwae_handle* h, int kind, int epi) {
   if (!h) return IWAE_EINVAL;
   HIPCHK(hipStreamSynchronize(h->stream));
-  h->prof_kind = kind;
-  h->prof_epi = epi;
-  h->prof_used = 0;
-  h->prof_flop = 0.0;
-  h->prof_have = false;
-  h->prof_is_tc = false;
-  h->prof_mem = nullptr;
+  h->prof.kind = kind;
+  h->prof.epi = epi;
+  h->prof.used = 0;
+  h->prof.flop = 0.0;
+  h->prof.have = false;
+  h->prof.is_tc = false;
+  h->prof.mem = nullptr;
   return IWAE_OK;
 }
 
 int iwae_profile_replay(iwae_handle* h, int n, double* total_ms, double* total_flop) {
   if (!h || !total_ms || !total_flop || n <= 0) return IWAE_EINVAL;
-  if (!h->prof_have) return fail(h, IWAE_EINVAL, "no launch of the profiled GEMM class was recorded");
+  if (!h->prof.have) return fail(h, IWAE_EINVAL, "no launch of the profiled GEMM class was recorded");
   hipEvent_t e0, e1;
   HIPCHK(hipEventCreate(&e0));
   HIPCHK(hipEventCreate(&e1));
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipEventRecord(e0, h->stream));
   for (int i = 0; i < n; ++i) {
-    if (h->prof_is_tc) HIPCHK(launch_tc(h->stream, h->prof_tc, h->prof_tc_rt, h->prof_tc_lds));
-    else if (h->prof_kind >= 12) HIPCHK(h->prof_mem(h->stream));     // (12-16: recorded closures)
-    else HIPCHK(launch_gemm(h->stream, h->prof_k, h->prof_e, h->prof_tile, h->prof_splits, h->prof_ks, h->prof_args));
+    if (h->prof.is_tc) HIPCHK(launch_tc(h->stream, h->prof.tc, h->prof.tc_rt, h->prof.tc_lds));
+    else if (h->prof.kind >= 12) HIPCHK(h->prof.mem(h->stream));     // (12-16: recorded closures)
+    else HIPCHK(launch_gemm(h->stream, h->prof.k, h->prof.e, h->prof.tile, h->prof.splits, h->prof.ks, h->prof.args));
   }
   HIPCHK(hipEventRecord(e1, h->stream));
   HIPCHK(hipEventSynchronize(e1));
@@ -4084,7 +4062,7 @@ int iwae_profile_replay(iwae_handle* h, int n, double* total_ms, double* total_f
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
   *total_ms = ms;
-  *total_flop = h->prof_flop1 * n;
+  *total_flop = h->prof.flop1 * n;
   return IWAE_OK;
 }
 
@@ -4092,14 +4070,14 @@ int iwae_profile_read(iwae_handle* h, double* total_ms, double* total_flop, long
   if (!h || !total_ms || !total_flop || !launches) return IWAE_EINVAL;
   HIPCHK(hipStreamSynchronize(h->stream));
   double ms = 0.0;
-  for (size_t i = 0; i + 1 < h->prof_used; i += 2) {
+  for (size_t i = 0; i + 1 < h->prof.used; i += 2) {
     float t = 0.f;
-    HIPCHK(hipEventElapsedTime(&t, h->prof_ev[i], h->prof_ev[i + 1]));
+    HIPCHK(hipEventElapsedTime(&t, h->prof.ev[i], h->prof.ev[i + 1]));
     ms += t;
   }
   *total_ms = ms;
-  *total_flop = h->prof_flop;
-  *launches = (long long)(h->prof_used / 2);
+  *total_flop = h->prof.flop;
+  *launches = (long long)(h->prof.used / 2);
   return IWAE_OK;
 }
 

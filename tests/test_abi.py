@@ -71,6 +71,37 @@ def test_loss_ids_match_header():
         assert _lib.LOSS_IDS[name] == ids[hname]
 
 
+def test_knob_ids_match_header():
+    """_lib.KNOBS and the IWAE_KNOB_* enum of include/iwae.h name the same knobs
+    with the same ids (names lower-cased), in both directions."""
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    header = dict((m.group(1).lower(), int(m.group(2))) for m in re.finditer(r"\bIWAE_KNOB_([A-Z_0-9]+)\s*=\s*(\d+)", src))
+    assert len(header) == 36
+    assert sorted(header.values()) == list(range(1, 10)) + list(range(11, 36)) + [41, 42]
+    for name, kid in header.items():
+        assert _lib.KNOBS.get(name) == kid, name
+    for name, kid in _lib.KNOBS.items():
+        assert header.get(name) == kid, name
+
+
+def test_source_manifest_lists_every_source_once():
+    """csrc/SOURCES.txt is the one list of sources and per-source flags: every
+    *.hip of csrc/ appears in it exactly once, the build's tables come from it,
+    and the train engine's source keeps both of its flags."""
+    import __graft_entry__ as G
+    csrc = os.path.join(ROOT, "iwae_replication_project_amd", "csrc")
+    lines = [ln.split("#", 1)[0].split() for ln in open(os.path.join(csrc, "SOURCES.txt"))]
+    manifest = [(w[0], w[1:]) for w in lines if w]
+    names = [s for s, _ in manifest]
+    on_disk = sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
+    assert sorted(names) == on_disk                      # every source, exactly once
+    assert len(set(names)) == len(names)
+    assert G.SOURCES == names
+    assert G.SOURCE_FLAGS == {s: f for s, f in manifest if f}
+    flags = dict(manifest)
+    assert "-fno-slp-vectorize" in flags["iwae_train.hip"] and "-Os" in flags["iwae_train.hip"]
+
+
 def test_create_without_gpu_fails_cleanly():
     import torch
     if torch.cuda.is_available():
