@@ -315,6 +315,28 @@ int iwae_encoder_means(iwae_handle* h, const float* x, int N, int n, const float
  * [1][B][d_i], then L-1 prior buffers [1][B][d_{L-2-j}] in generation order. */
 int iwae_reconstruct(iwae_handle* h, const float* x, int B, const float* const* eps, int n_eps,
                      float* probs, int ld_probs, float* loss_dev);
+/* Decoder.generate_x (F:107-F:119) and ancestral sampling from the prior.
+ * n rows.  h_top [dev] [n][d_L] or NULL (then h_L ~ N(0, I)).  eps (optional):
+ * h_top given: L-1 prior buffers [1][n][d_{L-2-j}] in generation order (as
+ * iwae_reconstruct's); h_top NULL: one [1][n][d_L] buffer for h_L first, then
+ * those.  u [dev] [n][x_dim] uniforms for the pixel draws, or NULL (Philox).
+ * probs / pixels [dev] [n][ld] (ld >= x_dim, multiple of 4, 16-byte aligned),
+ * either may be NULL, not both.  h_out (optional): L buffers [n][d_i] in
+ * encoder order h_1..h_L.  Weights, Adam state and captured graphs untouched.
+ * Each prior layer samples h = eps (exp(zs) + 1e-6) + mu (F:113-F:114); probs =
+ * sigmoid(logit) (1 - 1e-6) + 1e-7 (F:101-F:102); pixels = (u < probs) as 0.0 /
+ * 1.0.  Columns [x_dim, ld) of the outputs are not written; ld <= 2^22.  One fused launch
+ * (gen_kernel: activations in LDS, bf16x3 products) when the model fits 160 KB
+ * of LDS; layer-wise launches otherwise and under iwae_set_precision(h, 0) or
+ * iwae_set_path(h, 1).  Device noise: Philox layer ids IWAE_MAX_LAYERS + j for
+ * prior layer j (iwae_reconstruct's), IWAE_MAX_LAYERS + L - 1 for h_L,
+ * 2 * IWAE_MAX_LAYERS for the pixels, row = the generated row; both paths draw
+ * the same stream, and every call advances the noise position once.  n == 0
+ * succeeds and launches nothing; the handle's sticky error (iwae_status) is
+ * returned before any work is enqueued. */
+int iwae_generate(iwae_handle* h, int n, const float* h_top, const float* const* eps, int n_eps,
+                  const float* u, float* probs, int ld_probs, float* pixels, int ld_pixels,
+                  float* const* h_out, int n_out);
 /* get_NLL_without_inactive_units (F:466-F:494): like iwae_nll / iwae_nll_eps
  * with every sampled h_i multiplied by masks[i] ([dev], d_i floats of 0/1). */
 int iwae_nll_masked(iwae_handle* h, const float* x, int N, int k, const float* const* eps,
@@ -339,7 +361,8 @@ double iwae_workspace_bytes(const iwae_handle* h);
  * backward + update launch that gave up (synchronous; 0 unless the GPU was
  * shared with a kernel that held CUs for ~1 s, or IWAE_KNOB_TCU_WAIT_TEST;
  * each also sets the error iwae_status reports), 9 such combined launches
- * issued (a captured step counts once, at capture); -1 for an unknown id. */
+ * issued (a captured step counts once, at capture), 10 fused generation
+ * launches (gen_kernel) issued by iwae_generate; -1 for an unknown id. */
 long long iwae_debug_count(const iwae_handle* h, int what);
 /* Live kernel timing: bracket every launch of one kernel class with HIP events
  * on the handle's stream -- a GEMM class (kind: 0 forward, 1 backward-data,

@@ -682,4 +682,83 @@ hipError_t launch_bern_probs(hipStream_t st, float* z, int rows, int cols, int l
   return hipGetLastError();
 }
 
+// ------------------------------------------- layer-wise generation (F:107-F:119)
+// Top latent of iwae_generate's layer-wise path: one thread per (row, column
+// quad); H[r][j] = src[r][j] (the caller's h_L, or injected eps * 1 + 0), else
+// the Philox normals gen_kernel draws for the same (row, layer, quad).
+__global__ __launch_bounds__(256) void gen_top_kernel(const float* __restrict__ src, int n, int d, float* H, int ldH,
+                                                      float* copy, uint64_t seed, const uint64_t* rng_base,
+                                                      int layer) {
+  const int ng = (d + 3) >> 2;
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)n * ng) return;
+  const int r = (int)(i / ng), g = (int)(i - (long long)r * ng);
+  float4 e4;
+  if (src) {
+    const float* s = src + (size_t)r * d;
+    const int j = 4 * g;
+    e4 = make_float4(s[j], s[min(j + 1, d - 1)], s[min(j + 2, d - 1)], s[min(j + 3, d - 1)]);
+  } else {
+    e4 = philox_normal4(seed, *rng_base, (unsigned)r, (unsigned)layer, (unsigned)g);
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int j = 4 * g + q;
+    if (j >= d) break;
+    H[(size_t)r * ldH + j] = f4_at(e4, q);
+    if (copy) copy[(size_t)r * d + j] = f4_at(e4, q);
+  }
+}
+hipError_t launch_gen_top(hipStream_t st, const float* src, int n, int d, float* H, int ldH, float* copy,
+                          uint64_t seed, const uint64_t* rng_base, int layer) {
+  const long long t = (long long)n * ((d + 3) >> 2);
+  if (t <= 0) return hipSuccess;
+  hipLaunchKernelGGL(gen_top_kernel, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, st, src, n, d, H, ldH, copy,
+                     seed, rng_base, layer);
+  return hipGetLastError();
+}
+
+// Pixel draws x = (u < p) of the layer-wise path (out may be p itself): u from
+// the caller's [n][xdim] buffer, else gen_kernel's Philox uniforms.
+__global__ __launch_bounds__(256) void gen_pixels_kernel(const float* p, int ldp, const float* __restrict__ u, int n,
+                                                         int xdim, float* out, int ldo, uint64_t seed,
+                                                         const uint64_t* rng_base, int layer) {
+  const int ng = (xdim + 3) >> 2;
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)n * ng) return;
+  const int r = (int)(i / ng), g = (int)(i - (long long)r * ng);
+  float4 u4;
+  if (u) {
+    const float* s = u + (size_t)r * xdim;
+    const int j = 4 * g;
+    u4 = make_float4(s[j], s[min(j + 1, xdim - 1)], s[min(j + 2, xdim - 1)], s[min(j + 3, xdim - 1)]);
+  } else {
+    u4 = philox_uniform4(seed, *rng_base, (unsigned)r, (unsigned)layer, (unsigned)g);
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int j = 4 * g + q;
+    if (j >= xdim) break;
+    const float pv = p[(size_t)r * ldp + j];
+    out[(size_t)r * ldo + j] = f4_at(u4, q) < pv ? 1.f : 0.f;
+  }
+}
+hipError_t launch_gen_pixels(hipStream_t st, const float* p, int ldp, const float* u, int n, int xdim, float* out,
+                             int ldo, uint64_t seed, const uint64_t* rng_base, int layer) {
+  const long long t = (long long)n * ((xdim + 3) >> 2);
+  if (t <= 0) return hipSuccess;
+  hipLaunchKernelGGL(gen_pixels_kernel, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, st, p, ldp, u, n, xdim, out,
+                     ldo, seed, rng_base, layer);
+  return hipGetLastError();
+}
+
+__global__ void rng_advance_kernel(uint64_t* rng_base) {
+  rng_base[1] = rng_base[0];
+  rng_base[0] += 1;
+}
+hipError_t launch_rng_advance(hipStream_t st, uint64_t* rng_base) {
+  hipLaunchKernelGGL(rng_advance_kernel, dim3(1), dim3(1), 0, st, rng_base);
+  return hipGetLastError();
+}
+
 }  // namespace iwae

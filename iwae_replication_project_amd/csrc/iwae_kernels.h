@@ -102,6 +102,25 @@ __device__ __forceinline__ float2 philox_normal2(uint64_t seed, uint64_t base, u
   const float r = __builtin_amdgcn_sqrtf(-1.38629436f * __builtin_amdgcn_logf(ua));
   return make_float2(r * __builtin_amdgcn_cosf(ub), r * __builtin_amdgcn_sinf(ub));
 }
+// The four uniforms of the same block (same ten rounds, same counter layout):
+// u = (c + 0.5) * 2^-32, the pixel draws of iwae_generate (uniform q of group
+// g is the draw of column 4g + q).
+__device__ __forceinline__ float4 philox_uniform4(uint64_t seed, uint64_t base, unsigned row, unsigned layer,
+                                                  unsigned grp) {
+  unsigned c0 = row, c1 = (layer << 20) | grp, c2 = (unsigned)base, c3 = (unsigned)(base >> 32);
+  unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+#pragma unroll
+  for (int i = 0; i < 10; ++i) {
+    unsigned lo0, hi0, lo1, hi1;
+    philox_mul(0xD2511F53u, c0, lo0, hi0);
+    philox_mul(0xCD9E8D57u, c2, lo1, hi1);
+    c0 = philox_xor3(hi1, c1, k0); c1 = lo1; c2 = philox_xor3(hi0, c3, k1); c3 = lo0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  constexpr float k2m32 = 2.3283064365386963e-10f;
+  return make_float4(((float)c0 + 0.5f) * k2m32, ((float)c1 + 0.5f) * k2m32, ((float)c2 + 0.5f) * k2m32,
+                     ((float)c3 + 0.5f) * k2m32);
+}
 __device__ __forceinline__ float f4_at(const float4& v, int q) {
   return q == 0 ? v.x : q == 1 ? v.y : q == 2 ? v.z : v.w;
 }
@@ -745,5 +764,47 @@ hipError_t launch_group_mean(hipStream_t st, const float* H, int ldH, int n, int
 // probs = sigmoid(logit) * (1 - 1e-6) + 1e-7 in place over [rows][ld] (F:102)
 hipError_t launch_bern_probs(hipStream_t st, float* z, int rows, int cols, int ld);
 hipError_t launch_transpose_lw(hipStream_t st, const float* lw_img, int Bimg, int kS, float* out);
+
+// ------------------------------------- generation from the prior (fused) ----
+// gen_kernel (iwae_generate.hip): Decoder.generate_x (F:107-F:119) on 16*RT
+// generated rows per workgroup, activations resident in LDS as split bf16
+// planes (mega_fwd_kernel's storage, weight streaming and head layout): top
+// latent h_L (given, injected or Philox) -> per prior layer tanh, tanh, head:
+// sample h -> output MLP tanh, tanh, Dense(x_dim) -> probabilities (F:101-F:102)
+// and / or Bernoulli pixel draws.
+enum GnAct { GN_TANH = 1, GN_OUT = 2, GN_HEAD = 3 };
+struct GnStage {
+  const __bf16* Whi; const __bf16* Wlo; unsigned W_bytes;
+  int ldk, N;                // FX k extent (input ones column at fin); output features (heads: 8 * ceil(d / 4) permuted)
+  int in_buf, out_buf;       // LDS buffer ids; out_buf: TANH output, HEAD destination latent
+  int act;                   // GnAct
+  int d, layer;              // HEAD: latent width, Philox layer id
+  int next_k;                // TANH / HEAD: padded K of the reader of out_buf (ones column + zero pad)
+  const float* eps;          // HEAD: injected noise [n][d], or null (Philox)
+  float* h_out;              // HEAD: f32 copy of the sampled latent [n][d], or null
+};
+struct GnLaunch {
+  GnStage st[kMgMaxStages]; int nst;
+  int buf_off[kMgMaxBufs], buf_ld[kMgMaxBufs];   // bf16 offset of the hi plane / row stride
+  int n;                                          // generated rows
+  // top latent: h_top [n][d_top], else eps_top [n][d_top] (h_L = eps * 1 + 0), else Philox normals
+  const float* h_top; const float* eps_top; float* top_out;
+  int d_top, top_buf, top_next_k, top_layer;
+  // outputs (either may be null): probabilities / pixels [n][ld]; u: injected uniforms [n][xdim] or null
+  float* probs; int ld_probs; float* pixels; int ld_pixels; const float* u; int pix_layer;
+  uint64_t seed; uint64_t* rng_base; unsigned* ticket;   // the last workgroup advances the Philox base
+};
+hipError_t launch_gen(hipStream_t st, const GnLaunch& L, int rt, size_t lds_bytes);
+hipError_t gen_setup_attributes();
+
+// layer-wise generation (iwae_elem.hip), same Philox counters as gen_kernel:
+// top latent H[r][j] = src[r][j] (h_top or injected eps) or a Philox normal
+// (+ optional tight f32 copy), pixel draws out = (u < p), and the Philox base's
+// advance as a one-thread launch
+hipError_t launch_gen_top(hipStream_t st, const float* src, int n, int d, float* H, int ldH, float* copy,
+                          uint64_t seed, const uint64_t* rng_base, int layer);
+hipError_t launch_gen_pixels(hipStream_t st, const float* p, int ldp, const float* u, int n, int xdim, float* out,
+                             int ldo, uint64_t seed, const uint64_t* rng_base, int layer);
+hipError_t launch_rng_advance(hipStream_t st, uint64_t* rng_base);
 
 }  // namespace iwae

@@ -199,6 +199,7 @@ struct Counters {
   long long nrb = 0, nre = 0;        // 5, 6: nrb_kernel / nre_kernel launches
   long long captures = 0;            // 7: train-step graphs captured (single and multi-step)
   long long tcu = 0;                 // 9: combined job I' + update launches (tcu_kernel)
+  long long gen = 0;                 // 10: fused generation launches (gen_kernel)
 };
 
 // row-chain train engine plan (device resident, per shape; iwae_train.hip)
@@ -2975,6 +2976,7 @@ iwae_handle* iwae_create(const iwae_config* cfg, int device) {
   if (e == hipSuccess) e = tc_setup_attributes();
   if (e == hipSuccess) e = upd_setup_attributes();
   if (e == hipSuccess) e = dw_setup_attributes();
+  if (e == hipSuccess) e = gen_setup_attributes();
   if (e != hipSuccess) {
     g_create_error = std::string("hipFuncSetAttribute failed: ") + hipGetErrorString(e);
     iwae_destroy(h);
@@ -3975,6 +3977,150 @@ int iwae_reconstruct(iwae_handle* h, const float* x, int B, const float* const* 
   return IWAE_OK;
 }
 
+// ------------------------------------------------ generation from the prior
+// Plan of gen_kernel for this model (iwae_generate.hip).  LDS buffers: the
+// latents h_0 .. h_{L-1} kept (ids 0 .. L-1), scratch P (id L) and Q (id L+1).
+//   prior layer j = 0..L-2:  h_{L-1-j} -> Q (tanh) -> P (tanh) -> head: sample h_{L-2-j}
+//   output MLP:              h_0 -> Q -> P -> Dense(x_dim): probabilities / pixels
+// Row strides of 8 mod 16 dwords (conflict-free fragment reads).  RT from
+// {4, 2, 1}: the largest that fits 160 KB of LDS.  False if RT = 1 does not fit.
+static bool gen_plan(iwae_handle* h, GnLaunch& G, int& rt, size_t& lds) {
+  const int L = h->L;
+  std::memset(&G, 0, sizeof(G));
+  auto r32 = [](int x) { return (x + 31) & ~31; };
+  const int bP = L, bQ = L + 1, nb = L + 2;
+  if (nb > kMgMaxBufs || 3 * L > kMgMaxStages) return false;
+  std::vector<int> width(nb, 0);
+  auto stage = [&](int di, int in, int out, int act, int next_k) -> GnStage& {
+    const DenseL& d = h->dense[di];
+    GnStage& S = G.st[G.nst++];
+    S.Whi = h->fx_hi + d.fx_off; S.Wlo = h->fx_lo + d.fx_off;
+    S.W_bytes = (unsigned)((h->fx_elems - d.fx_off) * (long long)sizeof(__bf16));
+    S.ldk = d.ldF; S.N = d.fout;
+    S.in_buf = in; S.out_buf = out; S.act = act; S.next_k = next_k;
+    width[in] = std::max(width[in], S.ldk);
+    if (act == GN_TANH) width[out] = std::max(width[out], std::max(S.N, next_k));
+    return S;
+  };
+  for (int j = 0; j < L - 1; ++j) {
+    const StochL& D = h->dec[j];
+    stage(D.l1, L - 1 - j, bQ, GN_TANH, h->dense[D.l2].ldF);
+    stage(D.l2, bQ, bP, GN_TANH, h->dense[D.head].ldF);
+    GnStage& S = stage(D.head, bP, L - 2 - j, GN_HEAD, r32(D.d + 1));
+    S.N = 8 * ((D.d + 3) / 4);
+    S.d = D.d; S.layer = IWAE_MAX_LAYERS + j;
+    width[L - 2 - j] = std::max(width[L - 2 - j], r32(D.d + 1));
+  }
+  stage(h->o1, 0, bQ, GN_TANH, h->dense[h->o2].ldF);
+  stage(h->o2, bQ, bP, GN_TANH, h->dense[h->o3].ldF);
+  stage(h->o3, bP, -1, GN_OUT, 0);
+  G.d_top = h->enc[L - 1].d; G.top_buf = L - 1; G.top_next_k = r32(G.d_top + 1);
+  G.top_layer = IWAE_MAX_LAYERS + L - 1; G.pix_layer = 2 * IWAE_MAX_LAYERS;
+  width[L - 1] = std::max(width[L - 1], G.top_next_k);
+  int per_row = 0;                               // bf16 units per row: both planes of every buffer
+  for (int b = 0; b < nb; ++b) {
+    int sdw = (std::max(width[b], 32) + 1) / 2;
+    while (sdw % 16 != 8) ++sdw;
+    G.buf_ld[b] = 2 * sdw;
+    per_row += 2 * G.buf_ld[b];
+  }
+  rt = 0;
+  for (int c : {4, 2, 1})
+    if ((size_t)16 * c * per_row * sizeof(__bf16) <= 160 * 1024) { rt = c; break; }
+  if (!rt) return false;
+  int off = 0;
+  for (int b = 0; b < nb; ++b) {
+    G.buf_off[b] = off;
+    off += 2 * 16 * rt * G.buf_ld[b];
+  }
+  lds = (size_t)off * sizeof(__bf16);
+  return true;
+}
+
+int iwae_generate(iwae_handle* h, int n, const float* h_top, const float* const* eps, int n_eps, const float* u,
+                  float* probs, int ld_probs, float* pixels, int ld_pixels, float* const* h_out, int n_out) {
+  if (!h) return IWAE_EINVAL;
+  CHK(kernel_status(h));
+  const int L = h->L;
+  if (n < 0) return fail(h, IWAE_EINVAL, "n must not be negative");
+  if (!probs && !pixels) return fail(h, IWAE_EINVAL, "probs and pixels are both NULL");
+  // (ld <= 2^22: a workgroup's 64 rows stay within gen_kernel's 32-bit buffer offsets)
+  constexpr int kMaxLd = 1 << 22;
+  if (probs && (ld_probs < h->xdim || ld_probs > kMaxLd || (ld_probs & 3) || ((uintptr_t)probs & 15)))
+    return fail(h, IWAE_EINVAL, "probs needs x_dim <= ld <= 2^22, a multiple of 4, 16-byte aligned");
+  if (pixels && (ld_pixels < h->xdim || ld_pixels > kMaxLd || (ld_pixels & 3) || ((uintptr_t)pixels & 15)))
+    return fail(h, IWAE_EINVAL, "pixels needs x_dim <= ld <= 2^22, a multiple of 4, 16-byte aligned");
+  const bool injected = eps && n_eps > 0;
+  const int need = h_top ? L - 1 : L;
+  if (n_eps != 0 && n_eps != need)
+    return fail(h, IWAE_EINVAL, "expected " + std::to_string(need) + " eps buffers (" +
+                                   (h_top ? "the prior draws" : "h_L, then the prior draws") + "), got " +
+                                   std::to_string(n_eps));
+  if (n_eps != 0 && !eps) return fail(h, IWAE_EINVAL, "eps is NULL");
+  for (int i = 0; injected && i < n_eps; ++i)
+    if (!eps[i]) return fail(h, IWAE_EINVAL, "NULL eps buffer");
+  const bool keep = h_out && n_out > 0;
+  if (n_out != 0 && (!h_out || n_out != L))
+    return fail(h, IWAE_EINVAL, "expected one h_out buffer per stochastic layer");
+  for (int i = 0; keep && i < L; ++i)
+    if (!h_out[i]) return fail(h, IWAE_EINVAL, "NULL h_out buffer");
+  if (n == 0) return IWAE_OK;
+  const float* eps_top = (injected && !h_top) ? eps[0] : nullptr;
+  const float* const* eps_pri = injected ? eps + (h_top ? 0 : 1) : nullptr;   // prior layer j's
+  GnLaunch G;
+  int rt = 0;
+  size_t lds = 0;
+  if (h->x3 && h->path != 1 && gen_plan(h, G, rt, lds)) {
+    CHK(ensure_fx(h));
+    G.n = n;
+    G.h_top = h_top; G.eps_top = eps_top; G.top_out = keep ? h_out[L - 1] : nullptr;
+    for (int j = 0; j < L - 1; ++j) {
+      GnStage& S = G.st[3 * j + 2];
+      S.eps = eps_pri ? eps_pri[j] : nullptr;
+      S.h_out = keep ? h_out[L - 2 - j] : nullptr;
+    }
+    G.probs = probs; G.ld_probs = ld_probs; G.pixels = pixels; G.ld_pixels = ld_pixels; G.u = u;
+    G.seed = h->seed; G.rng_base = &h->ds->rng[0]; G.ticket = &h->ds->tickets[3];
+    HIPCHK(launch_gen(h->stream, G, rt, lds));
+    ++h->count.gen;
+    return IWAE_OK;
+  }
+  // layer-wise: the GEMM and Gaussian launches of iwae_reconstruct's generate_x
+  // (exact f32 products under iwae_set_precision 0), the same Philox counters
+  if (h->x3) CHK(ensure_wsplit(h));
+  CHK(ensure_capacity(h, 1, n, false));
+  const int dL = h->enc[L - 1].d;
+  HIPCHK(launch_gen_top(h->stream, h_top ? h_top : eps_top, n, dL, h->h[L - 1].p, h->h[L - 1].ld,
+                        keep ? h_out[L - 1] : nullptr, h->seed, &h->ds->rng[0], IWAE_MAX_LAYERS + L - 1));
+  for (int j = 0; j < L - 1; ++j) {
+    CHK(stoch_fwd(h, h->dec[j], h->h[L - 1 - j], n, h->db[j]));
+    GaussArgs g{};
+    g.P = h->db[j].P.p; g.ldP = h->db[j].P.ld; g.prow_div = 1; g.d = h->dec[j].d;
+    g.H = h->h[L - 2 - j].p; g.ldH = h->h[L - 2 - j].ld;
+    g.eps_a = eps_pri ? eps_pri[j] : nullptr;
+    g.kS = 1; g.Bsplit = n; g.Bimg = n;
+    g.seed = h->seed; g.rng_base = &h->ds->rng[0]; g.layer = IWAE_MAX_LAYERS + j;
+    g.out = h->logp; g.accumulate = 0; g.M = n;
+    HIPCHK(launch_gauss_fwd(h->stream, 0, g));
+    if (keep) {
+      const size_t wb = (size_t)g.d * sizeof(float);
+      HIPCHK(hipMemcpy2DAsync(h_out[L - 2 - j], wb, g.H, (size_t)g.ldH * sizeof(float), wb, n,
+                              hipMemcpyDeviceToDevice, h->stream));
+    }
+  }
+  CHK(gemm_fwd(h, EPI_TANH, h->h[0], n, h->dense[h->o1], h->ob.y1));
+  CHK(gemm_fwd(h, EPI_TANH, h->ob.y1, n, h->dense[h->o2], h->ob.y2));
+  Mat pm;                                        // the logits, then the probabilities, in the caller's buffer
+  pm.p = probs ? probs : pixels; pm.ld = probs ? ld_probs : ld_pixels;
+  CHK(gemm_fwd(h, EPI_STORE, h->ob.y2, n, h->dense[h->o3], pm));
+  HIPCHK(launch_bern_probs(h->stream, pm.p, n, h->xdim, pm.ld));
+  if (pixels)
+    HIPCHK(launch_gen_pixels(h->stream, pm.p, pm.ld, u, n, h->xdim, pixels, ld_pixels, h->seed, &h->ds->rng[0],
+                             2 * IWAE_MAX_LAYERS));
+  HIPCHK(launch_rng_advance(h->stream, &h->ds->rng[0]));
+  return IWAE_OK;
+}
+
 // get_NLL_without_inactive_units (F:466-F:494): k-sample log p(x) with every
 // sampled h_i multiplied by its 0/1 active-unit mask masks[i] ([dev], d_i).
 int iwae_nll_masked(iwae_handle* h, const float* x, int N, int k, const float* const* eps, int n_eps,
@@ -4025,6 +4171,7 @@ long long iwae_debug_count(const iwae_handle* h, int what) {
       return v[2];
     }
     case 9: return h->count.tcu;
+    case 10: return h->count.gen;
     default: return -1;
   }
 }

@@ -154,6 +154,18 @@ class Adam:
 
 
 # ------------------------------------------------------------------ model
+class _Decoder:
+    """``model.decoder``: the reference's ``mdl.decoder.generate_x(h)``
+    (F:107-F:119) forwarded to the model (held weakly: no reference cycle)."""
+
+    def __init__(self, model):
+        import weakref
+        self._model = weakref.ref(model)
+
+    def generate_x(self, h, eps=None):
+        return self._model().generate_x(h, eps=eps)
+
+
 class Flexible_Model:
     """HIP-backed ``Flexible_Model`` (F:177-F:545)."""
 
@@ -216,6 +228,7 @@ class Flexible_Model:
         self.set_weights(glorot_weights(self.dense, rng, resolve_dataset_bias(dataset_bias, x_dim)))
         self._loss_buf = torch.zeros(1, device=self.device)
         self._scratch = torch.zeros(1, device=self.device)
+        self.decoder = _Decoder(self)                         # mdl.decoder.generate_x(h), F:107-F:119
 
     # ------------------------------------------------------------- plumbing
     def set_seed(self, seed):
@@ -611,6 +624,81 @@ class Flexible_Model:
         """F:256-F:262: mean over the batch of the Keras BCE of x against the
         reconstructed probabilities, summed over pixels."""
         return self._reconstruct(x, eps, False)[1]
+
+    # ------------------------------------------------------------ generation
+    def _generate(self, n, h_top, eps, u, want_probs, want_pixels, want_latents):
+        """iwae_generate on n rows; returns (probs, pixels, latents), each
+        None unless asked for.  Arguments are validated before the native call."""
+        L = len(self.n_latent_encoder)
+        n = int(n)
+        if n < 0:
+            raise ValueError("n must not be negative")
+        dims = [] if h_top is not None else [self.n_latent_encoder[L - 1]]
+        dims += [self.n_latent_encoder[L - 2 - j] for j in range(L - 1)]
+        keep, arr, ne = [], None, 0
+        if eps is not None:
+            eps = list(eps)
+            if len(eps) != len(dims):
+                what = "the prior draws" if h_top is not None else "h_L, then the prior draws"
+                raise ValueError(f"expected {len(dims)} eps arrays ({what}), got {len(eps)}")
+            with torch.cuda.stream(self._stream):
+                for e, d in zip(eps, dims):
+                    t = torch.as_tensor(e).to(device=self.device, dtype=torch.float32).contiguous()
+                    if tuple(t.shape) != (1, n, d):
+                        raise ValueError(f"eps arrays must be [1, n={n}, d={d}], got {tuple(t.shape)}")
+                    keep.append(t)
+            arr, ne = _lib.fptr_array(keep)
+        ut = None
+        if u is not None:
+            with torch.cuda.stream(self._stream):
+                ut = torch.as_tensor(u).to(device=self.device, dtype=torch.float32).contiguous()
+            if tuple(ut.shape) != (n, self.x_dim):
+                raise ValueError(f"u must be [n={n}, {self.x_dim}], got {tuple(ut.shape)}")
+        with torch.cuda.stream(self._stream):
+            ld = (self.x_dim + 3) // 4 * 4
+            probs = torch.empty(n, ld, device=self.device) if want_probs else None
+            pixels = torch.empty(n, ld, device=self.device) if want_pixels else None
+            hs = [torch.empty(n, d, device=self.device) for d in self.n_latent_encoder] if want_latents else []
+        harr, nh = _lib.fptr_array(hs)
+        if n > 0:
+            self._call(self._lib.iwae_generate(self._h, n, _lib.fptr(h_top), arr, ne, _lib.fptr(ut),
+                                               _lib.fptr(probs), ld if want_probs else 0,
+                                               _lib.fptr(pixels), ld if want_pixels else 0, harr, nh))
+        self._stream.synchronize()
+        return (probs[:, :self.x_dim] if want_probs else None, pixels[:, :self.x_dim] if want_pixels else None,
+                hs if want_latents else None)
+
+    def generate_x(self, h_top, eps=None):
+        """Decoder.generate_x (F:107-F:119): pixel probabilities of the images
+        generated from the top latent ``h_top`` ([S, B, d_L] as in the
+        reference, or [B, d_L]) by ancestral sampling through the decoder's
+        prior layers; device tensor [S, B, x_dim] (or [B, x_dim]).  The rows
+        are the flattened S*B.  ``eps``: the L-1 prior draws in generation
+        order, [1, S*B, d_{L-2-j}]."""
+        with torch.cuda.stream(self._stream):
+            t = torch.as_tensor(h_top).to(device=self.device, dtype=torch.float32).contiguous()
+        dL = self.n_latent_encoder[-1]
+        if t.dim() not in (2, 3) or t.shape[-1] != dL:
+            raise ValueError(f"h_top must be [S, B, {dL}] or [B, {dL}], got {tuple(t.shape)}")
+        lead = tuple(t.shape[:-1])
+        probs, _, _ = self._generate(int(np.prod(lead)), t.reshape(-1, dL), eps, None, True, False, False)
+        return probs.reshape(*lead, self.x_dim)
+
+    def sample(self, n, eps=None, u=None, return_probs=True, return_latents=False):
+        """n unconditional samples: h_L ~ N(0, I), ancestral sampling down the
+        decoder's prior layers (F:107-F:119), binary pixels x ~ Bernoulli(probs).
+        Returns {"x": [n, x_dim] of 0.0 / 1.0} plus "probs" ([n, x_dim]) and
+        "h" (the L latents [n, d_i], encoder order) when asked for.  ``eps``:
+        L arrays [1, n, d], h_L's first and then the prior draws in generation
+        order; ``u``: [n, x_dim] uniforms for the pixel draws.  By default all
+        noise is drawn on the device (Philox)."""
+        probs, pixels, hs = self._generate(n, None, eps, u, bool(return_probs), True, bool(return_latents))
+        out = {"x": pixels}
+        if return_probs:
+            out["probs"] = probs
+        if return_latents:
+            out["h"] = hs
+        return out
 
     def encoder_means(self, x, n_samples, eps=None):
         """Device [N, d_i] per layer: the mean over n_samples draws of q(h|x)
