@@ -54,7 +54,14 @@ enum iwae_loss_id {
   IWAE_LOSS_L_MEDIAN = 5,   /* -get_L_median F:239, F:373 */
   IWAE_LOSS_CIWAE = 6,      /* -get_L_CIWAE  F:241, F:382 */
   IWAE_LOSS_MIWAE = 7,      /* MIWAE(k1,k2), PDF p7 */
-  IWAE_LOSS_PIWAE = 8       /* decoder: IWAE_{k1 k2}, encoder: MIWAE(k1,k2) */
+  IWAE_LOSS_PIWAE = 8,      /* decoder: IWAE_{k1 k2}, encoder: MIWAE(k1,k2) */
+  /* Path-gradient estimators of the IWAE bound.  Loss value and decoder
+   * gradient are IWAE's.  The encoder's gradient is that of
+   * sum_{b,s} a_enc[s][b] log w[s][b] taken through the sampling path
+   * h_i = mu_i + s_i eps_i only (the encoder's parameters inside the densities
+   * log q held fixed), with sm = softmax_k(log w) per image: */
+  IWAE_LOSS_IWAE_STL = 9,   /* a_enc = sm / B     "sticking the landing", Roeder et al. 2017 (biased for k > 1) */
+  IWAE_LOSS_IWAE_DREG = 10  /* a_enc = sm^2 / B   doubly reparameterised, Tucker et al. 2019 (unbiased) */
 };
 
 /* Architecture knobs of Flexible_Model.__init__ (F:178-F:180). */
@@ -184,7 +191,7 @@ int iwae_set_tuning(iwae_handle* h, int knob, long long value);
  * tiled GEMMs' largest tile also 32x32x2_f32). */
 int iwae_set_precision(iwae_handle* h, int mode);
 /* Kernel path: 0 auto (train step on the bf16x3 row-chain engine where it
- * applies -- every loss but L_alpha / VAE_V1 / PIWAE, up to 3 stochastic
+ * applies -- every loss but VAE_V1 / IWAE_STL / IWAE_DREG, up to 3 stochastic
  * layers -- else the f32 fused row-block kernels up to 65536 sample rows, else
  * layer-wise GEMMs), 1 layer-wise only, 2 fused row-block kernels whenever the
  * widths allow, 3 the engine (as auto). */
@@ -362,7 +369,10 @@ double iwae_workspace_bytes(const iwae_handle* h);
  * shared with a kernel that held CUs for ~1 s, or IWAE_KNOB_TCU_WAIT_TEST;
  * each also sets the error iwae_status reports), 9 such combined launches
  * issued (a captured step counts once, at capture), 10 fused generation
- * launches (gen_kernel) issued by iwae_generate; -1 for an unknown id. */
+ * launches (gen_kernel) issued by iwae_generate; IWAE_STL / IWAE_DREG steps
+ * (a captured step counts once, at capture): 11 path-gradient encoder jobs
+ * issued on rb_bwd_kernel (path and density jobs), 12 path-gradient launches
+ * of gauss_bwd_enc_kernel (path and density); -1 for an unknown id. */
 long long iwae_debug_count(const iwae_handle* h, int what);
 /* Live kernel timing: bracket every launch of one kernel class with HIP events
  * on the handle's stream -- a GEMM class (kind: 0 forward, 1 backward-data,

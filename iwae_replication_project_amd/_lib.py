@@ -26,6 +26,7 @@ KNOBS = {
 LOSS_IDS = {
     "VAE": 0, "IWAE": 1, "VAE_V1": 2, "L_alpha": 3, "L_power_p": 4,
     "L_median": 5, "CIWAE": 6, "MIWAE": 7, "PIWAE": 8,
+    "IWAE_STL": 9, "IWAE_DREG": 10,
 }
 
 

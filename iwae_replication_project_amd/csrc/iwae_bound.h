@@ -67,7 +67,7 @@ __device__ ImgBound image_bound(const BoundArgs& a, int mode, const LwView& lw) 
     o.val = wave_sum(s) / (float)kS;          // reduce_mean (F:430)
     return o;
   }
-  if (mode == BM_IWAE || mode == BM_POWER) {
+  if (mode == BM_IWAE || mode == BM_POWER || mode == BM_SM2) {
     const float pp = mode == BM_POWER ? a.p : 1.f;
     float mx = -INFINITY;
     for (int q = lane; q < kS; q += 64) mx = fmaxf(mx, lw(q));
@@ -142,6 +142,12 @@ __device__ __forceinline__ void image_grad(const BoundArgs& a, int mode, int row
   } else if (mode == BM_IWAE || mode == BM_POWER) {
     const float pp = mode == BM_POWER ? a.p : 1.f;
     for (int q = lane; q < kS; q += 64) put(row0 + q, coef * (expf((lw(q) - ib.mx) * pp) / ib.se));
+  } else if (mode == BM_SM2) {
+    // squared normalized weights (Tucker et al. 2019, eq. 8)
+    for (int q = lane; q < kS; q += 64) {
+      const float sm = expf(lw(q) - ib.mx) / ib.se;
+      put(row0 + q, coef * (sm * sm));
+    }
   } else if (mode == BM_MEDIAN) {
     for (int q = lane; q < kS; q += 64)
       put(row0 + q, coef * (0.5f * (q == ib.lo) + 0.5f * (q == ib.hi)));

@@ -128,7 +128,8 @@ hipError_t launch_gauss_fwd(hipStream_t st, int mode, const GaussArgs& a) {
 // GradientTape semantics of log N(h; mu, s) with h = eps*s + mu: partials
 // through h AND through (mu, s) (F:59-F:73), chained into zs via ds/dzs = exp(zs).
 // Mode 0 (encoder sampling layer): block = 4 P-rows (prow_div == 1) or one
-// image (prow_div > 1; waves split its rows, LDS combine).
+// image (prow_div > 1; waves split its rows, LDS combine).  grad_mode keeps
+// both kinds of partials (GM_TOTAL) or one of them (GradMode, iwae_kernels.h).
 __global__ __launch_bounds__(256) void gauss_bwd_enc_kernel(GaussBwdArgs a) {
   __shared__ float red[2][4][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -165,14 +166,24 @@ __global__ __launch_bounds__(256) void gauss_bwd_enc_kernel(GaussBwdArgs a) {
         const float ev = E[(size_t)r * a.ld_eps + j];
         const float dl = DL[r], dlq = -dl;
         const float z = h * rs - mu * rs;
+        if (a.grad_mode == GM_DENSITY) {
+          amu += dlq * (z * rs);
+          asc += dlq * ((z * z - 1.f) * rs);
+          continue;
+        }
         float G = 0.f;
 #pragma unroll
         for (int q = 0; q < 4; ++q)
           G += bld1(rsrcs[q], q < a.nsrc ? (unsigned)(r * a.ldsrc[q] + j) * 4u : kOOB);
         if (a.std_normal) G += dl * (-h);
         G += dlq * (-z * rs);
-        amu += G + dlq * (z * rs);
-        asc += G * ev + dlq * ((z * z - 1.f) * rs);
+        if (a.grad_mode == GM_PATH) {
+          amu += G;
+          asc += G * ev;
+        } else {
+          amu += G + dlq * (z * rs);
+          asc += G * ev + dlq * ((z * z - 1.f) * rs);
+        }
       }
     }
     if (per_image) {

@@ -543,8 +543,16 @@ __global__ __launch_bounds__(RB_WAVES * 64) void rb_bwd_kernel(RbBwdLaunch L) {
             float Gq = G[q];
             if (J.std_normal) Gq += dl * (-hv[q]);
             Gq += dlq * (-z * rs);
-            dmu = Gq + dlq * (z * rs);
-            dsc = Gq * ev[q] + dlq * ((z * z - 1.f) * rs);
+            if (J.gmode == GM_PATH) {
+              dmu = Gq;
+              dsc = Gq * ev[q];
+            } else if (J.gmode == GM_DENSITY) {
+              dmu = dlq * (z * rs);
+              dsc = dlq * ((z * z - 1.f) * rs);
+            } else {
+              dmu = Gq + dlq * (z * rs);
+              dsc = Gq * ev[q] + dlq * ((z * z - 1.f) * rs);
+            }
             if (J.kl_coef != 0.f) {
               dmu += J.kl_coef * mu[q] / (float)J.kl_rows;
               dsc += J.kl_coef * (sc - rs) / (float)J.kl_rows;
@@ -553,8 +561,10 @@ __global__ __launch_bounds__(RB_WAVES * 64) void rb_bwd_kernel(RbBwdLaunch L) {
           const float dzs = dsc * ez;
           rbs[D + rr * lda + c] = dmu;
           rbs[D + rr * lda + d + c] = dzs;
-          J.dP_out[(size_t)rg * J.ld_dP + c] = dmu;
-          J.dP_out[(size_t)rg * J.ld_dP + d + c] = dzs;
+          if (J.dP_out) {                  // (null: a density job, which stores its last stage's dX only)
+            J.dP_out[(size_t)rg * J.ld_dP + c] = dmu;
+            J.dP_out[(size_t)rg * J.ld_dP + d + c] = dzs;
+          }
         }
       }
     }
@@ -607,8 +617,13 @@ __global__ __launch_bounds__(RB_WAVES * 64) void rb_bwd_kernel(RbBwdLaunch L) {
             float Gq = G[q];
             if (J.std_normal) Gq += dl * (-hv[q]);
             Gq += dlq * (-z * rs[q]);
-            amu[q] += Gq + dlq * (z * rs[q]);
-            asc[q] += Gq * ev[q] + dlq * ((z * z - 1.f) * rs[q]);
+            if (J.gmode == GM_PATH) {
+              amu[q] += Gq;
+              asc[q] += Gq * ev[q];
+            } else {
+              amu[q] += Gq + dlq * (z * rs[q]);
+              asc[q] += Gq * ev[q] + dlq * ((z * z - 1.f) * rs[q]);
+            }
           }
         }
       }

@@ -242,6 +242,14 @@ struct GaussArgs {
 // mode 2: log N(h; 0, 1)                                      (F:135-F:136)
 hipError_t launch_gauss_fwd(hipStream_t st, int mode, const GaussArgs& a);
 
+// Which partials of log q(h | .) with h = eps*s + mu an encoder Gaussian
+// backward puts into (dmu, dsc), per row with dht = dL/dh + dlq * (-z/s):
+//   GM_TOTAL    dmu = dht + dlq z/s,  dsc = dht eps + dlq (z^2 - 1)/s   (GradientTape)
+//   GM_PATH     dmu = dht,            dsc = dht eps    (through the sample only: STL / DReG)
+//   GM_DENSITY  dmu = dlq z/s,        dsc = dlq (z^2 - 1)/s   (through (mu, s) only; no dL/dh
+//               sources: the chain below it yields the density's dL/dh of the layer underneath)
+enum GradMode { GM_TOTAL = 0, GM_PATH = 1, GM_DENSITY = 2 };
+
 struct GaussBwdArgs {
   const float* P; int ldP; int prow_div; int d;
   const float* H; int ldH;
@@ -253,13 +261,15 @@ struct GaussBwdArgs {
   float* dP; int lddP;       // (dmu | dzs) per P row
   float* dh_out; int ldh_out;  // prior mode: dL/dh of the target
   int M;                     // rows of H
+  int grad_mode;             // encoder mode: GM_TOTAL (0), GM_PATH or GM_DENSITY
 };
 // mode 0: backward of an encoder sampling layer -> dP (reduced over prow_div rows)
 // mode 1: backward of a decoder prior head      -> dP (per row) and dh_out
 hipError_t launch_gauss_bwd(hipStream_t st, int mode, const GaussBwdArgs& a);
 
 // --------------------------------------------------------------- bounds ----
-enum BoundMode { BM_VAE = 0, BM_IWAE = 1, BM_POWER = 2, BM_MEDIAN = 3, BM_MIWAE = 4, BM_NONE = 5 };
+// BM_SM2: value as BM_IWAE, row weights the squared softmax (e/se)^2 (DReG's encoder weighting)
+enum BoundMode { BM_VAE = 0, BM_IWAE = 1, BM_POWER = 2, BM_MEDIAN = 3, BM_MIWAE = 4, BM_NONE = 5, BM_SM2 = 6 };
 
 struct BoundArgs {
   const float* part; const float* part2; int ldpart, npart;
@@ -269,7 +279,7 @@ struct BoundArgs {
   float* dlw2; float* dpx2;             // PIWAE second weighting (encoder), may be null
   int kS, Bimg, Bsplit;
   int mode_a; float w_a; int mode_b; float w_b;
-  int mode2;                            // weighting of dlw2 (PIWAE: MIWAE)
+  int mode2;                            // weighting of dlw2 (PIWAE: MIWAE; DReG: BM_SM2)
   float p; int k1, k2;
   float bce_w;                          // objective += bce_w * mean_s(bce row) / Bg
   float dpx_const; int dpx_is_const;    // dpx = dpx_const instead of dlw
@@ -497,8 +507,9 @@ struct RbBwdJob {
   const float* H; int ldH; const float* eps; int ld_eps; const float* dlw;
   const float* src[4]; int ldsrc[4]; int nsrc;
   int std_normal; float kl_coef; int kl_rows; int kS;
-  float* dP_out; int ld_dP; float* dh_out; int ld_dh;
+  float* dP_out; int ld_dP; float* dh_out; int ld_dh;   // (pro 1: dP_out may be null -- a dX-only density job)
   int nst; RbStage st[3];
+  int gmode;                 // pro 1 / 3: GradMode of the sampling layer's partials
 };
 struct RbBwdLaunch {
   RbBwdJob job[kRbMaxJobs];

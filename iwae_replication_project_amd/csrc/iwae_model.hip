@@ -58,6 +58,7 @@ struct Mat {
 
 struct LayerBufs {
   Mat y1, y2, P, dP, dY2, dY1;
+  Mat dPq;                     // path-gradient losses, encoder layers >= 1: dP of the density chain (layer-wise path)
 };
 
 struct KerasDense {
@@ -85,7 +86,8 @@ struct Plan {
   int dpx_const = 0;
   float dpx_val = 0.f;
   int kl = 0;                  // VAE_V1 analytic KL on the last encoder layer
-  int piwae = 0;
+  int piwae = 0;               // two backward passes: dlw / dpx for the decoder, dlw2 / dpx2 (mode2) for the encoder
+  int path = 0;                // IWAE_STL / IWAE_DREG: the encoder's gradient through the sampling path only
 };
 
 // Tuning knobs (iwae_set_tuning; ids, ranges and the measurements behind the
@@ -200,6 +202,8 @@ struct Counters {
   long long captures = 0;            // 7: train-step graphs captured (single and multi-step)
   long long tcu = 0;                 // 9: combined job I' + update launches (tcu_kernel)
   long long gen = 0;                 // 10: fused generation launches (gen_kernel)
+  long long path_rb = 0;             // 11: path-gradient encoder jobs issued on rb_bwd_kernel (path and density jobs)
+  long long path_gauss = 0;          // 12: path-gradient launches of gauss_bwd_enc_kernel (path and density)
 };
 
 // row-chain train engine plan (device resident, per shape; iwae_train.hip)
@@ -294,10 +298,12 @@ struct iwae_handle {
   size_t arena_bytes = 0;
   int cap_img = 0, cap_rows = 0;
   bool cap_train = false;
+  bool cap_path = false;             // the workspace holds the path-gradient losses' buffers (dh_encq, dPq)
   Mat x_in;
   std::vector<LayerBufs> eb, db;
   LayerBufs ob;                      // output MLP: y1 = o1, y2 = o2, P = g
   std::vector<Mat> h, eps_st, dh_out, dh_prior, dh_dec, dh_enc;
+  std::vector<Mat> dh_encq;          // path-gradient losses: dL/dh[i] through the density of q(h[i+1] | h[i])
   float *logq = nullptr, *logp = nullptr, *lw = nullptr, *dlw = nullptr, *dpx = nullptr;
   float *dlw2 = nullptr, *dpx2 = nullptr, *contrib = nullptr, *part = nullptr, *part2 = nullptr;
   float *run_m = nullptr, *run_s = nullptr;
@@ -405,14 +411,18 @@ static void free_workspace(iwae_handle* h) {
   h->arena_bytes = 0;
   h->cap_img = h->cap_rows = 0;
   h->cap_train = false;
+  h->cap_path = false;
 }
 
-static int ensure_capacity(iwae_handle* h, int Bimg, int rows, bool train) {
-  if (h->arena && Bimg <= h->cap_img && rows <= h->cap_rows && (!train || h->cap_train)) return IWAE_OK;
+// (path: a train step of a path-gradient loss, which needs dh_encq / dPq too)
+static int ensure_capacity(iwae_handle* h, int Bimg, int rows, bool train, bool path = false) {
+  if (h->arena && Bimg <= h->cap_img && rows <= h->cap_rows && (!train || h->cap_train) && (!path || h->cap_path))
+    return IWAE_OK;
   HIPCHK(hipStreamSynchronize(h->stream));
   Bimg = std::max(Bimg, h->cap_img);
   rows = std::max(rows, h->cap_rows);
   train = train || h->cap_train;
+  path = path || h->cap_path;
   free_workspace(h);
   // ---- layout pass (offsets in floats, 64-float aligned)
   size_t off = 0;
@@ -439,6 +449,7 @@ static int ensure_capacity(iwae_handle* h, int Bimg, int rows, bool train) {
   h->dh_prior.assign(L, Mat());
   h->dh_dec.assign(L, Mat());
   h->dh_enc.assign(L, Mat());
+  h->dh_encq.assign(L, Mat());
   mat(h->x_in, Bimg, h->xdim + 1);
   for (int i = 0; i < L; ++i) {
     const StochL& s = h->enc[i];
@@ -478,6 +489,8 @@ static int ensure_capacity(iwae_handle* h, int Bimg, int rows, bool train) {
       const int di = h->enc[i].d;
       if (i <= L - 2) { mat(h->dh_prior[i], rows, di); mat(h->dh_enc[i], rows, di); }
       if (i >= 1) mat(h->dh_dec[i], rows, di);
+      if (path && i <= L - 2) mat(h->dh_encq[i], rows, di);
+      if (path && i >= 1) mat(h->eb[i].dPq, rows, 2 * di);
     }
   }
   h->npart = (int)cdiv(h->xdim, 32);
@@ -542,6 +555,7 @@ static int ensure_capacity(iwae_handle* h, int Bimg, int rows, bool train) {
   h->cap_img = Bimg;
   h->cap_rows = rows;
   h->cap_train = train;
+  h->cap_path = train && path;
   return IWAE_OK;
 }
 
@@ -669,6 +683,17 @@ static int stoch_bwd(iwae_handle* h, const StochL& s, const Mat& in, int rows, L
   return IWAE_OK;
 }
 
+// dX-only pass of an encoder layer's density chain (path-gradient losses):
+// b.dPq through the three transposed layers into dx, no weight gradients.
+// b.dY2 / b.dY1 are its scratch: stoch_bwd's weight-gradient GEMMs, their only
+// readers, are ahead of it on the stream.
+static int stoch_bwd_dx(iwae_handle* h, const StochL& s, int rows, LayerBufs& b, Mat& dx) {
+  CHK(gemm_bwd_data(h, b.dPq, rows, h->dense[s.head], b.dY2, &b.y2, nullptr));
+  CHK(gemm_bwd_data(h, b.dY2, rows, h->dense[s.l2], b.dY1, &b.y1, nullptr));
+  CHK(gemm_bwd_data(h, b.dY1, rows, h->dense[s.l1], dx, nullptr, nullptr));
+  return IWAE_OK;
+}
+
 // ------------------------------------------------------------ loss plan
 static int make_plan(iwae_handle* h, const iwae_loss_config* lc, int B, Plan& P) {
   if (!lc) return fail(h, IWAE_EINVAL, "loss config is NULL");
@@ -681,6 +706,11 @@ static int make_plan(iwae_handle* h, const iwae_loss_config* lc, int B, Plan& P)
   switch (lc->loss) {
     case IWAE_LOSS_VAE: P.mode_a = BM_VAE; break;
     case IWAE_LOSS_IWAE: P.mode_a = BM_IWAE; break;
+    // value and decoder gradient of IWAE; the encoder's through the sampling
+    // path only, weighted by the softmax (STL) or its square (DReG: a second
+    // pass on dlw2 / dpx2, PIWAE's structure)
+    case IWAE_LOSS_IWAE_STL: P.mode_a = BM_IWAE; P.path = 1; break;
+    case IWAE_LOSS_IWAE_DREG: P.mode_a = BM_IWAE; P.mode2 = BM_SM2; P.piwae = 1; P.path = 1; break;
     case IWAE_LOSS_L_POWER_P:
       if (!(lc->p > 0.f) && !(lc->p < 0.f)) return fail(h, IWAE_EINVAL, "L_power_p needs p != 0");
       P.mode_a = BM_POWER; break;
@@ -903,9 +933,12 @@ static int encoder_bwd(iwae_handle* h, const Plan& P, const float* dlw) {
       g.src[n] = h->dh_enc[i].p; g.ldsrc[n++] = h->dh_enc[i].ld;
     }
     if (i >= 1) { g.src[n] = h->dh_dec[i].p; g.ldsrc[n++] = h->dh_dec[i].ld; }
+    if (P.path && i <= L - 2) { g.src[n] = h->dh_encq[i].p; g.ldsrc[n++] = h->dh_encq[i].ld; }
     g.nsrc = n;
     g.std_normal = i == L - 1;
     g.dlw = dlw;
+    g.grad_mode = P.path ? GM_PATH : GM_TOTAL;
+    if (P.path) h->count.path_gauss++;
     if (P.kl && i == L - 1) {
       g.kl_coef = 1.f;   // dLoss/dKL_mean for loss = -(E - KL)
       g.kl_rows = (L == 1) ? P.Bimg : M;
@@ -916,6 +949,20 @@ static int encoder_bwd(iwae_handle* h, const Plan& P, const float* dlw) {
     const Mat& in = i == 0 ? h->x_in : h->h[i - 1];
     const int rows = i == 0 ? P.Bimg : M;
     CHK(stoch_bwd(h, h->enc[i], in, rows, h->eb[i], true, i > 0 ? &h->dh_enc[i - 1] : nullptr));
+    if (P.path && i > 0) {
+      // q(h_i | h_{i-1}) depends on h_{i-1} through (mu, s) too: that is a path
+      // of the layer below, so the density partials still send their dX down
+      GaussBwdArgs q{};
+      q.P = g.P; q.ldP = g.ldP; q.prow_div = 1; q.d = g.d;
+      q.H = g.H; q.ldH = g.ldH; q.eps_rows = g.eps_rows; q.ld_eps = g.ld_eps;
+      q.dlw = dlw;
+      q.grad_mode = GM_DENSITY;
+      q.dP = h->eb[i].dPq.p; q.lddP = h->eb[i].dPq.ld;
+      q.M = M;
+      HIPCHK(launch_gauss_bwd(h->stream, 0, q));
+      h->count.path_gauss++;
+      CHK(stoch_bwd_dx(h, h->enc[i], M, h->eb[i], h->dh_encq[i - 1]));
+    }
   }
   return IWAE_OK;
 }
@@ -1103,8 +1150,10 @@ static int rb_ld(const iwae_handle* h, bool bwd) {
     if (!first) w = std::max(w, d.fin + 1);
     if (!out) w = std::max(w, d.fout + 1);
   }
-  (void)bwd;
-  return rb_k_pad(std::min(w, kRbMaxWidth), false) + 4;
+  // (the backward stages pad to 64 at least, the forward ones to 32: a model
+  // whose every width is below 32 needs the wider backward row, else the
+  // padding of one LDS row lands in the next)
+  return rb_k_pad(std::min(w, kRbMaxWidth), bwd) + 4;
 }
 
 static RbStage rb_fwd_stage(iwae_handle* h, int di, int act, Mat* out) {
@@ -1473,8 +1522,10 @@ static int fused_encoder_bwd(iwae_handle* h, const Plan& P, const float* dlw, in
       J.src[n] = h->dh_enc[i].p; J.ldsrc[n++] = h->dh_enc[i].ld;
     }
     if (i >= 1) { J.src[n] = h->dh_dec[i].p; J.ldsrc[n++] = h->dh_dec[i].ld; }
+    if (P.path && i <= L - 2) { J.src[n] = h->dh_encq[i].p; J.ldsrc[n++] = h->dh_encq[i].ld; }
     J.nsrc = n;
     J.std_normal = i == L - 1;
+    J.gmode = P.path ? GM_PATH : GM_TOTAL;
     if (P.kl && i == L - 1) { J.kl_coef = 1.f; J.kl_rows = (L == 1) ? P.Bimg : M; }
     J.dP_out = h->eb[i].dP.p; J.ld_dP = h->eb[i].dP.ld;
     const bool sm0 = i == 0 && smallm_ok(h, P.Bimg);
@@ -1485,6 +1536,24 @@ static int fused_encoder_bwd(iwae_handle* h, const Plan& P, const float* dlw, in
     }
     if (i > 0) J.st[2] = rb_bwd_stage(h, S.l1, nullptr, &h->dh_enc[i - 1]);
     Lb.njobs = 1;
+    if (P.path) h->count.path_rb++;
+    if (P.path && i > 0) {
+      // the density job, beside the path job: the layer's density partials
+      // through the same three transposed layers, storing only the final dX
+      // (dh_encq[i - 1]) -- dP / dY2 / dY1 stay the path job's (weight_grads)
+      RbBwdJob& Q = Lb.job[1];
+      Q.pro = 1; Q.rows = M; Q.rpb = 16; Q.kS = kS;
+      Q.P = J.P; Q.ldP = J.ldP; Q.d = J.d;
+      Q.H = J.H; Q.ldH = J.ldH; Q.eps = J.eps; Q.ld_eps = J.ld_eps;
+      Q.dlw = dlw;
+      Q.gmode = GM_DENSITY;
+      Q.nst = 3;
+      Q.st[0] = rb_bwd_stage(h, S.head, &h->eb[i].y2, nullptr);
+      Q.st[1] = rb_bwd_stage(h, S.l2, &h->eb[i].y1, nullptr);
+      Q.st[2] = rb_bwd_stage(h, S.l1, nullptr, &h->dh_encq[i - 1]);
+      Lb.njobs = 2;
+      h->count.path_rb++;
+    }
     HIPCHK(launch_rb_bwd(h->stream, Lb));
     if (sm0) {
       // first encoder layer's head and l2 backward as N-split few-row launches
@@ -1824,6 +1893,7 @@ constexpr int kTcMaxLayers = 3;      // op-table capacity: 4 ops per stochastic 
 static bool use_engine(const iwae_handle* h, const Plan& P) {
   if (!h->tune.engine || !h->x3 || h->path == 1 || h->path == 2 || h->masked) return false;
   if (P.kl) return false;       // VAE_V1's analytic KL: fused row-block path
+  if (P.path) return false;     // IWAE_STL / IWAE_DREG: the engine's Gaussian backward has no gradient modes
   if (h->L > kTcMaxLayers || h->enc[0].d > 2048) return false;   // (image-row backward: d / 4 column quads)
   const long long rows = (long long)P.Bimg * P.kS;
   if (rows > (1LL << 18)) return false;
@@ -2572,7 +2642,7 @@ static int fused_train_body(iwae_handle* h, const Plan& P, const EpsSet& E, bool
   if (P.piwae) {
     CHK(fused_decoder_bwd(h, P, h->dlw, h->dpx, false));      // decoder weights: IWAE_{k1 k2}
     CHK(weight_grads(h, P, false, true, h->dpx));
-    CHK(fused_decoder_bwd(h, P, h->dlw2, h->dpx2, true));     // encoder path: MIWAE(k1, k2)
+    CHK(fused_decoder_bwd(h, P, h->dlw2, h->dpx2, true));     // encoder path: MIWAE(k1, k2) (DReG: softmax^2)
     CHK(fused_encoder_bwd(h, P, h->dlw2));
     CHK(weight_grads(h, P, true, false, nullptr));
   } else {
@@ -2595,7 +2665,7 @@ static int train_body(iwae_handle* h, const Plan& P, const EpsSet& E, bool adam)
   CHK(run_bound(h, P, true, -1.f, train_loss_ptr(h), adam));
   if (P.piwae) {
     CHK(decoder_bwd(h, P, h->dlw, h->dpx, true, false));      // decoder: IWAE_{k1 k2}
-    CHK(decoder_bwd(h, P, h->dlw2, h->dpx2, false, true));    // encoder path: MIWAE(k1,k2)
+    CHK(decoder_bwd(h, P, h->dlw2, h->dpx2, false, true));    // encoder path: MIWAE(k1,k2) (DReG: softmax^2)
     CHK(encoder_bwd(h, P, h->dlw2));
   } else {
     CHK(decoder_bwd(h, P, h->dlw, h->dpx, true, true));
@@ -2722,7 +2792,7 @@ static int do_train(iwae_handle* h, const iwae_loss_config* lc, const float* x, 
   CHK(make_plan(h, lc, B, P));
   EpsSet E;
   CHK(parse_eps(h, P, eps, n_eps, E));
-  CHK(ensure_capacity(h, P.Bimg, P.Bimg * P.kS, true));
+  CHK(ensure_capacity(h, P.Bimg, P.Bimg * P.kS, true, P.path != 0));
   const bool engine = use_engine(h, P);
   if (engine) CHK(prepare_engine(h, P));
   // the fused step's first kernel reads the caller's x itself (and fills x_in);
@@ -2814,7 +2884,7 @@ static int do_train_steps(iwae_handle* h, const iwae_loss_config* lc, const floa
   CHK(make_plan(h, lc, B, P));
   EpsSet E;
   CHK(parse_eps(h, P, nullptr, 0, E));
-  CHK(ensure_capacity(h, P.Bimg, P.Bimg * P.kS, true));
+  CHK(ensure_capacity(h, P.Bimg, P.Bimg * P.kS, true, P.path != 0));
   const bool engine = use_engine(h, P);
   // (the engine step refreshes every copy it reads inside the step; other
   // paths decide their split-copy refreshes on the host at capture time)
@@ -4172,6 +4242,8 @@ long long iwae_debug_count(const iwae_handle* h, int what) {
     }
     case 9: return h->count.tcu;
     case 10: return h->count.gen;
+    case 11: return h->count.path_rb;
+    case 12: return h->count.path_gauss;
     default: return -1;
   }
 }

@@ -21,6 +21,11 @@ Differences a user of the reference should know about (all deliberate):
   * ``loss_function`` additionally accepts "MIWAE" and "PIWAE" (k = k1*k2,
     IWAE_replication.pdf p7); an unknown name raises ValueError where the
     reference hits UnboundLocalError (F:242).
+  * ``loss_function`` also accepts "IWAE_STL" (Roeder et al. 2017) and
+    "IWAE_DREG" (Tucker et al. 2019): the IWAE loss value and decoder gradient,
+    the encoder's gradient taken through the sampling path only (weights
+    softmax / softmax squared).  They run on the fused row-block or layer-wise
+    kernels (``kernel_path`` "auto", "fused", "layerwise"), not on the engine.
 """
 from __future__ import annotations
 
