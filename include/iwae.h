@@ -191,10 +191,14 @@ int iwae_set_tuning(iwae_handle* h, int knob, long long value);
  * tiled GEMMs' largest tile also 32x32x2_f32). */
 int iwae_set_precision(iwae_handle* h, int mode);
 /* Kernel path: 0 auto (train step on the bf16x3 row-chain engine where it
- * applies -- every loss but VAE_V1 / IWAE_STL / IWAE_DREG, up to 3 stochastic
- * layers -- else the f32 fused row-block kernels up to 65536 sample rows, else
+ * applies -- every loss but VAE_V1 / IWAE_STL / IWAE_DREG and L_power_p with
+ * p < 0 (whose row weights amplify the bf16x3 rounding), up to 3 stochastic
+ * layers, layer widths whose plan fits 160 KB of LDS at 16 rows per workgroup
+ * (hidden widths up to about 1200) -- else the f32 fused row-block kernels up
+ * to 65536 sample rows, 4 stochastic layers and layer widths of 511, else
  * layer-wise GEMMs), 1 layer-wise only, 2 fused row-block kernels whenever the
- * widths allow, 3 the engine (as auto). */
+ * depth and widths allow, 3 the engine (as auto).  A path that does not apply
+ * to the model is never an error: the next one in that order runs. */
 int iwae_set_path(iwae_handle* h, int path);
 
 /* --- parameters (synchronous host copies) --------------------------------- */
@@ -305,7 +309,13 @@ int iwae_nll(iwae_handle* h, const float* x, int N, int k, int chunk, float* out
  * log p(x) = M + log S - log(k_total). */
 int iwae_nll_partials(iwae_handle* h, const float* x, int N, int k_local, int chunk,
                       float* out_m, float* out_s);
-/* Same as iwae_nll with injected noise (parity tests): eps[i] is [k][N][d_i]. */
+/* Same as iwae_nll with injected noise (parity tests): eps[i] is [k][N][d_i].
+ * Where the fused NLL kernel applies (bf16x3 precision, not iwae_set_path(h, 1),
+ * at most 4 stochastic layers -- 24 stages -- and layer widths whose plan
+ * fits 160 KB of LDS) it runs, chunk by chunk, on the caller's noise.  Where it
+ * does not, the call is not an error: all N * k sample rows run as ONE forward
+ * pass on the row-block or layer-wise kernels (no chunking: the workspace
+ * grows to N * k rows), with the same result. */
 int iwae_nll_eps(iwae_handle* h, const float* x, int N, int k, const float* const* eps,
                  int n_eps, float* out_logpx);
 
@@ -372,7 +382,14 @@ double iwae_workspace_bytes(const iwae_handle* h);
  * launches (gen_kernel) issued by iwae_generate; IWAE_STL / IWAE_DREG steps
  * (a captured step counts once, at capture): 11 path-gradient encoder jobs
  * issued on rb_bwd_kernel (path and density jobs), 12 path-gradient launches
- * of gauss_bwd_enc_kernel (path and density); -1 for an unknown id. */
+ * of gauss_bwd_enc_kernel (path and density); 13 row-block forward launches
+ * (rb_fwd_kernel: train steps and evaluation passes on the fused row-block
+ * path; none on the engine's small-batch steps or the layer-wise path), 14
+ * fused update launches (update_kernel: weight gradients, Adam and the
+ * fragment-major copies) issued, or recorded for the combined launch of id 9,
+ * by a train step (a captured step counts once, at capture; 0 on the row-block
+ * and layer-wise paths, whose steps end in the GEMM + Adam launches); -1 for
+ * an unknown id. */
 long long iwae_debug_count(const iwae_handle* h, int what);
 /* Live kernel timing: bracket every launch of one kernel class with HIP events
  * on the handle's stream -- a GEMM class (kind: 0 forward, 1 backward-data,

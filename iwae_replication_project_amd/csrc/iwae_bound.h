@@ -69,14 +69,18 @@ __device__ ImgBound image_bound(const BoundArgs& a, int mode, const LwView& lw) 
   }
   if (mode == BM_IWAE || mode == BM_POWER || mode == BM_SM2) {
     const float pp = mode == BM_POWER ? a.p : 1.f;
+    // the shift is the extremum that keeps every exponent (lw - mx) p <= 0:
+    // the largest lw, or for p < 0 the smallest (the value is the same for any
+    // shift; the largest one overflows expf once the spread of lw exceeds 88 / |p|)
+    const float sg = pp < 0.f ? -1.f : 1.f;
     float mx = -INFINITY;
-    for (int q = lane; q < kS; q += 64) mx = fmaxf(mx, lw(q));
-    mx = wave_max(mx);
+    for (int q = lane; q < kS; q += 64) mx = fmaxf(mx, sg * lw(q));
+    mx = sg * wave_max(mx);
     float se = 0.f;
     for (int q = lane; q < kS; q += 64) se += expf((lw(q) - mx) * pp);
     se = wave_sum(se);
     o.mx = mx; o.se = se;
-    // F:369: log(reduce_mean(exp(lw - max))) + max ; F:408: .../p + max
+    // F:369: log(reduce_mean(exp(lw - max))) + max ; F:408: .../p + max (p < 0: min)
     o.val = (mode == BM_POWER) ? logf(se / (float)kS) / pp + mx : logf(se / (float)kS) + mx;
     return o;
   }

@@ -204,6 +204,8 @@ struct Counters {
   long long gen = 0;                 // 10: fused generation launches (gen_kernel)
   long long path_rb = 0;             // 11: path-gradient encoder jobs issued on rb_bwd_kernel (path and density jobs)
   long long path_gauss = 0;          // 12: path-gradient launches of gauss_bwd_enc_kernel (path and density)
+  long long rb_fwd = 0;              // 13: row-block forward launches (rb_fwd_kernel)
+  long long upd = 0;                 // 14: fused update launches issued or recorded by run_update
 };
 
 // row-chain train engine plan (device resident, per shape; iwae_train.hip)
@@ -319,6 +321,7 @@ struct iwae_handle {
   bool masked = false;               // active-unit masks in force (iwae_nll_masked only)
   const float* mask[IWAE_MAX_LAYERS] = {};
   std::map<std::vector<long long>, TcRec> tc_plans;     // engine plans per shape
+  int tc_fit[2] = {-1, -1};          // whether the engine's plans fit the LDS (tc_fits; [1]: with fold0), -1 unknown
   std::map<std::vector<long long>, GraphRec> graphs;    // captured train steps per graph key
 };
 
@@ -1156,6 +1159,13 @@ static int rb_ld(const iwae_handle* h, bool bwd) {
   return rb_k_pad(std::min(w, kRbMaxWidth), bwd) + 4;
 }
 
+// every row-block forward launch goes through here (iwae_debug_count id 13)
+static int run_rb_fwd(iwae_handle* h, RbFwdLaunch& Lf) {
+  HIPCHK(launch_rb_fwd(h->stream, Lf));
+  h->count.rb_fwd++;
+  return IWAE_OK;
+}
+
 static RbStage rb_fwd_stage(iwae_handle* h, int di, int act, Mat* out) {
   const DenseL& d = h->dense[di];
   RbStage s{};
@@ -1320,7 +1330,7 @@ static int enc0_forward(iwae_handle* h, const Plan& P, bool l1_only = false) {
     J.st[0] = rb_fwd_stage(h, h->enc[0].l2, 1, &h->eb[0].y2);
     J.st[1] = rb_fwd_stage(h, h->enc[0].head, 0, &h->eb[0].P);
     Lf.njobs = 1;
-    HIPCHK(launch_rb_fwd(h->stream, Lf));
+    CHK(run_rb_fwd(h, Lf));
   }
   return IWAE_OK;
 }
@@ -1355,7 +1365,7 @@ static int fused_forward(iwae_handle* h, const Plan& P, const EpsSet& E, bool tr
     J.ep_eps = train ? h->eps_st[i].p : nullptr; J.ep_ldeps = train ? h->eps_st[i].ld : 0;
     J.logq = h->logq;
     Lf.njobs = 1;
-    HIPCHK(launch_rb_fwd(h->stream, Lf));
+    CHK(run_rb_fwd(h, Lf));
   }
   // (4) decoder prior layers and the output MLP's two hidden layers
   {
@@ -1395,7 +1405,7 @@ static int fused_forward(iwae_handle* h, const Plan& P, const EpsSet& E, bool tr
       J.st[1] = rb_fwd_stage(h, h->o2, 1, &h->ob.y2);
     }
     Lf.njobs = nj;
-    HIPCHK(launch_rb_fwd(h->stream, Lf));
+    CHK(run_rb_fwd(h, Lf));
   }
   // deeper decoder layers (L >= 3) accumulate into log p one launch at a time
   for (int i = 1; i < L - 1; ++i) {
@@ -1412,7 +1422,7 @@ static int fused_forward(iwae_handle* h, const Plan& P, const EpsSet& E, bool tr
     J.epi = 2; J.ep_d = S.d; J.ep_tgt = h->h[L - 2 - i].p; J.ep_ldtgt = h->h[L - 2 - i].ld;
     J.logp = h->logp; J.logp_acc = 1;
     Lf.njobs = 1;
-    HIPCHK(launch_rb_fwd(h->stream, Lf));
+    CHK(run_rb_fwd(h, Lf));
   }
   // (5) output layer 200 -> 784 with the fused Bernoulli epilogue
   {
@@ -1755,6 +1765,7 @@ static int run_update(iwae_handle* h, const Plan& P, bool adam, int bucket = 0, 
   a.gscale = slabs ? 1.f : gscale; a.tail = (slabs || apply) ? nullptr : tail; a.tail_val = gscale;
   a.apply = apply ? (from_slabs ? 2 : 1) : 0; a.scale_dev = scale_dev;
   a.waves = h->tune.upd_waves;
+  h->count.upd++;
   if (h->step.defer_launch && st == h->stream && !slabs && !apply) {
     // recorded for a combined launch (tcu_kernel) with job I': the first
     // encoder layer's jobs are the ones that wait for it
@@ -1890,10 +1901,17 @@ static int run_dw(iwae_handle* h, const Plan& P) {
 // copies the engine reads).  See iwae_train.hip.
 constexpr int kTcMaxLayers = 3;      // op-table capacity: 4 ops per stochastic layer and direction
 
+static bool tc_fits(const iwae_handle* h, const Plan& P);
+
 static bool use_engine(const iwae_handle* h, const Plan& P) {
   if (!h->tune.engine || !h->x3 || h->path == 1 || h->path == 2 || h->masked) return false;
   if (P.kl) return false;       // VAE_V1's analytic KL: fused row-block path
   if (P.path) return false;     // IWAE_STL / IWAE_DREG: the engine's Gaussian backward has no gradient modes
+  // L_power_p with p < 0: the row weights softmax(p lw) sit on each image's smallest
+  // log-weights, the ones of the largest magnitude, and scale the engine's bf16x3
+  // rounding of lw by |p| (3 layers, p = -1.5: gradient 1.7e-4 off float64 against
+  // 3e-6 on the f32 row-block kernels, which run instead)
+  if (P.mode_a == BM_POWER && P.p < 0.f) return false;
   if (h->L > kTcMaxLayers || h->enc[0].d > 2048) return false;   // (image-row backward: d / 4 column quads)
   const long long rows = (long long)P.Bimg * P.kS;
   if (rows > (1LL << 18)) return false;
@@ -1903,7 +1921,10 @@ static bool use_engine(const iwae_handle* h, const Plan& P) {
   long long w = h->xdim;
   for (const DenseL& d : h->dense) w = std::max<long long>(w, std::max(d.fout, d.fin + 1));
   w = (w + 31) / 32 * 32;
-  return rows * w * (long long)sizeof(float) < (1LL << 31);
+  if (rows * w * (long long)sizeof(float) >= (1LL << 31)) return false;
+  // layers too wide for the engine's LDS plan at 16 rows per workgroup: the
+  // row-block kernels (up to kRbMaxWidth) or the layer-wise ones run
+  return tc_fits(h, P);
 }
 
 struct TcBuild {
@@ -1996,16 +2017,16 @@ static std::vector<long long> tc_key(const Plan& P, int which) {
   return {which, P.Bimg, P.Bsplit, P.kS};
 }
 
-// Plans of this shape, built once and uploaded: which = 0 the sample-row
-// forward launch, 1 the sample-row backward launch, 2 / 3 the first encoder
-// layer's image-row forward (after its input Dense) / backward launch.
-static int tc_prepare_one(iwae_handle* h, const Plan& P, int which) {
-  const auto key = tc_key(P, which);
-  if (h->tc_plans.count(key)) return IWAE_OK;
+// wide workgroups (32 / 64 sample rows, two-set weight pipeline) for large batches
+static bool tc_wide(const iwae_handle* h, const Plan& P, int which) {
+  return (which <= 1 || which >= 4) && (long long)P.Bimg * P.kS >= h->tune.wide_rows;
+}
+
+// The jobs of launch `which` (see tc_prepare_one): op tables and the buffer
+// widths the LDS layout needs.  Reads the handle only.
+static std::vector<TcBuild> tc_build_jobs(iwae_handle* h, const Plan& P, int which) {
   const int L = h->L, kS = P.kS;
-  auto r32 = [](int x) { return (x + 31) & ~31; };
-  // wide workgroups (32 / 64 sample rows, two-set weight pipeline) for large batches
-  const bool wide = (which <= 1 || which >= 4) && (long long)P.Bimg * kS >= h->tune.wide_rows;
+  const bool wide = tc_wide(h, P, which);
   std::vector<TcBuild> jobs;
   const bool fold0 = which == 0 && use_fold0(h, P);
   auto ldF = [&](int di) { return h->dense[di].ldF; };
@@ -2197,7 +2218,51 @@ static int tc_prepare_one(iwae_handle* h, const Plan& P, int which) {
       jobs.push_back(B);
     }
   }
-  (void)r32;
+  return jobs;
+}
+
+// LDS bytes of one launch's jobs at rt row tiles: the widest job's buffers,
+// then the per-row accumulators (log q, log p, [4][8 waves] partials, the
+// in-launch bound's dL/dlw and dpx); acc_off: their float offset
+static size_t tc_lds_bytes(std::vector<TcBuild>& jobs, int rt, int* acc_off = nullptr) {
+  size_t mx = 0;
+  for (auto& B : jobs) mx = std::max(mx, tc_layout(B, rt));
+  const int off = (int)((mx + 15) / 16 * 4);          // floats, 16-byte aligned
+  if (acc_off) *acc_off = off;
+  return (size_t)off * sizeof(float) + (size_t)(4 + 4 * 8) * 16 * rt * sizeof(float);
+}
+
+constexpr size_t kTcLdsBytes = 160 * 1024;
+
+// Whether every launch of an engine step has a plan that fits the LDS at the
+// smallest workgroup (one 16-row tile).  It depends on the layer widths and,
+// through fold0, on whether the batch takes the few-row launches: decided
+// once per model for each, so use_engine() can decline the engine (the step
+// then runs on the row-block or the layer-wise kernels) instead of failing in
+// tc_prepare_one.  (Launches 4 and 5 run subsets of launch 1's jobs.)
+static bool tc_fits(const iwae_handle* ch, const Plan& P) {
+  iwae_handle* h = const_cast<iwae_handle*>(ch);     // (the builders only read it)
+  if ((int)h->eb.size() < h->L) return true;          // no workspace yet: decided at the first step
+  int& fit = h->tc_fit[use_fold0(h, P) ? 1 : 0];
+  if (fit < 0) {
+    fit = 1;
+    for (int which : {0, 1, 2, 3}) {
+      std::vector<TcBuild> jobs = tc_build_jobs(h, P, which);
+      if (tc_lds_bytes(jobs, 1) > kTcLdsBytes) fit = 0;
+    }
+  }
+  return fit == 1;
+}
+
+// Plans of this shape, built once and uploaded: which = 0 the sample-row
+// forward launch, 1 the sample-row backward launch, 2 / 3 the first encoder
+// layer's image-row forward (after its input Dense) / backward launch.
+static int tc_prepare_one(iwae_handle* h, const Plan& P, int which) {
+  const auto key = tc_key(P, which);
+  if (h->tc_plans.count(key)) return IWAE_OK;
+  const int kS = P.kS;
+  const bool wide = tc_wide(h, P, which);
+  std::vector<TcBuild> jobs = tc_build_jobs(h, P, which);
   if ((int)jobs.size() > kTcMaxJobs) return fail(h, IWAE_EINVAL, "engine: too many jobs");
   // rows per workgroup: the largest tile count the LDS allows, fewer for small batches
   const bool img = which == 2 || which == 3;
@@ -2213,17 +2278,9 @@ static int tc_prepare_one(iwae_handle* h, const Plan& P, int which) {
   TcRec rec;
   for (int rt : {4, 2, 1}) {
     if (rt > want) continue;
-    size_t mx = 0;
     int acc_off = 0;
-    for (auto& B : jobs) {
-      const size_t b = tc_layout(B, rt);
-      mx = std::max(mx, b);
-    }
-    acc_off = (int)((mx + 15) / 16 * 4);            // floats, 16-byte aligned
-    // per-row accumulators: log q, log p, [4][8 waves] partials, the in-launch
-    // bound's dL/dlw and dpx
-    const size_t lds = (size_t)acc_off * sizeof(float) + (size_t)(4 + 4 * 8) * 16 * rt * sizeof(float);
-    if (lds <= 160 * 1024) {
+    const size_t lds = tc_lds_bytes(jobs, rt, &acc_off);
+    if (lds <= kTcLdsBytes) {
       rec.rt = rt;
       rec.lds = lds;
       rec.acc_off = acc_off;
@@ -4244,6 +4301,8 @@ long long iwae_debug_count(const iwae_handle* h, int what) {
     case 10: return h->count.gen;
     case 11: return h->count.path_rb;
     case 12: return h->count.path_gauss;
+    case 13: return h->count.rb_fwd;
+    case 14: return h->count.upd;
     default: return -1;
   }
 }

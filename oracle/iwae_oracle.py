@@ -277,8 +277,9 @@ def L_from_weights(lw):
 
 
 def L_power_p_from_weights(lw, p):
-    """F:405-F:409."""
-    m = lw.max(axis=0)
+    """F:405-F:409.  (p < 0: shifted by the smallest lw instead of the largest --
+    the same value, and exp((lw - m) p) stays <= 1 in float32 as well.)"""
+    m = lw.max(axis=0) if p > 0 else lw.min(axis=0)
     return np.mean(np.log(np.mean(np.exp((lw - m) * p), axis=0)) / p + m)
 
 
