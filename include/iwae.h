@@ -388,8 +388,12 @@ double iwae_workspace_bytes(const iwae_handle* h);
  * fused update launches (update_kernel: weight gradients, Adam and the
  * fragment-major copies) issued, or recorded for the combined launch of id 9,
  * by a train step (a captured step counts once, at capture; 0 on the row-block
- * and layer-wise paths, whose steps end in the GEMM + Adam launches); -1 for
- * an unknown id. */
+ * and layer-wise paths, whose steps end in the GEMM + Adam launches); 15
+ * bound_kernel launches issued by train steps and forward-only bounds (a
+ * captured step counts once, at capture; none where the engine's backward
+ * launch computes the bound itself), 16 those of them with more than one
+ * workgroup (more than 64 images and more than 8192 sample rows); -1 for an
+ * unknown id. */
 long long iwae_debug_count(const iwae_handle* h, int what);
 /* Live kernel timing: bracket every launch of one kernel class with HIP events
  * on the handle's stream -- a GEMM class (kind: 0 forward, 1 backward-data,

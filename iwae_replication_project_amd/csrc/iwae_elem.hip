@@ -273,14 +273,18 @@ __global__ __launch_bounds__(kBoundWaves * 64) void bound_kernel(BoundArgs a) {
   }
 }
 
+// workgroups of a bound launch; small batches: one (no cross-workgroup hand-off at all)
+int bound_grid(const BoundArgs& a) {
+  const int rows = a.Bimg * a.kS;
+  return (a.Bimg <= 4 * kBoundWaves || rows <= 8192) ? 1 : (a.Bimg + kBoundWaves - 1) / kBoundWaves;
+}
+
 hipError_t launch_bound(hipStream_t st, const BoundArgs& a) {
   if (a.Bimg <= 0) return hipSuccess;
   auto needs_lds = [](int m) { return m == BM_MEDIAN || m == BM_MIWAE; };
   if ((needs_lds(a.mode_a) || needs_lds(a.mode_b) || needs_lds(a.mode2)) && a.kS > 1024)
     return hipErrorInvalidValue;
-  // small batches: one workgroup (no cross-workgroup hand-off at all)
-  const int rows = a.Bimg * a.kS;
-  int grid = (a.Bimg <= 4 * kBoundWaves || rows <= 8192) ? 1 : (a.Bimg + kBoundWaves - 1) / kBoundWaves;
+  const int grid = bound_grid(a);
   if (grid > 1 && !a.ticket) return hipErrorInvalidValue;
   hipLaunchKernelGGL(bound_kernel, dim3(grid), dim3(kBoundWaves * 64), 0, st, a);
   return hipGetLastError();

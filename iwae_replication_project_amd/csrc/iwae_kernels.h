@@ -290,6 +290,7 @@ struct BoundArgs {
   long long* adam_step;                 // train step with Adam: advance the step counter (or null)
 };
 hipError_t launch_bound(hipStream_t st, const BoundArgs& a);
+int bound_grid(const BoundArgs& a);    // its workgroups
 
 // per-image LSE over this chunk's rows merged into running (m, s)
 struct LseArgs {

@@ -206,6 +206,7 @@ struct Counters {
   long long path_gauss = 0;          // 12: path-gradient launches of gauss_bwd_enc_kernel (path and density)
   long long rb_fwd = 0;              // 13: row-block forward launches (rb_fwd_kernel)
   long long upd = 0;                 // 14: fused update launches issued or recorded by run_update
+  long long bound = 0, bound_multi = 0;  // 15, 16: bound_kernel launches (all / with more than one workgroup)
 };
 
 // row-chain train engine plan (device resident, per shape; iwae_train.hip)
@@ -877,6 +878,8 @@ static int run_bound(iwae_handle* h, const Plan& P, bool train, float sign, floa
   }
   const BoundArgs b = make_bound_args(h, P, train, sign, value_out, adam_tick, engine);
   HIPCHK(launch_bound(h->stream, b));
+  h->count.bound++;
+  if (bound_grid(b) > 1) h->count.bound_multi++;
   if (h->prof.kind == 13 && !h->prof.have) {
     // replays write the loss, Philox base and Adam step into scratch instead
     if (!h->prof.scratch) HIPCHK(hipMalloc(&h->prof.scratch, 64 * sizeof(float)));
@@ -4303,6 +4306,8 @@ long long iwae_debug_count(const iwae_handle* h, int what) {
     case 12: return h->count.path_gauss;
     case 13: return h->count.rb_fwd;
     case 14: return h->count.upd;
+    case 15: return h->count.bound;
+    case 16: return h->count.bound_multi;
     default: return -1;
   }
 }
