@@ -647,24 +647,25 @@ static int gemm_bwd_data(iwae_handle* h, const Mat& dZ, int rows, const DenseL& 
   return IWAE_OK;
 }
 
-// slabs of dW_aug[fin+1][fout] = X_aug[rows][fin+1]^T . dZ[rows][fout], split over rows
-static int gemm_bwd_weight(iwae_handle* h, const Mat& X, const Mat& dZ, int rows, DenseL& d,
-                           const float* kscale) {
+// slabs of dW_aug[fin+1][fout] = X_aug[rows][fin+1]^T . dZ[rows][fout], split over rows (the slab count: d.splits)
+static GemmArgs bwd_weight_args(const iwae_handle* h, const Mat& X, const Mat& dZ, int rows, DenseL& d,
+                                const float* kscale) {
   GemmArgs a{};
   a.x3 = h->x3;
   a.A = X.p; a.lda = X.ld;
   a.B = dZ.p; a.ldb = dZ.ld;
   a.C = h->slabs + d.slab_off; a.ldc = d.ldw;
   a.M = d.fin + 1; a.N = d.fout; a.K = rows;
-  long long S = std::min<long long>(d.max_splits, std::max(1LL, cdiv(rows, 64)));
-  int kchunk = (int)(cdiv(cdiv(rows, S), 64) * 64);
-  S = cdiv(rows, kchunk);
-  d.splits = (int)S;
-  a.kchunk = kchunk;
-  a.c_split_stride = d.size();
-  a.kscale = kscale;
+  const long long S = std::min<long long>(d.max_splits, std::max(1LL, cdiv(rows, 64)));
+  a.kchunk = (int)(cdiv(cdiv(rows, S), 64) * 64);
+  d.splits = (int)cdiv(rows, a.kchunk);
+  a.c_split_stride = d.size(); a.kscale = kscale;
+  return a;
+}
+static int gemm_bwd_weight(iwae_handle* h, const Mat& X, const Mat& dZ, int rows, DenseL& d, const float* kscale) {
+  const GemmArgs a = bwd_weight_args(h, X, dZ, rows, d, kscale);
   CHK(prof_begin(h, GEMM_BWD_WEIGHT, EPI_STORE, 2.0 * rows * d.fout * (d.fin + 1)));
-  HIPCHK(launch_gemm(h->stream, GEMM_BWD_WEIGHT, EPI_STORE, 0, (int)S, kscale != nullptr, a));
+  HIPCHK(launch_gemm(h->stream, GEMM_BWD_WEIGHT, EPI_STORE, 0, d.splits, kscale != nullptr, a));
   CHK(prof_end(h, GEMM_BWD_WEIGHT, EPI_STORE));
   return IWAE_OK;
 }
@@ -1050,12 +1051,55 @@ static int ensure_fx(iwae_handle* h) {
   return IWAE_OK;
 }
 
+// Profiling replays (iwae_profile_replay) repeat a step's update on scratch
+// copies, so the model is untouched: *base = prof.adam holds the parameters, m
+// and v (n floats each, copied here on the step's stream) and extra_bytes behind
+// them (the fragment-major copies: room only, the replayed launch rewrites them).
+static int prof_state_copy(iwae_handle* h, size_t extra_bytes, float** base) {
+  const size_t pb = (size_t)h->nparam_int * sizeof(float);
+  if (h->prof.adam_bytes < 3 * pb + extra_bytes) {
+    if (h->prof.adam) HIPCHK(hipFree(h->prof.adam));
+    h->prof.adam = nullptr;
+    HIPCHK(hipMalloc(&h->prof.adam, 3 * pb + extra_bytes));
+    h->prof.adam_bytes = 3 * pb + extra_bytes;
+  }
+  HIPCHK(hipMemcpyAsync(h->prof.adam, h->params, pb, hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->prof.adam + h->nparam_int, h->adam_m, pb, hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->prof.adam + 2 * h->nparam_int, h->adam_v, pb, hipMemcpyDeviceToDevice, h->stream));
+  *base = h->prof.adam;
+  return IWAE_OK;
+}
+// (a replayed update launch's state: with the fragment-major copies)
+static int prof_state_copy(iwae_handle* h, UpdArgs& r) {
+  float* s = nullptr;
+  CHK(prof_state_copy(h, (size_t)h->fx_elems * 2 * sizeof(__bf16), &s));
+  r.param = s; r.m = s + h->nparam_int; r.v = s + 2 * h->nparam_int;
+  r.fx_hi = reinterpret_cast<__bf16*>(s + 3 * h->nparam_int); r.fx_lo = r.fx_hi + h->fx_elems;
+  return IWAE_OK;
+}
 
-static int run_adam(iwae_handle* h, bool read_slabs, bool write_grad, bool do_adam, float scale_override,
-                    bool tick, const float* scale_dev = nullptr, float* tail = nullptr) {
+struct AdamMode {   // what one adam_kernel launch does
+  bool read_slabs = false;           // sum the weight-gradient slabs (DenseL::splits of them) into the gradient buffer first
+  bool do_adam = false;              // then step Adam (else the gradient buffer is all it writes)
+  float scale = 1.f;                 // gradient scale (0: AdamState's) ...
+  const float* scale_dev = nullptr;  // ... or 1 / *scale_dev (data parallel: the all-reduced batch total)
+  float* tail = nullptr;             // data parallel: *tail = scale (this rank's batch size)
+  bool tick = false;                 // advance the Adam step count first (inside a train step the bound launch has)
+  // the end of a step: the slabs summed into the gradient buffer, then (adam) the update
+  static AdamMode from_slabs(bool adam) { return {true, adam}; }
+  // data parallel: the slabs summed into b_local * g, b_local into the buffer's tail
+  static AdamMode weighted_slab_sum(float b_local, float* tail) { return {true, false, b_local, nullptr, tail}; }
+  // the update from the gradient buffer times scale, or times 1 / *total (data parallel: the summed buffer's tail)
+  static AdamMode from_grad(float scale) { return {false, true, scale}; }
+  static AdamMode from_grad_over(const float* total) { return {false, true, 0.f, total}; }
+  // a call of its own (iwae_apply_adam): no bound launch has advanced the step count
+  AdamMode own_tick() const { return {read_slabs, do_adam, scale, scale_dev, tail, true}; }
+};
+
+static int run_adam(iwae_handle* h, const AdamMode& mode) {
+  const bool read_slabs = mode.read_slabs, do_adam = mode.do_adam;
   AdamArgs a{};
-  a.scale_dev = scale_dev;
-  a.tail = tail; a.tail_val = scale_override;
+  a.scale_dev = mode.scale_dev; a.tail = mode.tail; a.tail_val = mode.scale;
   a.param = h->params; a.m = h->adam_m; a.v = h->adam_v; a.grad = h->grad; a.slabs = h->slabs;
   // the engine reads the split copies: its steps rewrite them with every update,
   // other paths refresh them lazily (ensure_wsplit)
@@ -1073,31 +1117,22 @@ static int run_adam(iwae_handle* h, bool read_slabs, bool write_grad, bool do_ad
     mx = std::max(mx, d.size());
   }
   a.nseg = (int)h->dense.size();
-  a.write_grad = write_grad; a.do_adam = do_adam; a.read_slabs = read_slabs;
+  a.write_grad = true; a.do_adam = do_adam; a.read_slabs = read_slabs;
   a.state = &h->ds->adam; a.ticket = &h->ds->tickets[2];
-  a.grad_scale_override = scale_override;
-  a.tick = tick;
+  a.grad_scale_override = mode.scale; a.tick = mode.tick;
   HIPCHK(launch_adam(h->stream, a, mx));
   if (h->prof.kind == 12 && do_adam && !h->prof.have) {
     AdamArgs r = a;
     r.tick = false;                  // replays repeat this step's update (same t)
     // ... on scratch copies of the parameters and moments: the model is untouched
-    const size_t pb = (size_t)h->nparam_int * sizeof(float);
-    if (h->prof.adam_bytes < 3 * pb) {
-      if (h->prof.adam) HIPCHK(hipFree(h->prof.adam));
-      h->prof.adam = nullptr;
-      HIPCHK(hipMalloc(&h->prof.adam, 3 * pb));
-      h->prof.adam_bytes = 3 * pb;
-    }
-    HIPCHK(hipMemcpyAsync(h->prof.adam, h->params, pb, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->prof.adam + h->nparam_int, h->adam_m, pb, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->prof.adam + 2 * h->nparam_int, h->adam_v, pb, hipMemcpyDeviceToDevice, h->stream));
-    r.param = h->prof.adam; r.m = h->prof.adam + h->nparam_int; r.v = h->prof.adam + 2 * h->nparam_int;
+    float* s = nullptr;
+    CHK(prof_state_copy(h, 0, &s));
+    r.param = s; r.m = s + h->nparam_int; r.v = s + 2 * h->nparam_int;
     // (the gradient buffer is rewritten with the same values)
     h->prof.mem = [r, mx](hipStream_t st) { return launch_adam(st, r, mx); };
     double bytes = 0.0;
-    for (int i = 0; i < a.nseg; ++i)      // p, m, v in; p, m, v (+ g) out; the slabs in
-      bytes += (double)a.seg[i].n * 4.0 * (6 + (write_grad ? 1 : 0) + (read_slabs ? a.seg[i].splits : 1));
+    for (int i = 0; i < a.nseg; ++i)      // p, m, v in; p, m, v, g out; the slabs in
+      bytes += (double)a.seg[i].n * 4.0 * (7 + (read_slabs ? a.seg[i].splits : 1));
     h->prof.flop1 = bytes;
     h->prof.have = true;
   }
@@ -1577,63 +1612,51 @@ static int fused_encoder_bwd(iwae_handle* h, const Plan& P, const float* dlw, in
   return IWAE_OK;
 }
 
-// the row scale of layer di's dZ in the weight gradients: ks as given, or under
-// piwae_unit the layer's weighting
-static const float* dz_scale(const iwae_handle* h, int di, const float* ks) {
-  if (!h->step.piwae_ks) return ks;
-  if (di == h->o1 || di == h->o2 || di == h->o3) return h->dpx;
-  for (int i = 0; i < h->L - 1; ++i)
-    if (di == h->dec[i].l1 || di == h->dec[i].l2 || di == h->dec[i].head) return h->dlw;
-  for (int i = 1; i < h->L; ++i)
-    if (di == h->enc[i].l1 || di == h->enc[i].l2 || di == h->enc[i].head) return h->dlw2;
-  return ks;                          // the first encoder layer: its image-row dZ are weighted already
+// One weight-gradient job of a train step: dW_aug of Dense layer di = A_aug^T (ks . dZ) over rows.
+enum WGroup { WG_ENC0, WG_ENC, WG_DEC, WG_OUT };   // first encoder layer (image rows), encoder, decoder, output MLP
+// sets of groups: the two passes of PIWAE's fused step; the data-parallel step's two all-reduce buckets
+enum WGroups : unsigned {
+  WG_ALL = 15, WG_ENCODER = 1u << WG_ENC0 | 1u << WG_ENC, WG_DECODER = 1u << WG_DEC | 1u << WG_OUT,
+  WG_OUT_ONLY = 1u << WG_OUT, WG_BUT_OUT = WG_ALL & ~WG_OUT_ONLY,
+};
+struct WJob { int di; const Mat* A; const Mat* dZ; int rows; const float* ks; WGroup grp; };   // ks: dZ's row scale, or null
+
+// The step's weight-gradient jobs in their natural order: the encoder layers
+// ascending, the decoder layers ascending, the output MLP, each layer as l1,
+// l2, head (three jobs).  Row scales: the output layer's dZ is g, scaled by
+// dpx; under piwae_unit every layer's dZ takes its own weighting (see
+// engine_train_body), but the first encoder layer's image-row dZ, weighted
+// already.  The three consumers (weight_grads, run_update's slab pass, run_dw)
+// each choose a layer's slab count and leave it in DenseL::splits, which the launch
+// that sums the slabs reads: run_adam (read_slabs) or run_update's apply from the slabs.
+static std::vector<WJob> layer_jobs(const iwae_handle* h, const Plan& P, WGroups groups = WG_ALL) {
+  const int L = h->L, M = P.Bimg * P.kS;
+  const float* const unit_ks[] = {nullptr, h->dlw2, h->dlw, h->dpx};      // piwae_unit's weighting by WGroup
+  std::vector<WJob> js;
+  auto layer = [&](const StochL& S, const Mat* in, const LayerBufs& b, int rows, WGroup grp) {
+    if (!(groups >> grp & 1u)) return;
+    const float* ks = h->step.piwae_ks ? unit_ks[grp] : nullptr;
+    js.push_back({S.l1, in, &b.dY1, rows, ks, grp});
+    js.push_back({S.l2, &b.y1, &b.dY2, rows, ks, grp});
+    js.push_back({S.head, &b.y2, grp == WG_OUT ? &b.P : &b.dP, rows, grp == WG_OUT ? h->dpx : ks, grp});
+  };
+  layer(h->enc[0], &h->x_in, h->eb[0], P.Bimg, WG_ENC0);
+  for (int i = 1; i < L; ++i) layer(h->enc[i], &h->h[i - 1], h->eb[i], M, WG_ENC);
+  for (int i = 0; i < L - 1; ++i) layer(h->dec[i], &h->h[L - 1 - i], h->db[i], M, WG_DEC);
+  layer({0, 0, 0, h->o1, h->o2, h->o3}, &h->h[0], h->ob, M, WG_OUT);      // the output MLP as one layer (head dZ: ob.P)
+  return js;
 }
 
-// all weight gradients (X_aug^T dZ, split over rows) in grouped launches
-static int weight_grads(iwae_handle* h, const Plan& P, bool enc, bool dec, const float* dpx) {
-  const int L = h->L, M = P.Bimg * P.kS;
-  struct WJ { int di; const Mat* A; const Mat* dZ; int rows; const float* ks; };
-  std::vector<WJ> js;
-  if (enc) {
-    for (int i = 0; i < L; ++i) {
-      const StochL& S = h->enc[i];
-      const int rows = i == 0 ? P.Bimg : M;
-      js.push_back({S.l1, i == 0 ? &h->x_in : &h->h[i - 1], &h->eb[i].dY1, rows, nullptr});
-      js.push_back({S.l2, &h->eb[i].y1, &h->eb[i].dY2, rows, nullptr});
-      js.push_back({S.head, &h->eb[i].y2, &h->eb[i].dP, rows, nullptr});
-    }
-  }
-  if (dec) {
-    for (int i = 0; i < L - 1; ++i) {
-      const StochL& S = h->dec[i];
-      js.push_back({S.l1, &h->h[L - 1 - i], &h->db[i].dY1, M, nullptr});
-      js.push_back({S.l2, &h->db[i].y1, &h->db[i].dY2, M, nullptr});
-      js.push_back({S.head, &h->db[i].y2, &h->db[i].dP, M, nullptr});
-    }
-    js.push_back({h->o1, &h->h[0], &h->ob.dY1, M, nullptr});
-    js.push_back({h->o2, &h->ob.y1, &h->ob.dY2, M, nullptr});
-    js.push_back({h->o3, &h->ob.y2, &h->ob.P, M, dpx});
-  }
+// weight gradients (X_aug^T dZ, split over rows) of the groups' layers in grouped launches
+static int weight_grads(iwae_handle* h, const Plan& P, WGroups groups) {
+  const std::vector<WJob> js = layer_jobs(h, P, groups);
   for (size_t b = 0; b < js.size(); b += kMaxGroup) {
     GemmGroup gg{};
     for (size_t q = b; q < std::min(js.size(), b + kMaxGroup); ++q) {
-      const WJ& w = js[q];
+      const WJob& w = js[q];
       DenseL& d = h->dense[w.di];
-      GemmArgs& a = gg.g[gg.n];
-      a.x3 = h->x3;
-      a.A = w.A->p; a.lda = w.A->ld;
-      a.B = w.dZ->p; a.ldb = w.dZ->ld;
-      a.C = h->slabs + d.slab_off; a.ldc = d.ldw;
-      a.M = d.fin + 1; a.N = d.fout; a.K = w.rows;
-      long long S = std::min<long long>(d.max_splits, std::max(1LL, cdiv(w.rows, 64)));
-      const int kchunk = (int)(cdiv(cdiv(w.rows, S), 64) * 64);
-      S = cdiv(w.rows, kchunk);
-      d.splits = (int)S;
-      a.kchunk = kchunk;
-      a.c_split_stride = d.size();
-      a.kscale = dz_scale(h, w.di, w.ks);      // PIWAE's unit chain: the layer's own weighting
-      gg.splits[gg.n] = (int)S;
-      gg.n++;
+      gg.g[gg.n] = bwd_weight_args(h, *w.A, *w.dZ, w.rows, d, w.ks);
+      gg.splits[gg.n++] = d.splits;
     }
     HIPCHK(launch_gemm_group_bwd_weight(h->stream, gg));
   }
@@ -1652,15 +1675,9 @@ static bool upd_tiles_ok(const iwae_handle* h) {
   return tiles <= kUpdMaxTiles && (int)h->dense.size() <= kUpdMaxJobs;
 }
 static bool use_update(const iwae_handle* h, const Plan& P) {
-  if (!h->tune.upd || !h->x3 || (long long)P.Bimg * P.kS > h->tune.upd_rows) return false;
-  long long tiles = 0;
-  for (const DenseL& d : h->dense) tiles += cdiv(d.fin + 1, 64) * cdiv(d.fout, 64);
-  return tiles <= kUpdMaxTiles && (int)h->dense.size() <= kUpdMaxJobs;
+  return h->tune.upd && h->x3 && (long long)P.Bimg * P.kS <= h->tune.upd_rows && upd_tiles_ok(h);
 }
 
-// part: 0 every layer, 1 all but the first encoder layer (sample rows), 2 the
-// first encoder layer (image rows; its backward may still be running when
-// part 1 starts on another stream)
 // slabs: larger batches (beyond upd_rows), the gradient pass only, split over
 // rows into the split-K slabs the Adam launch sums (the weight-gradient GEMMs'
 // role); about two workgroups per CU of sample-row tiles
@@ -1669,63 +1686,45 @@ static bool use_update_slabs(const iwae_handle* h, const Plan& P) {
          (int)h->dense.size() <= kUpdMaxJobs;
 }
 
-// bucket: 0 every layer, 1 the output MLP only, 2 every layer but the output
-// MLP (the data-parallel step's two all-reduce buckets: the output MLP is the
-// last range of the parameter buffer).  apply: data parallel after the
-// all-reduce -- no reduction, Adam + FX / GX from the summed gradient in the
-// buffer times 1 / *scale_dev.
-static int run_update(iwae_handle* h, const Plan& P, bool adam, int bucket = 0, hipStream_t st = nullptr,
-                      float gscale = 1.f, float* tail = nullptr, bool slabs = false, bool apply = false,
-                      const float* scale_dev = nullptr, bool from_slabs = false) {
-  if (!st) st = h->stream;
-  const int L = h->L, M = P.Bimg * P.kS;
-  constexpr long long UP_ROWS_ITER = kUpdRowsPerIter;   // rows per reduction iteration of the update kernel
-  struct WJ { int di; const Mat* A; const Mat* dZ; int rows; const float* ks; };
-  std::vector<WJ> js;
-  for (int i = 0; i < L; ++i) {
-    const StochL& S = h->enc[i];
-    const int rows = i == 0 ? P.Bimg : M;
-    js.push_back({S.l1, i == 0 ? &h->x_in : &h->h[i - 1], &h->eb[i].dY1, rows, nullptr});
-    js.push_back({S.l2, &h->eb[i].y1, &h->eb[i].dY2, rows, nullptr});
-    js.push_back({S.head, &h->eb[i].y2, &h->eb[i].dP, rows, nullptr});
-  }
-  for (int i = 0; i < L - 1; ++i) {
-    const StochL& S = h->dec[i];
-    js.push_back({S.l1, &h->h[L - 1 - i], &h->db[i].dY1, M, nullptr});
-    js.push_back({S.l2, &h->db[i].y1, &h->db[i].dY2, M, nullptr});
-    js.push_back({S.head, &h->db[i].y2, &h->db[i].dP, M, nullptr});
-  }
-  js.push_back({h->o1, &h->h[0], &h->ob.dY1, M, nullptr});
-  js.push_back({h->o2, &h->ob.y1, &h->ob.dY2, M, nullptr});
-  js.push_back({h->o3, &h->ob.y2, &h->ob.P, M, h->dpx});
-  if (bucket != 0) {
-    std::vector<WJ> keep;
-    for (const WJ& w : js) {
-      const bool out = w.di == h->o1 || w.di == h->o2 || w.di == h->o3;
-      if (out == (bucket == 1)) keep.push_back(w);
-    }
-    js.swap(keep);
-  }
+struct UpdMode {   // what one launch of the update kernel does
+  enum Kind { FUSED, DP_GRADS, SLAB_PASS, APPLY_GRAD, APPLY_SLABS } kind = FUSED;
+  bool adam = false;                 // FUSED: step Adam and rewrite the FX / GX copies (else the gradients only)
+  WGroups bucket = WG_ALL; hipStream_t st = nullptr;   // DP_GRADS: the layers of the pass, its stream (null: the step's)
+  const float* total = nullptr;      // APPLY_GRAD: the all-reduced batch total
+  // every weight gradient, the gradient buffer, (adam) Adam and the FX / GX copies
+  static UpdMode fused(bool adam) { return {FUSED, adam}; }
+  // data parallel before the all-reduce: B_local * g only, B_local into the tail with the bucket that holds it
+  static UpdMode dp_grads(WGroups bucket, hipStream_t st) { return {DP_GRADS, false, bucket, st}; }
+  static UpdMode slab_pass() { return {SLAB_PASS}; }      // (use_update_slabs) the gradient pass only, into the split-K slabs
+  // data parallel after the all-reduce: no reduction, Adam + FX / GX from the summed buffer times 1 / *total
+  static UpdMode apply_grad(const float* total) { return {APPLY_GRAD, false, WG_ALL, nullptr, total}; }
+  // the slabs of a gradient pass summed (DenseL::splits of them), then Adam + FX / GX
+  static UpdMode apply_slabs() { return {APPLY_SLABS}; }
+};
+
+static int run_update(iwae_handle* h, const Plan& P, const UpdMode& mode) {
+  const hipStream_t st = mode.st ? mode.st : h->stream;
+  const int M = P.Bimg * P.kS;
+  const bool slabs = mode.kind == UpdMode::SLAB_PASS, from_slabs = mode.kind == UpdMode::APPLY_SLABS;
+  const bool apply = mode.kind == UpdMode::APPLY_GRAD || from_slabs;
+  std::vector<WJob> js = layer_jobs(h, P, mode.bucket);
   if ((int)js.size() > kUpdMaxJobs) return fail(h, IWAE_EINVAL, "fused update: too many layers");
   // the long reductions first (dispatched first)
-  std::stable_sort(js.begin(), js.end(), [](const WJ& x, const WJ& y) { return x.rows > y.rows; });
+  std::stable_sort(js.begin(), js.end(), [](const WJob& x, const WJob& y) { return x.rows > y.rows; });
   UpdArgs a{};
-  int tiles = 0;
+  int tiles = 0, nsplit = 1;
   double flop = 0.0;
-  int nsplit = 1;
   if (slabs) {
     long long st_tiles = 0;                      // sample-row tiles: nsplit of them per CU pair
-    for (const WJ& w : js)
+    for (const WJob& w : js)
       if (w.rows == M) st_tiles += cdiv(h->dense[w.di].fin + 1, 64) * cdiv(h->dense[w.di].fout, 64);
     const long long target = h->tune.upd_slab_wg;     // sample-row workgroups of the pass
     nsplit = (int)std::max(1LL, (target + st_tiles / 2) / std::max(1LL, st_tiles));
-    a.search = 1;
   }
-  for (const WJ& w : js) {
+  for (const WJob& w : js) {
     DenseL& d = h->dense[w.di];
     UpdJob& J = a.job[a.njobs++];
-    const float* ks = dz_scale(h, w.di, w.ks);
-    J.A = w.A->p; J.lda = w.A->ld; J.B = w.dZ->p; J.ldb = w.dZ->ld; J.ks = ks ? ks : h->ones; J.rows = w.rows;
+    J.A = w.A->p; J.lda = w.A->ld; J.B = w.dZ->p; J.ldb = w.dZ->ld; J.ks = w.ks ? w.ks : h->ones; J.rows = w.rows;
     J.off = d.off; J.fin = d.fin; J.fout = d.fout; J.ldw = d.ldw;
     const bool fx = w.di != h->enc[0].l1;       // the input layer has no fragment-major copies
     J.fx_off = fx ? d.fx_off : -1; J.fx_steps = d.fx_steps; J.head_d = d.head_d;
@@ -1735,16 +1734,16 @@ static int run_update(iwae_handle* h, const Plan& P, bool adam, int bucket = 0, 
     J.tile0 = tiles;
     J.nsplit = 1;
     if (slabs) {
-      // row chunks of whole 128-row iterations, at most the layer's slab count
+      // row chunks of whole reduction iterations (128 rows), at most the layer's slab count
       long long S = std::min<long long>(w.rows == M ? nsplit : 1, d.max_splits);
-      const long long chunk = cdiv(cdiv(w.rows, S), UP_ROWS_ITER) * UP_ROWS_ITER;
+      const long long chunk = cdiv(cdiv(w.rows, S), kUpdRowsPerIter) * kUpdRowsPerIter;
       S = cdiv(w.rows, chunk);
       J.nsplit = (int)S; J.chunk = (int)chunk; J.slab_stride = d.size();
       J.off = d.slab_off; J.fx_off = -1; J.tn = 64;
       J.tiles_n = (int)cdiv(d.fout, 64);
       d.splits = (int)S;
     }
-    if (apply && from_slabs) {
+    if (from_slabs) {
       // apply from the gradient pass's slabs: B, chunk, slab_stride name them
       J.B = h->slabs + d.slab_off; J.chunk = d.splits; J.slab_stride = d.size();
     }
@@ -1762,11 +1761,20 @@ static int run_update(iwae_handle* h, const Plan& P, bool adam, int bucket = 0, 
   a.nheavy = heavy;
   a.per_xcd = (int)cdiv(heavy, 8);
   a.per_xcd2 = (int)cdiv(tiles - heavy, 8);
-  a.param = h->params; a.m = h->adam_m; a.v = h->adam_v; a.grad = slabs ? h->slabs : h->grad;
+  a.param = h->params; a.m = h->adam_m; a.v = h->adam_v; a.grad = h->grad;
   a.fx_hi = h->fx_hi; a.fx_lo = h->fx_lo;
-  a.state = &h->ds->adam; a.do_adam = (adam || apply) && !slabs ? 1 : 0;
-  a.gscale = slabs ? 1.f : gscale; a.tail = (slabs || apply) ? nullptr : tail; a.tail_val = gscale;
-  a.apply = apply ? (from_slabs ? 2 : 1) : 0; a.scale_dev = scale_dev;
+  a.state = &h->ds->adam;
+  a.gscale = a.tail_val = 1.f;
+  switch (mode.kind) {
+    case UpdMode::FUSED: a.do_adam = mode.adam ? 1 : 0; break;
+    case UpdMode::DP_GRADS:
+      a.gscale = a.tail_val = (float)P.B;
+      a.tail = (mode.bucket & WG_OUT_ONLY) ? h->grad + h->nparam_int : nullptr;
+      break;
+    case UpdMode::SLAB_PASS: a.search = 1; a.grad = h->slabs; break;
+    case UpdMode::APPLY_GRAD: a.do_adam = 1; a.apply = 1; a.scale_dev = mode.total; break;
+    case UpdMode::APPLY_SLABS: a.do_adam = 1; a.apply = 2; break;
+  }
   a.waves = h->tune.upd_waves;
   h->count.upd++;
   if (h->step.defer_launch && st == h->stream && !slabs && !apply) {
@@ -1775,8 +1783,7 @@ static int run_update(iwae_handle* h, const Plan& P, bool adam, int bucket = 0, 
     h->pend.upd = a; h->pend.upd_have = true;
     h->pend.upd_mask = 0; h->pend.upd_cons = 0;
     for (int j = 0; j < a.njobs; ++j) {
-      const int di = js[j].di;
-      if (di == h->enc[0].l1 || di == h->enc[0].l2 || di == h->enc[0].head) {
+      if (js[j].grp == WG_ENC0) {
         h->pend.upd_mask |= 1u << j;
         h->pend.upd_cons += a.job[j].tiles_m * a.job[j].tiles_n;
       }
@@ -1785,23 +1792,11 @@ static int run_update(iwae_handle* h, const Plan& P, bool adam, int bucket = 0, 
     HIPCHK(launch_update(st, a));
   }
   if (a.do_adam) h->params_version++;
-  if (h->prof.kind == 15 && adam && !h->prof.have) {
+  if (h->prof.kind == 15 && a.do_adam && !h->prof.have) {
     // replays repeat this step's update on scratch copies of the parameters,
     // moments and fragment-major copies: the model is untouched
-    const size_t pb = (size_t)h->nparam_int * sizeof(float), fb = (size_t)h->fx_elems * 2 * sizeof(__bf16);
-    if (h->prof.adam_bytes < 3 * pb + fb) {
-      if (h->prof.adam) HIPCHK(hipFree(h->prof.adam));
-      h->prof.adam = nullptr;
-      HIPCHK(hipMalloc(&h->prof.adam, 3 * pb + fb));
-      h->prof.adam_bytes = 3 * pb + fb;
-    }
-    HIPCHK(hipMemcpyAsync(h->prof.adam, h->params, pb, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->prof.adam + h->nparam_int, h->adam_m, pb, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->prof.adam + 2 * h->nparam_int, h->adam_v, pb, hipMemcpyDeviceToDevice, h->stream));
     UpdArgs r = a;
-    r.param = h->prof.adam; r.m = h->prof.adam + h->nparam_int; r.v = h->prof.adam + 2 * h->nparam_int;
-    r.fx_hi = reinterpret_cast<__bf16*>(h->prof.adam + 3 * h->nparam_int);
-    r.fx_lo = r.fx_hi + h->fx_elems;
+    CHK(prof_state_copy(h, r));
     h->prof.mem = [r](hipStream_t st) { return launch_update(st, r); };
     h->prof.flop1 = flop;
     h->prof.have = true;
@@ -1817,25 +1812,15 @@ static int run_update(iwae_handle* h, const Plan& P, bool adam, int bucket = 0, 
 // layer; work items are ordered chunk-major so one row chunk's blocks share an
 // XCD (and its L2).
 static int run_dw(iwae_handle* h, const Plan& P) {
-  const int L = h->L, M = P.Bimg * P.kS;
-  struct WJ { int di; const Mat* A; const Mat* dZ; int rows; const float* ks; };
-  std::vector<WJ> js;
-  js.push_back({h->o3, &h->ob.y2, &h->ob.P, M, h->dpx});
-  js.push_back({h->o2, &h->ob.y1, &h->ob.dY2, M, nullptr});
-  js.push_back({h->o1, &h->h[0], &h->ob.dY1, M, nullptr});
-  for (int i = 0; i < L - 1; ++i) {
-    const StochL& S = h->dec[i];
-    js.push_back({S.head, &h->db[i].y2, &h->db[i].dP, M, nullptr});
-    js.push_back({S.l2, &h->db[i].y1, &h->db[i].dY2, M, nullptr});
-    js.push_back({S.l1, &h->h[L - 1 - i], &h->db[i].dY1, M, nullptr});
-  }
-  for (int i = L - 1; i >= 0; --i) {
-    const StochL& S = h->enc[i];
-    const int rows = i == 0 ? P.Bimg : M;
-    js.push_back({S.head, &h->eb[i].y2, &h->eb[i].dP, rows, nullptr});
-    js.push_back({S.l2, &h->eb[i].y1, &h->eb[i].dY2, rows, nullptr});
-    js.push_back({S.l1, i == 0 ? &h->x_in : &h->h[i - 1], &h->eb[i].dY1, rows, nullptr});
-  }
+  const int L = h->L;
+  // the output MLP first, then the decoder layers ascending, then the encoder
+  // layers descending, each layer as head, l2, l1
+  const std::vector<WJob> nat = layer_jobs(h, P);
+  std::vector<WJob> js;
+  auto layer = [&](int t) { for (int q = 2; q >= 0; --q) js.push_back(nat[3 * t + q]); };
+  layer(2 * L - 1);
+  for (int i = 0; i < L - 1; ++i) layer(L + i);
+  for (int i = L - 1; i >= 0; --i) layer(i);
   if ((int)js.size() > kDwMaxJobs) return fail(h, IWAE_EINVAL, "weight-gradient pass: too many layers");
   DwArgs a;
   std::memset(&a, 0, sizeof(a));
@@ -1858,35 +1843,28 @@ static int run_dw(iwae_handle* h, const Plan& P) {
   // block-k-steps of tiles per workgroup; the grid must not exceed one workgroup
   // per CU (8 XCDs x 32): a second round would double the pass
   double target = W / (double)h->tune.dw_wg;
+  auto chunk_of = [&](size_t q) {          // job q's row chunk at this target: whole 32-row k steps
+    long long S = std::llround((double)cdiv(js[q].rows, 32) * cost[q] / std::max(target, 1.0));
+    S = std::max(1LL, std::min<long long>(S, h->dense[js[q].di].cap_splits));
+    return cdiv(cdiv(js[q].rows, S), 32) * 32;
+  };
   for (int tries = 0; tries < 64; ++tries) {
     long long n = 0;
-    for (size_t q = 0; q < js.size(); ++q) {
-      const long long S = std::max(1LL, std::min<long long>(std::llround((double)cdiv(js[q].rows, 32) * cost[q] /
-                                                                         std::max(target, 1.0)),
-                                                            h->dense[js[q].di].cap_splits));
-      const long long chunk = cdiv(cdiv(js[q].rows, S), 32) * 32;
-      n += (long long)a.job[q].nib * a.job[q].njb * cdiv(js[q].rows, chunk);
-    }
+    for (size_t q = 0; q < js.size(); ++q) n += (long long)a.job[q].nib * a.job[q].njb * cdiv(js[q].rows, chunk_of(q));
     if (n <= h->tune.dw_wg) break;
     target *= 1.02;
   }
   int items = 0;
   for (size_t q = 0; q < js.size(); ++q) {
-    const WJ& w = js[q];
+    const WJob& w = js[q];
     DenseL& d = h->dense[w.di];
     DwJob& J = a.job[q];
-    const float* ks = dz_scale(h, w.di, w.ks);
-    J.A = w.A->p; J.lda = w.A->ld; J.B = w.dZ->p; J.ldb = w.dZ->ld; J.ks = ks ? ks : h->ones;
-    J.scaled = ks ? 1 : 0;                     // (unscaled dZ: no row-scale loads)
+    J.A = w.A->p; J.lda = w.A->ld; J.B = w.dZ->p; J.ldb = w.dZ->ld; J.ks = w.ks ? w.ks : h->ones;
+    J.scaled = w.ks ? 1 : 0;                   // (unscaled dZ: no row-scale loads)
     J.rows = w.rows;
     J.out = h->slabs + d.slab_off; J.ldo = d.ldw; J.slab_stride = d.size();
-    const double ksteps = (double)cdiv(w.rows, 32);
-    long long S = std::llround(ksteps * cost[q] / std::max(target, 1.0));
-    S = std::max(1LL, std::min<long long>(S, d.cap_splits));
-    const long long chunk = cdiv(cdiv(w.rows, S), 32) * 32;
-    S = cdiv(w.rows, chunk);
-    J.nsplit = (int)S; J.chunk = (int)chunk;
-    d.splits = (int)S;
+    const long long chunk = chunk_of(q);
+    J.nsplit = d.splits = (int)cdiv(w.rows, chunk); J.chunk = (int)chunk;
     J.item0 = items;
     items += J.nib * J.njb * J.nsplit;
   }
@@ -2016,25 +1994,33 @@ static bool use_fold0(const iwae_handle* h, const Plan& P) {
   return h->tune.engine_fold0 && smallm_ok(h, P.Bimg) && h->L >= 1;
 }
 
-static std::vector<long long> tc_key(const Plan& P, int which) {
+// The engine's launches.  The value is part of the plan key (tc_key).
+enum TcLaunch : int {
+  TCL_FWD = 0, TCL_BWD = 1,          // sample-row forward (jobs E, O) / backward (jobs O', E')
+  TCL_IMG_FWD = 2, TCL_IMG_BWD = 3,  // first encoder layer's image-row forward (job I) / backward (job I')
+  TCL_BWD_ENC = 4,                   // PIWAE's encoder pass: the backward chain on the MIWAE weighting
+  TCL_BWD_NO_OUT = 5,                // the backward without job O' (nrb_kernel runs it)
+};
+
+static std::vector<long long> tc_key(const Plan& P, TcLaunch which) {
   return {which, P.Bimg, P.Bsplit, P.kS};
 }
 
 // wide workgroups (32 / 64 sample rows, two-set weight pipeline) for large batches
-static bool tc_wide(const iwae_handle* h, const Plan& P, int which) {
-  return (which <= 1 || which >= 4) && (long long)P.Bimg * P.kS >= h->tune.wide_rows;
+static bool tc_wide(const iwae_handle* h, const Plan& P, TcLaunch which) {
+  return which != TCL_IMG_FWD && which != TCL_IMG_BWD && (long long)P.Bimg * P.kS >= h->tune.wide_rows;
 }
 
 // The jobs of launch `which` (see tc_prepare_one): op tables and the buffer
 // widths the LDS layout needs.  Reads the handle only.
-static std::vector<TcBuild> tc_build_jobs(iwae_handle* h, const Plan& P, int which) {
+static std::vector<TcBuild> tc_build_jobs(iwae_handle* h, const Plan& P, TcLaunch which) {
   const int L = h->L, kS = P.kS;
   const bool wide = tc_wide(h, P, which);
   std::vector<TcBuild> jobs;
-  const bool fold0 = which == 0 && use_fold0(h, P);
+  const bool fold0 = which == TCL_FWD && use_fold0(h, P);
   auto ldF = [&](int di) { return h->dense[di].ldF; };
   auto ldG = [&](int di) { return h->dense[di].ldG; };
-  if (which == 0) {
+  if (which == TCL_FWD) {
     // job E: h1 (kept, buffer 0 .. L-2 hold h_0 .. h_{L-2}), P = L-1 (also h_{L-1}), Q = L
     if (L >= 2) {
       TcBuild B;
@@ -2111,7 +2097,7 @@ static std::vector<TcBuild> tc_build_jobs(iwae_handle* h, const Plan& P, int whi
     }
     // wide launches (large batches): the output job, the longest, dispatched first
     if (wide && jobs.size() == 2) std::swap(jobs[0], jobs[1]);
-  } else if (which == 2) {
+  } else if (which == TCL_IMG_FWD) {
     // job I: y1 = tanh(sum of the input Dense's slabs) -> l2 tanh -> head: P0 = (mu | zs)
     TcBuild B;
     const StochL& S0 = h->enc[0];
@@ -2126,7 +2112,7 @@ static std::vector<TcBuild> tc_build_jobs(iwae_handle* h, const Plan& P, int whi
     TcOp& c = tc_head_op(h, B, TC_HEADP, S0.head, 1, -1, S0.d, 0);
     c.out = h->eb[0].P.p; c.ld_out = h->eb[0].P.ld;
     jobs.push_back(B);
-  } else if (which == 3) {
+  } else if (which == TCL_IMG_BWD) {
     // job I': dP0 summed over each image's samples -> head^T (1 - y2^2) -> l2^T (1 - y1^2)
     TcBuild B;
     const StochL& S0 = h->enc[0];
@@ -2151,14 +2137,14 @@ static std::vector<TcBuild> tc_build_jobs(iwae_handle* h, const Plan& P, int whi
     b.y = h->eb[0].y1.p; b.ld_y = h->eb[0].y1.ld; b.out = h->eb[0].dY1.p; b.ld_out = h->eb[0].dY1.ld;
     jobs.push_back(B);
   } else {
-    // which 1: the backward launch.  which 4 (PIWAE's encoder pass): the same
+    // TCL_BWD: the backward launch.  TCL_BWD_ENC (PIWAE's encoder pass): the same
     // chain run on the MIWAE weighting, storing only what the encoder's
     // backward reads (dL/dh, the encoder layers' dZ): the decoder layers' dZ
-    // of the IWAE pass stay for their weight gradients.  which 5: which 1
+    // of the IWAE pass stay for their weight gradients.  TCL_BWD_NO_OUT: TCL_BWD
     // without job O' (nrb_kernel runs it)
-    const bool dec_out = which != 4;
+    const bool dec_out = which != TCL_BWD_ENC;
     // job O': (dpx g) W3^T (1 - y2^2) -> W2^T (1 - y1^2) -> W1^T = dL/dh1 (output MLP part)
-    if (which != 5) {
+    if (which != TCL_BWD_NO_OUT) {
       TcBuild B;
       TcOp& g = B.add(TC_LOADG);
       g.out_buf = 0; g.N = h->xdim; g.next_k = ldG(h->o3);
@@ -2242,14 +2228,14 @@ constexpr size_t kTcLdsBytes = 160 * 1024;
 // through fold0, on whether the batch takes the few-row launches: decided
 // once per model for each, so use_engine() can decline the engine (the step
 // then runs on the row-block or the layer-wise kernels) instead of failing in
-// tc_prepare_one.  (Launches 4 and 5 run subsets of launch 1's jobs.)
+// tc_prepare_one.  (TCL_BWD_ENC and TCL_BWD_NO_OUT run subsets of TCL_BWD's jobs.)
 static bool tc_fits(const iwae_handle* ch, const Plan& P) {
   iwae_handle* h = const_cast<iwae_handle*>(ch);     // (the builders only read it)
   if ((int)h->eb.size() < h->L) return true;          // no workspace yet: decided at the first step
   int& fit = h->tc_fit[use_fold0(h, P) ? 1 : 0];
   if (fit < 0) {
     fit = 1;
-    for (int which : {0, 1, 2, 3}) {
+    for (TcLaunch which : {TCL_FWD, TCL_BWD, TCL_IMG_FWD, TCL_IMG_BWD}) {
       std::vector<TcBuild> jobs = tc_build_jobs(h, P, which);
       if (tc_lds_bytes(jobs, 1) > kTcLdsBytes) fit = 0;
     }
@@ -2257,10 +2243,9 @@ static bool tc_fits(const iwae_handle* ch, const Plan& P) {
   return fit == 1;
 }
 
-// Plans of this shape, built once and uploaded: which = 0 the sample-row
-// forward launch, 1 the sample-row backward launch, 2 / 3 the first encoder
-// layer's image-row forward (after its input Dense) / backward launch.
-static int tc_prepare_one(iwae_handle* h, const Plan& P, int which) {
+// Plans of this shape, built once and uploaded (the launches: TcLaunch; the
+// image-row forward runs after the first encoder layer's input Dense).
+static int tc_prepare_one(iwae_handle* h, const Plan& P, TcLaunch which) {
   const auto key = tc_key(P, which);
   if (h->tc_plans.count(key)) return IWAE_OK;
   const int kS = P.kS;
@@ -2268,16 +2253,16 @@ static int tc_prepare_one(iwae_handle* h, const Plan& P, int which) {
   std::vector<TcBuild> jobs = tc_build_jobs(h, P, which);
   if ((int)jobs.size() > kTcMaxJobs) return fail(h, IWAE_EINVAL, "engine: too many jobs");
   // rows per workgroup: the largest tile count the LDS allows, fewer for small batches
-  const bool img = which == 2 || which == 3;
+  const bool img = which == TCL_IMG_FWD || which == TCL_IMG_BWD;
   const long long rows = img ? (long long)P.Bimg : (long long)P.Bimg * kS;
   // image rows: one image per workgroup (latency-bound chains of a few rows), up to 256 workgroups
   // (knobs img_rows_fwd / img_rows_bwd: rows per workgroup of job I / I' instead)
   int row_step = img ? (int)std::max<long long>(1, cdiv(P.Bimg, 256)) : 0;
-  if (which == 2 && h->tune.img_rows_fwd > 0) row_step = h->tune.img_rows_fwd;
-  if (which == 3 && h->tune.img_rows_bwd > 0) row_step = h->tune.img_rows_bwd;
+  if (which == TCL_IMG_FWD && h->tune.img_rows_fwd > 0) row_step = h->tune.img_rows_fwd;
+  if (which == TCL_IMG_BWD && h->tune.img_rows_bwd > 0) row_step = h->tune.img_rows_bwd;
   // rows per workgroup: 16 (four-set pipeline) below wide_rows, else the
   // widest the LDS allows (two-set pipeline)
-  const int want = wide ? (which == 0 ? 4 : h->tune.wide_rt) : h->tune.tc_rt;
+  const int want = wide ? (which == TCL_FWD ? 4 : h->tune.wide_rt) : h->tune.tc_rt;
   TcRec rec;
   for (int rt : {4, 2, 1}) {
     if (rt > want) continue;
@@ -2319,16 +2304,16 @@ static int tc_prepare_one(iwae_handle* h, const Plan& P, int which) {
 }
 
 static int tc_prepare(iwae_handle* h, const Plan& P) {
-  CHK(tc_prepare_one(h, P, 2));
-  CHK(tc_prepare_one(h, P, 3));
-  CHK(tc_prepare_one(h, P, 0));
-  if (P.piwae) CHK(tc_prepare_one(h, P, 4));
-  return tc_prepare_one(h, P, 1);
+  CHK(tc_prepare_one(h, P, TCL_IMG_FWD));
+  CHK(tc_prepare_one(h, P, TCL_IMG_BWD));
+  CHK(tc_prepare_one(h, P, TCL_FWD));
+  if (P.piwae) CHK(tc_prepare_one(h, P, TCL_BWD_ENC));
+  return tc_prepare_one(h, P, TCL_BWD);
 }
 
 // dlw / dpx: the bound's weighting the launch reads (default: the bound's
 // first one; PIWAE's encoder pass: the MIWAE one, dlw2 / dpx2)
-static int tc_run(iwae_handle* h, const Plan& P, const EpsSet& E, int which, const BoundArgs* bnd = nullptr,
+static int tc_run(iwae_handle* h, const Plan& P, const EpsSet& E, TcLaunch which, const BoundArgs* bnd = nullptr,
                   const float* dlw = nullptr, const float* dpx = nullptr, bool unit = false) {
   auto it = h->tc_plans.find(tc_key(P, which));
   if (it == h->tc_plans.end()) return fail(h, IWAE_EINVAL, "engine plan missing");
@@ -2343,7 +2328,7 @@ static int tc_run(iwae_handle* h, const Plan& P, const EpsSet& E, int which, con
     tot += rec.nb[j];
   }
   a.block_start[kTcMaxJobs] = tot;
-  a.rows = (which == 2 || which == 3) ? P.Bimg : P.Bimg * P.kS; a.kS = P.kS;
+  a.rows = (which == TCL_IMG_FWD || which == TCL_IMG_BWD) ? P.Bimg : P.Bimg * P.kS; a.kS = P.kS;
   a.row_step = rec.row_step;
   // XCD-aware placement: the XCDs split over the jobs in proportion to their
   // workgroups, so each XCD's L2 fetches one job's weight copies (a launch that
@@ -2386,7 +2371,7 @@ static int tc_run(iwae_handle* h, const Plan& P, const EpsSet& E, int which, con
     a.bnd_lds = rec.acc_off + (2 + 4 * 8) * 16 * rec.rt;
     a.rng_base = nullptr;
   }
-  const bool prof = which <= 1 && h->prof.kind == 10 + which;
+  const bool prof = (which == TCL_FWD || which == TCL_BWD) && h->prof.kind == 10 + which;
   h->count.tc++;
   if (h->step.defer_launch) {
     // recorded for a combined launch (tcu_kernel); launch_pending issues it
@@ -2439,16 +2424,16 @@ static int allreduce_grad(iwae_handle* h, long long offset, long long count, con
 // Data parallel: the slabs summed into B_local * g (B_local in the tail), then
 // (all_reduce: a step that applies Adam) the n + 4 floats summed over the ranks.
 static int dp_reduce_slabs(iwae_handle* h, const Plan& P, bool all_reduce) {
-  CHK(run_adam(h, true, true, false, (float)P.B, false, nullptr, h->grad + h->nparam_int));
+  CHK(run_adam(h, AdamMode::weighted_slab_sum((float)P.B, h->grad + h->nparam_int)));
   if (!all_reduce) return IWAE_OK;
   if (!h->comm) return fail(h, IWAE_EINVAL, "data parallel without a library communicator");
   return allreduce_grad(h, 0, h->nparam_int + 4, "");
 }
 
 static int finish_step(iwae_handle* h, const Plan& P, bool adam) {
-  if (!h->dp_weighted) return run_adam(h, true, true, adam, 1.f, false);
+  if (!h->dp_weighted) return run_adam(h, AdamMode::from_slabs(adam));
   CHK(dp_reduce_slabs(h, P, adam));
-  return adam ? run_adam(h, false, true, true, 0.f, false, h->grad + h->nparam_int) : IWAE_OK;
+  return adam ? run_adam(h, AdamMode::from_grad_over(h->grad + h->nparam_int)) : IWAE_OK;
 }
 
 // The bound inside the engine's backward launch (no bound launch): up to 256
@@ -2462,7 +2447,7 @@ static bool use_tc_bound(iwae_handle* h, const Plan& P, bool ring) {
   // (one spare workgroup runs the whole bound: up to 64 images, 8 per wave)
   if (!h->tune.tc_bound || P.kS > 256 || P.Bimg > 64 || P.need_bce || P.kl || h->prof.kind == 13) return false;
   if (P.piwae && !piwae_unit(h, P, ring)) return false;
-  auto it = h->tc_plans.find(tc_key(P, 1));
+  auto it = h->tc_plans.find(tc_key(P, TCL_BWD));
   if (it == h->tc_plans.end()) return false;
   return (long long)it->second.acc_off >= 64 + 8LL * r4(P.kS);
 }
@@ -2521,20 +2506,8 @@ static int launch_pending(iwae_handle* h) {
         // live timing (iwae_profile_replay): replays repeat this launch with the
         // update part on scratch copies of the parameters, moments and
         // fragment-major copies (job I' rewrites its own outputs): the model is untouched
-        const size_t pb = (size_t)h->nparam_int * sizeof(float), fb = (size_t)h->fx_elems * 2 * sizeof(__bf16);
-        if (h->prof.adam_bytes < 3 * pb + fb) {
-          if (h->prof.adam) HIPCHK(hipFree(h->prof.adam));
-          h->prof.adam = nullptr;
-          HIPCHK(hipMalloc(&h->prof.adam, 3 * pb + fb));
-          h->prof.adam_bytes = 3 * pb + fb;
-        }
-        HIPCHK(hipMemcpyAsync(h->prof.adam, h->params, pb, hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(h->prof.adam + h->nparam_int, h->adam_m, pb, hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(h->prof.adam + 2 * h->nparam_int, h->adam_v, pb, hipMemcpyDeviceToDevice, h->stream));
         UpdArgs r = u;
-        r.param = h->prof.adam; r.m = h->prof.adam + h->nparam_int; r.v = h->prof.adam + 2 * h->nparam_int;
-        r.fx_hi = reinterpret_cast<__bf16*>(h->prof.adam + 3 * h->nparam_int);
-        r.fx_lo = r.fx_hi + h->fx_elems;
+        CHK(prof_state_copy(h, r));
         const TcArgs ta = a;
         h->prof.mem = [ta, r, w, lds](hipStream_t st) { return launch_tcu(st, ta, r, w, lds); };
         h->prof.flop1 = 0.0;
@@ -2545,6 +2518,107 @@ static int launch_pending(iwae_handle* h) {
   }
   if (tc) HIPCHK(launch_tc(h->stream, h->pend.tc, h->pend.tc_rt, h->pend.tc_lds));
   if (up) HIPCHK(launch_update(h->stream, h->pend.upd));
+  return IWAE_OK;
+}
+
+// How an engine train step ends ("How a train step ends"): where the weight
+// gradients come from and what turns them into updated weights, Adam state and fragment-major
+// copies (IN_FUSED: nothing follows the fused launch; APPLY_GRAD: data parallel, after the all-reduce).
+struct StepRoute {
+  enum Grads { FUSED_UPDATE, DW_KERNEL, UPDATE_SLAB_PASS, GROUPED_GEMMS } grads;
+  enum Finish { IN_FUSED, APPLY_GRAD, APPLY_SLABS, ADAM_THEN_FX } finish;
+  bool tcu;      // the fused launch is recorded for ONE launch with job I' (tcu_kernel)
+};
+
+static StepRoute step_route(const iwae_handle* h, const Plan& P, bool adam, bool img_bwd) {
+  const bool fused = use_update(h, P), slab_pass = use_update_slabs(h, P), dp = h->dp_weighted;
+  StepRoute r;
+  r.grads = fused ? StepRoute::FUSED_UPDATE : !slab_pass ? StepRoute::GROUPED_GEMMS
+            : h->tune.dw_wide ? StepRoute::DW_KERNEL : StepRoute::UPDATE_SLAB_PASS;
+  const bool apply = adam && h->tune.upd && upd_tiles_ok(h);    // the update kernel's apply modes can run
+  if (fused) r.finish = dp && adam ? StepRoute::APPLY_GRAD : StepRoute::IN_FUSED;
+  else if (dp && apply) r.finish = StepRoute::APPLY_GRAD;
+  else if (!dp && apply && h->tune.upd_apply && h->slabs) r.finish = StepRoute::APPLY_SLABS;
+  else r.finish = StepRoute::ADAM_THEN_FX;
+  // job I' and the fused update as one launch (tcu_kernel): recorded by tc_run
+  // and run_update, issued by launch_pending.  From 256 sample rows: below, the update's
+  // sample-row tiles are too short to cover job I' and the in-launch hand-off
+  // costs more than the launch boundary (configs[0], 100 rows: 0.0958 vs
+  // 0.0968 ms per step as two launches; profiles/r06j_tcu_rows_ab.txt)
+  r.tcu = img_bwd && h->tune.tcu && fused && !dp && (h->prof.kind < 0 || h->prof.kind == 16) &&
+          (long long)P.Bimg * P.kS >= 256;
+  return r;
+}
+
+// After the sample-row backward: the first encoder layer's backward, the weight gradients, the update.
+static int engine_step_end(iwae_handle* h, const Plan& P, const EpsSet& E, bool adam, bool img, bool unit) {
+  // (a second stream for the first encoder layer's backward beside the other
+  // weight gradients measured slower inside the captured graph: sequential).
+  // Its image-row job also at small batches (B = 20: step 128.1 -> 126.4 us
+  // against the row-block Gaussian backward + two few-row launches)
+  const bool img_bwd = img || h->tune.engine_img_bwd;
+  const StepRoute r = step_route(h, P, adam, img_bwd);
+  h->step.defer_launch = r.tcu;
+  if (img_bwd) CHK(tc_run(h, P, E, TCL_IMG_BWD, nullptr, P.piwae ? h->dlw2 : nullptr, nullptr, unit));
+  else CHK(fused_encoder_bwd(h, P, P.piwae ? h->dlw2 : h->dlw, 0));
+  float* const tail = h->grad + h->nparam_int;       // data parallel: the batch size behind the gradient
+  const long long out0 = h->dense[h->o1].off;        // ... the output MLP's range (the last of the buffer)
+  switch (r.grads) {
+    case StepRoute::FUSED_UPDATE:
+      if (!h->dp_weighted) {
+        // weight gradients, Adam and the fragment-major copies in one launch
+        CHK(run_update(h, P, UpdMode::fused(adam)));
+        h->step.defer_launch = false;
+        CHK(launch_pending(h));
+        break;
+      }
+      // data parallel: the fused gradient pass (B_local * g, B_local in the
+      // tail), the all-reduce, then Adam and the fragment-major copies.  (Not
+      // dp_reduce_slabs: the gradients come from two update launches on two
+      // streams and are reduced in two buckets, not from one sum of the slabs.)
+      if (!adam) return run_update(h, P, UpdMode::dp_grads(WG_ALL, h->stream));
+      if (!h->comm) return fail(h, IWAE_EINVAL, "data parallel without a library communicator");
+      // two buckets whose gradient passes run side by side (each pass alone is a
+      // latency chain on a fraction of the CUs): the output MLP's (the last
+      // range of the buffer, with the tail) on the step's stream, then its
+      // all-reduce while the other layers' pass may still run on the side
+      // stream; then their all-reduce; then ONE launch of Adam and the FX / GX
+      // copies from the summed buffer (the update kernel's apply mode, in place
+      // of the Adam and FX-refresh launches).  Both all-reduces on one stream:
+      // collectives of one communicator stay ordered.
+      HIPCHK(hipEventRecord(h->ev_fork, h->stream));
+      HIPCHK(hipStreamWaitEvent(h->side_stream, h->ev_fork, 0));
+      CHK(run_update(h, P, UpdMode::dp_grads(WG_BUT_OUT, h->side_stream)));
+      HIPCHK(hipEventRecord(h->ev_join, h->side_stream));
+      CHK(run_update(h, P, UpdMode::dp_grads(WG_OUT_ONLY, h->stream)));
+      CHK(allreduce_grad(h, out0, h->nparam_int - out0 + 4, " (output MLP bucket)"));
+      HIPCHK(hipStreamWaitEvent(h->stream, h->ev_join, 0));
+      CHK(allreduce_grad(h, 0, out0, ""));
+      break;
+    case StepRoute::DW_KERNEL: CHK(run_dw(h, P)); break;
+    case StepRoute::UPDATE_SLAB_PASS: CHK(run_update(h, P, UpdMode::slab_pass())); break;
+    case StepRoute::GROUPED_GEMMS: CHK(weight_grads(h, P, WG_ALL)); break;
+  }
+  switch (r.finish) {
+    case StepRoute::IN_FUSED: break;
+    case StepRoute::APPLY_GRAD:
+      // data parallel: as finish_step, but Adam + the FX / GX copies in one
+      // update launch (apply mode) in place of the Adam and FX-refresh launches
+      if (r.grads != StepRoute::FUSED_UPDATE) CHK(dp_reduce_slabs(h, P, /*all_reduce=*/true));
+      CHK(run_update(h, P, UpdMode::apply_grad(tail)));
+      break;
+    case StepRoute::APPLY_SLABS:
+      // the slabs summed, Adam and the fragment-major copies in one launch (the
+      // update kernel's apply mode) in place of adam_kernel + fx_refresh_kernel
+      CHK(run_update(h, P, UpdMode::apply_slabs()));
+      break;
+    case StepRoute::ADAM_THEN_FX:
+      CHK(finish_step(h, P, adam));
+      // the next step's engine reads the updated weights' fragment-major copies
+      if (adam) CHK(run_fx(h));
+      break;
+  }
+  if (adam) h->fx_version = h->params_version;
   return IWAE_OK;
 }
 
@@ -2559,7 +2633,7 @@ static int engine_train_body(iwae_handle* h, const Plan& P, const EpsSet& E, boo
   if (img) {
     // first encoder layer: input Dense (few-row / split-K), then its image-row engine job
     CHK(enc0_forward(h, P, true));
-    CHK(tc_run(h, P, E, 2));
+    CHK(tc_run(h, P, E, TCL_IMG_FWD));
   } else if (use_fold0(h, P)) {
     // input Dense only: its l2 and head run inside the forward launch's jobs
     CHK(enc0_forward(h, P, true));
@@ -2568,10 +2642,10 @@ static int engine_train_body(iwae_handle* h, const Plan& P, const EpsSet& E, boo
   }
   bool ring = false;
   if (!nring_train_forward(h, P, E, ring)) return fail(h, IWAE_EHIP, "weight-ring train forward launch failed");
-  if (!ring) CHK(tc_run(h, P, E, 0));
+  if (!ring) CHK(tc_run(h, P, E, TCL_FWD));
   if (use_tc_bound(h, P, ring)) {
     const BoundArgs b = make_bound_args(h, P, true, -1.f, train_loss_ptr(h), adam, true);
-    CHK(tc_run(h, P, E, 1, &b, nullptr, nullptr, piwae_unit(h, P, ring)));
+    CHK(tc_run(h, P, E, TCL_BWD, &b, nullptr, nullptr, piwae_unit(h, P, ring)));
   } else {
     CHK(run_bound(h, P, true, -1.f, train_loss_ptr(h), adam, true));
     // the output MLP's backward on the weight ring where the forward ran on it,
@@ -2597,12 +2671,12 @@ static int engine_train_body(iwae_handle* h, const Plan& P, const EpsSet& E, boo
     // 0.613-0.621 ms at B = 512 -- the two passes, one workgroup per CU each,
     // compete for the CUs)
     if (!rb) {
-      CHK(tc_run(h, P, E, 1, nullptr, nullptr, nullptr, piwae_unit(h, P, ring)));
+      CHK(tc_run(h, P, E, TCL_BWD, nullptr, nullptr, nullptr, piwae_unit(h, P, ring)));
     } else if (h->L >= 2) {
       // nring_bwd 3: the encoder / prior chains on the ring as well
       bool re = false;
       if (!nring_train_backward_enc(h, P, re)) return fail(h, IWAE_EHIP, "weight-ring encoder backward launch failed");
-      if (!re) CHK(tc_run(h, P, E, 5));
+      if (!re) CHK(tc_run(h, P, E, TCL_BWD_NO_OUT));
     }
     if (side) HIPCHK(hipStreamWaitEvent(h->stream, h->ev_join, 0));
   }
@@ -2614,86 +2688,9 @@ static int engine_train_body(iwae_handle* h, const Plan& P, const EpsSet& E, boo
   // (run_update / run_dw: dpx or dlw for the decoder, dlw2 for the encoder),
   // and the image-row job scales its dL/dh sources by dlw2 per sample.
   const bool unit = piwae_unit(h, P, ring);
-  const float* enc_dlw = P.piwae ? h->dlw2 : nullptr;
-  if (P.piwae && !unit) CHK(tc_run(h, P, E, 4, nullptr, h->dlw2, h->dpx2));
+  if (P.piwae && !unit) CHK(tc_run(h, P, E, TCL_BWD_ENC, nullptr, h->dlw2, h->dpx2));
   h->step.piwae_ks = unit;
-  // (a second stream for the first encoder layer's backward beside the other
-  // weight gradients measured slower inside the captured graph: sequential).
-  // Its image-row job also at small batches (B = 20: step 128.1 -> 126.4 us
-  // against the row-block Gaussian backward + two few-row launches)
-  const bool img_bwd = img || h->tune.engine_img_bwd;
-  // job I' and the fused update as one launch (tcu_kernel): recorded here,
-  // issued by launch_pending below.  From 256 sample rows: below, the update's
-  // sample-row tiles are too short to cover job I' and the in-launch hand-off
-  // costs more than the launch boundary (configs[0], 100 rows: 0.0958 vs
-  // 0.0968 ms per step as two launches; profiles/r06j_tcu_rows_ab.txt)
-  const bool tcu = img_bwd && h->tune.tcu && use_update(h, P) && !h->dp_weighted && (h->prof.kind < 0 || h->prof.kind == 16) &&
-                   (long long)P.Bimg * P.kS >= 256;
-  h->step.defer_launch = tcu;
-  if (img_bwd) CHK(tc_run(h, P, E, 3, nullptr, enc_dlw, nullptr, unit));
-  else CHK(fused_encoder_bwd(h, P, P.piwae ? h->dlw2 : h->dlw, 0));
-  if (use_update(h, P) && h->dp_weighted) {
-    // data parallel: the fused gradient pass (B_local * g, B_local in the
-    // tail), the all-reduce, then Adam and the fragment-major copies.  (Not
-    // dp_reduce_slabs: the gradients come from two update launches on two
-    // streams and are reduced in two buckets, not from one sum of the slabs.)
-    float* tail = h->grad + h->nparam_int;
-    if (!adam) return run_update(h, P, false, 0, nullptr, (float)P.B, tail);
-    if (!h->comm) return fail(h, IWAE_EINVAL, "data parallel without a library communicator");
-    // two buckets whose gradient passes run side by side (each pass alone is a
-    // latency chain on a fraction of the CUs): the output MLP's (the last
-    // range of the buffer, with the tail) on the step's stream, then its
-    // all-reduce while the other layers' pass may still run on the side
-    // stream; then their all-reduce; then ONE launch of Adam and the FX / GX
-    // copies from the summed buffer (the update kernel's apply mode, in place
-    // of the Adam and FX-refresh launches).  Both all-reduces on one stream:
-    // collectives of one communicator stay ordered.
-    const long long o0 = h->dense[h->o1].off;
-    HIPCHK(hipEventRecord(h->ev_fork, h->stream));
-    HIPCHK(hipStreamWaitEvent(h->side_stream, h->ev_fork, 0));
-    CHK(run_update(h, P, false, 2, h->side_stream, (float)P.B, nullptr));
-    HIPCHK(hipEventRecord(h->ev_join, h->side_stream));
-    CHK(run_update(h, P, false, 1, nullptr, (float)P.B, tail));
-    CHK(allreduce_grad(h, o0, h->nparam_int - o0 + 4, " (output MLP bucket)"));
-    HIPCHK(hipStreamWaitEvent(h->stream, h->ev_join, 0));
-    CHK(allreduce_grad(h, 0, o0, ""));
-    CHK(run_update(h, P, true, 0, nullptr, 1.f, nullptr, false, true, tail));
-    h->fx_version = h->params_version;
-    return IWAE_OK;
-  }
-  if (use_update(h, P)) {
-    // weight gradients, Adam and the fragment-major copies in one launch
-    CHK(run_update(h, P, adam));
-    h->step.defer_launch = false;
-    CHK(launch_pending(h));
-    if (adam) h->fx_version = h->params_version;
-    return IWAE_OK;
-  }
-  if (use_update_slabs(h, P) && h->tune.dw_wide) CHK(run_dw(h, P));
-  else if (use_update_slabs(h, P)) CHK(run_update(h, P, false, 0, nullptr, 1.f, nullptr, true));
-  else CHK(weight_grads(h, P, true, true, h->dpx));
-  if (h->dp_weighted && adam && h->tune.upd && upd_tiles_ok(h)) {
-    // data parallel: as finish_step, but Adam + the FX / GX copies in one
-    // update launch (apply mode) in place of the Adam and FX-refresh launches
-    CHK(dp_reduce_slabs(h, P, true));
-    CHK(run_update(h, P, true, 0, nullptr, 1.f, nullptr, false, true, h->grad + h->nparam_int));
-    h->fx_version = h->params_version;
-    return IWAE_OK;
-  }
-  if (adam && !h->dp_weighted && h->tune.upd && h->tune.upd_apply && upd_tiles_ok(h) && h->slabs) {
-    // the slabs summed, Adam and the fragment-major copies in one launch (the
-    // update kernel's apply mode) in place of adam_kernel + fx_refresh_kernel
-    CHK(run_update(h, P, true, 0, nullptr, 1.f, nullptr, false, true, nullptr, true));
-    h->fx_version = h->params_version;
-    return IWAE_OK;
-  }
-  CHK(finish_step(h, P, adam));
-  if (adam) {
-    // the next step's engine reads the updated weights' fragment-major copies
-    CHK(run_fx(h));
-    h->fx_version = h->params_version;
-  }
-  return IWAE_OK;
+  return engine_step_end(h, P, E, adam, img, unit);
 }
 
 static int fused_train_body(iwae_handle* h, const Plan& P, const EpsSet& E, bool adam) {
@@ -2701,14 +2698,14 @@ static int fused_train_body(iwae_handle* h, const Plan& P, const EpsSet& E, bool
   CHK(run_bound(h, P, true, -1.f, train_loss_ptr(h), adam));
   if (P.piwae) {
     CHK(fused_decoder_bwd(h, P, h->dlw, h->dpx, false));      // decoder weights: IWAE_{k1 k2}
-    CHK(weight_grads(h, P, false, true, h->dpx));
+    CHK(weight_grads(h, P, WG_DECODER));
     CHK(fused_decoder_bwd(h, P, h->dlw2, h->dpx2, true));     // encoder path: MIWAE(k1, k2) (DReG: softmax^2)
     CHK(fused_encoder_bwd(h, P, h->dlw2));
-    CHK(weight_grads(h, P, true, false, nullptr));
+    CHK(weight_grads(h, P, WG_ENCODER));
   } else {
     CHK(fused_decoder_bwd(h, P, h->dlw, h->dpx, true));
     CHK(fused_encoder_bwd(h, P, h->dlw));
-    CHK(weight_grads(h, P, true, true, h->dpx));
+    CHK(weight_grads(h, P, WG_ALL));
   }
   return finish_step(h, P, adam);
 }
@@ -2836,7 +2833,7 @@ static int prepare_engine(iwae_handle* h, const Plan& P) {
   NrbLaunch nb;
   NreLaunch ne;
   if (nring_plan(h, nr) && nrb_plan(h, nb) && h->L >= 2) {
-    CHK(tc_prepare_one(h, P, 5));
+    CHK(tc_prepare_one(h, P, TCL_BWD_NO_OUT));
     (void)nre_plan(h, ne);
   }
   return IWAE_OK;
@@ -3478,9 +3475,9 @@ int iwae_apply_adam(iwae_handle* h, float grad_scale) {
   if (!(grad_scale > 0.f)) {
     // data parallel: 1 / the all-reduced batch total in the buffer's tail
     if (!h->dp_weighted) return fail(h, IWAE_EINVAL, "grad_scale must be > 0 (0 only after iwae_dp_init)");
-    return run_adam(h, false, true, true, 0.f, true, h->grad + h->nparam_int);
+    return run_adam(h, AdamMode::from_grad_over(h->grad + h->nparam_int).own_tick());
   }
-  return run_adam(h, false, true, true, grad_scale, true);
+  return run_adam(h, AdamMode::from_grad(grad_scale).own_tick());
 }
 
 int iwae_dp_unique_id(void* out128) {
@@ -3738,7 +3735,7 @@ static bool nring_plan(iwae_handle* h, NrLaunch& R) {
 // 32 / 64-row workgroups re-stream their job's weights per tile of rows; here
 // 128 rows share one stream), the model shapes nring_kernel instantiates,
 // Philox or single-buffer injected noise, no Keras-BCE epilogue (L_alpha).
-// Writes what tc_run(which 0) writes.  False: run the engine's launch.
+// Writes what tc_run(TCL_FWD) writes.  False: run the engine's launch.
 static bool nring_train_forward(iwae_handle* h, const Plan& P, const EpsSet& E, bool& ran) {
   ran = false;
   const long long rows = (long long)P.Bimg * P.kS;

@@ -5,7 +5,7 @@ ranks comes from the oracle (test infrastructure); what is under test is
 iwae_replication_project_amd.distributed."""
 import math
 import os
-import socket
+import tempfile
 
 import numpy as np
 import pytest
@@ -14,18 +14,12 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 
-def free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _run(rank, world, port, fn, q):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+def _run(rank, world, rdzv, fn, q):
+    try:
+        dist.init_process_group("gloo", init_method=rdzv, rank=rank, world_size=world)
+    except Exception as e:          # pragma: no cover
+        q.put((rank, repr(e)))
+        return
     try:
         q.put((rank, fn(rank, world)))
     except Exception as e:          # pragma: no cover
@@ -35,15 +29,25 @@ def _run(rank, world, port, fn, q):
 
 
 def spawn(fn, world=2):
+    """The ranks meet through a file in a fresh directory (a port found free and
+    then released can be taken before rank 0 listens on it), and no rank
+    outlives the call: a failed rank cannot leave its peer waiting."""
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = free_port()
-    ps = [ctx.Process(target=_run, args=(r, world, port, fn, q)) for r in range(world)]
-    for p in ps:
-        p.start()
-    out = dict(q.get(timeout=120) for _ in ps)
-    for p in ps:
-        p.join(timeout=60)
+    with tempfile.TemporaryDirectory() as tmp:
+        rdzv = "file://" + os.path.join(tmp, "rendezvous")
+        ps = [ctx.Process(target=_run, args=(r, world, rdzv, fn, q), daemon=True) for r in range(world)]
+        for p in ps:
+            p.start()
+        try:
+            out = dict(q.get(timeout=120) for _ in ps)
+            for p in ps:
+                p.join(timeout=60)
+        finally:
+            for p in ps:
+                if p.is_alive():
+                    p.terminate()
+                    p.join(timeout=60)
     return out
 
 

@@ -15,7 +15,6 @@
   rank: the graph-captured forward_backward -> ncclAllReduce -> Adam step."""
 import math
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -45,41 +44,48 @@ def _flat(ws):
     return np.concatenate([np.asarray(w).ravel() for w in ws])
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _launch(fn, world=2, timeout=150):
+    """fn(rank, world) in `world` spawned processes of one gloo group.  The ranks
+    meet through a file in a fresh directory (a port found free and then
+    released can be taken before rank 0 listens on it, by another run on the
+    same machine for one); a rank that fails reports it, and no rank outlives
+    the call, so a failure cannot leave a process waiting for its peer."""
+    import tempfile
     import torch.multiprocessing as mp
-    port = _free_port()
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    ps = [ctx.Process(target=_rank_main, args=(fn, r, world, port, q)) for r in range(world)]
-    for p in ps:
-        p.start()
-    out = dict(q.get(timeout=timeout) for _ in ps)
-    for p in ps:
-        p.join(timeout=30)
+    with tempfile.TemporaryDirectory() as tmp:
+        rdzv = "file://" + os.path.join(tmp, "rendezvous")
+        ps = [ctx.Process(target=_rank_main, args=(fn, r, world, rdzv, q), daemon=True) for r in range(world)]
+        for p in ps:
+            p.start()
+        try:
+            out = dict(q.get(timeout=timeout) for _ in ps)
+            for p in ps:
+                p.join(timeout=30)
+        finally:
+            for p in ps:
+                if p.is_alive():
+                    p.terminate()
+                    p.join(timeout=30)
     for r in range(world):
         assert not isinstance(out[r], str), out[r]
     return out
 
 
-def _rank_main(fn, rank, world, port, q):
+def _rank_main(fn, rank, world, rdzv, q):
+    import traceback
     import torch
     import torch.distributed as dist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    torch.cuda.set_device(0)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        torch.cuda.set_device(0)
+        dist.init_process_group("gloo", init_method=rdzv, rank=rank, world_size=world)
+    except Exception as e:          # pragma: no cover
+        q.put((rank, repr(e) + traceback.format_exc()))
+        return
     try:
         q.put((rank, fn(rank, world)))
     except Exception as e:          # pragma: no cover
-        import traceback
         q.put((rank, repr(e) + traceback.format_exc()))
     finally:
         dist.destroy_process_group()
