@@ -685,7 +685,7 @@ enum TcKind {
   TC_LOADSLAB = 11,  // image rows: y1 = tanh(sum of the input layer's split-K slabs)   F:26
   TC_GBWD0 = 12      // image rows: dP0 = sum over the image's k samples of the h1 Gaussian backward
 };
-constexpr int kTcMaxOps = 20, kTcMaxBufs = 12, kTcMaxJobs = 3;
+constexpr int kTcMaxOps = 20, kTcMaxBufs = 16, kTcMaxJobs = 3;
 struct TcOp {
   int kind;
   const __bf16* Whi; const __bf16* Wlo; unsigned W_bytes; int ldk, K, N;   // dense ops: split rows [.][ldk]
@@ -706,7 +706,39 @@ struct TcOp {
   int img;                    // runs on the images of the workgroup's sample rows (rows b = row / kS)
   int gsync;                  // reads global data an earlier op of this launch wrote: full barrier before it
 };
+// The op's "hot" record: what the op loop and a Dense op's prologue read,
+// resolved on the host for the plan's row-tile count and packed into one
+// 64-byte line, which the kernel reads whole (one s_load_dwordx16, one wait)
+// -- for op s + 1 during op s, so the hand-over prefetch and the op itself use
+// the same registers.  TcOp keeps everything (the epilogues and the
+// elementwise ops read their fields from it where they use them).
+constexpr unsigned kTcHotImg = 1u << 8;        // TcOp::img
+constexpr unsigned kTcHotOnes = 1u << 9;       // TcOp::ones (ones column at pad_lo)
+constexpr unsigned kTcHotFullSync = 1u << 10;  // a full barrier follows the op (the next op reads this launch's global stores, or none follows)
+constexpr unsigned kTcHotNextDense = 1u << 11; // the next op is a Dense op whose first units this op may request
+struct alignas(64) TcHot {
+  uint32_t whi_lo, whi_hi, wlo_lo, wlo_hi;   // Dense: the two weight planes' buffer bases ...
+  uint32_t W_bytes;                          // ... and their range
+  uint32_t flags;                            // TcKind in bits 0-7 | kTcHot*
+  uint32_t in_off, in_ld;                    // Dense: input hi plane, bf16 offset / row stride (lo plane: + 16 RT ld)
+  uint32_t out_off, out_ld;                  // Dense: output hi plane (the input's when the op has no LDS output)
+  uint32_t pad;                              // Dense: per-op zero padding, columns [pad & 0xFFFF, pad >> 16) of the output
+  uint32_t kt;                               // Dense: ldk / 32 | k chunks of 128 (nch) << 16
+  uint32_t ntile, t0;                        // Dense: column tiles of N, the first one the job runs
+  uint32_t N;
+  uint32_t rsvd;
+};
+static_assert(sizeof(TcHot) == 64, "one 64-byte line per op");
+// A Dense output's padding written before the job's first barrier instead of
+// by its op (plans in which every op's LDS output has a buffer of its own)
+struct TcPad {
+  uint32_t off, ld;           // output hi plane: bf16 offset / row stride
+  uint32_t pad;               // columns [pad & 0xFFFF, pad >> 16)
+  uint32_t ones;              // ones column at the first of them
+};
 struct TcJob {
+  TcHot hot[kTcMaxOps];       // first: every record on a line of its own (TcPlan is 64-byte aligned)
+  TcPad pre[kTcMaxOps]; int npre;   // the up-front padding (npre > 0: the ops' own TcHot::pad are 0)
   TcOp op[kTcMaxOps]; int nop;
   int buf_off[kTcMaxBufs], buf_ld[kTcMaxBufs];   // bf16 offset of the hi plane / row stride
   float* logq; float* logp; float* bern; int ld_bern, bern_col;   // per-row sums this job writes (null: none)
@@ -758,10 +790,12 @@ struct TcArgs {
   int unit_w;
   // the bound inside the backward launch (bnd_rows): every workgroup computes
   // its rows' dL/dlw and dpx into LDS at float offset bnd_lds (dpx at + 16 RT)
-  // from its images' log weights, staging an image per wave at wave * bnd_ld;
+  // from its images' log weights, staging an image per wave at float offset
+  // bnd_stage + wave * bnd_ld (0: the op buffers' space, nothing in them yet;
+  // plans padded up front: the final row reduction's scratch);
   // workgroup bnd_block (the grid's last) runs the whole bound: log weights,
   // loss, global dlw / dpx, the Philox base and the Adam step
-  BoundArgs bnd; int bnd_rows, bnd_block, bnd_ld, bnd_lds;
+  BoundArgs bnd; int bnd_rows, bnd_block, bnd_ld, bnd_lds, bnd_stage;
 };
 hipError_t launch_tc(hipStream_t st, const TcArgs& a, int rt, size_t lds_bytes);
 // job I' (a one-job image-row plan, RT = 1) and the fused update (8 waves) in one launch

@@ -216,6 +216,7 @@ struct TcRec {
   int row_step = 0;                  // rows per workgroup (image-row launches; 0: 16 rt)
   size_t lds = 0;
   int acc_off = 0;                   // float offset of the per-row accumulators in LDS
+  bool prepad = false;               // every op's output in a buffer of its own, padding written up front (TcJob::pre)
   double flop = 0.0;                 // algorithmic FLOPs of one launch (weight products, no bias rows)
   unsigned kinds = 0;                // op kinds of the plan's jobs (TcArgs::kinds)
 };
@@ -1911,9 +1912,13 @@ static bool use_engine(const iwae_handle* h, const Plan& P) {
 struct TcBuild {
   TcJob J;
   std::vector<int> width;
+  struct Need { int op, buf, w; };
+  std::vector<Need> needs;           // every need() by the op it was made for (the op added last)
   TcBuild() : width(kTcMaxBufs, 0) { std::memset(&J, 0, sizeof(J)); }
   void need(int b, int w) {
-    if (b >= 0) width[b] = std::max(width[b], w);
+    if (b < 0) return;
+    width[b] = std::max(width[b], w);
+    needs.push_back({J.nop - 1, b, w});
   }
   TcOp& add(int kind) {
     TcOp& o = J.op[J.nop++];
@@ -1966,6 +1971,40 @@ static size_t tc_layout(TcBuild& B, int rt) {
     off += 2 * R * B.J.buf_ld[b];
   }
   return (size_t)off * sizeof(__bf16);
+}
+
+// The same job with every op's LDS output in a buffer of its own (the ops'
+// readers renamed; widths from the ops' own needs): no op then writes a buffer
+// another op's padding lives in, so all padding can be written before the
+// job's first barrier.  False when the job needs more than kTcMaxBufs buffers.
+static bool tc_unshare(const TcBuild& B, TcBuild& U) {
+  U = B;
+  std::fill(U.width.begin(), U.width.end(), 0);
+  U.needs.clear();
+  int cur[kTcMaxBufs], n = 0;         // the buffer that holds what the job's buffer b holds now
+  for (int b = 0; b < kTcMaxBufs; ++b) cur[b] = -1;
+  for (int s = 0; s < B.J.nop; ++s) {
+    const TcOp& o = B.J.op[s];
+    TcOp& u = U.J.op[s];
+    if (o.in_buf >= 0) {
+      if (cur[o.in_buf] < 0) {          // (scratch nothing wrote: job I's reduction)
+        if (n >= kTcMaxBufs) return false;
+        cur[o.in_buf] = n++;
+      }
+      u.in_buf = cur[o.in_buf];
+    }
+    if (o.out_buf >= 0) {
+      if (n >= kTcMaxBufs || o.out_buf == o.in_buf) return false;
+      u.out_buf = cur[o.out_buf] = n++;
+    }
+    for (const TcBuild::Need& q : B.needs) {
+      if (q.op != s) continue;
+      const int nb = q.buf == o.in_buf ? u.in_buf : q.buf == o.out_buf ? u.out_buf : -1;
+      if (nb < 0) return false;
+      U.width[nb] = std::max(U.width[nb], q.w);
+    }
+  }
+  return true;
 }
 
 // The first encoder layer's l2 and head folded into a forward sample-row job
@@ -2221,6 +2260,45 @@ static size_t tc_lds_bytes(std::vector<TcBuild>& jobs, int rt, int* acc_off = nu
   return (size_t)off * sizeof(float) + (size_t)(4 + 4 * 8) * 16 * rt * sizeof(float);
 }
 
+// The ops' hot records (TcHot) of a job whose LDS layout is final: everything
+// the op loop and a Dense op's prologue need, resolved here once per plan so
+// the kernel computes nothing about an op from its TcOp fields.
+static void tc_resolve_hot(TcJob& J, bool prepad) {
+  auto reads_global = [](const TcOp& o) { return o.kind == TC_PRIOR || o.kind == TC_GBWD_ENC || o.gsync != 0; };
+  for (int s = 0; s < kTcMaxOps; ++s) std::memset(&J.hot[s], 0, sizeof(TcHot));
+  std::memset(J.pre, 0, sizeof(J.pre));
+  J.npre = 0;
+  for (int s = 0; s < J.nop; ++s) {
+    const TcOp& o = J.op[s];
+    TcHot& H = J.hot[s];
+    const TcOp* nx = s + 1 < J.nop ? &J.op[s + 1] : nullptr;
+    H.flags = (uint32_t)o.kind | (o.img ? kTcHotImg : 0u) | (o.ones ? kTcHotOnes : 0u);
+    // LDS-only barrier unless the next op reads what this launch stored (or none follows)
+    if (!nx || reads_global(*nx)) H.flags |= kTcHotFullSync;
+    else if (nx->kind <= TC_LAST_DENSE) H.flags |= kTcHotNextDense;
+    if (o.kind > TC_LAST_DENSE) continue;
+    const uint64_t whi = (uint64_t)(uintptr_t)o.Whi, wlo = (uint64_t)(uintptr_t)o.Wlo;
+    H.whi_lo = (uint32_t)whi; H.whi_hi = (uint32_t)(whi >> 32);
+    H.wlo_lo = (uint32_t)wlo; H.wlo_hi = (uint32_t)(wlo >> 32);
+    H.W_bytes = o.W_bytes;
+    const int ob = o.out_buf >= 0 ? o.out_buf : o.in_buf;
+    H.in_off = (uint32_t)J.buf_off[o.in_buf]; H.in_ld = (uint32_t)J.buf_ld[o.in_buf];
+    H.out_off = (uint32_t)J.buf_off[ob]; H.out_ld = (uint32_t)J.buf_ld[ob];
+    // zero padding [width, next_k) of the output the op writes before its tiles
+    const int width = o.kind == TC_SAMPLE ? o.d : o.N;
+    if (o.out_buf >= 0 && o.next_k > width) H.pad = (uint32_t)width | ((uint32_t)o.next_k << 16);
+    if (prepad && H.pad) {               // written before the job's first barrier instead
+      J.pre[J.npre++] = TcPad{H.out_off, H.out_ld, H.pad, (uint32_t)(o.ones ? 1 : 0)};
+      H.pad = 0;
+    }
+    const int nch = (o.ldk + 127) / 128;     // k chunks of 4 k steps (TC_KS) of 32
+    H.kt = (uint32_t)(o.ldk >> 5) | ((uint32_t)nch << 16);
+    H.ntile = (uint32_t)((o.N + 15) >> 4);
+    H.t0 = (uint32_t)o.t0;
+    H.N = (uint32_t)o.N;
+  }
+}
+
 constexpr size_t kTcLdsBytes = 160 * 1024;
 
 // Whether every launch of an engine step has a plan that fits the LDS at the
@@ -2267,8 +2345,23 @@ static int tc_prepare_one(iwae_handle* h, const Plan& P, TcLaunch which) {
   for (int rt : {4, 2, 1}) {
     if (rt > want) continue;
     int acc_off = 0;
-    const size_t lds = tc_lds_bytes(jobs, rt, &acc_off);
+    size_t lds = tc_lds_bytes(jobs, rt, &acc_off);
     if (lds <= kTcLdsBytes) {
+      // 16-row plans that still fit with a buffer per op output: padding off
+      // the op chain (never a reason not to fit: the shared layout stays
+      // otherwise).  The backward launch's bound then stages its images' log
+      // weights in the row reduction's scratch ([4][8 waves][16] floats).
+      std::vector<TcBuild> own(jobs.size());
+      bool ok = rt == 1 && (which == TCL_FWD || img || 8 * r4(kS) <= 4 * 8 * 16);
+      for (size_t j = 0; ok && j < jobs.size(); ++j) ok = tc_unshare(jobs[j], own[j]);
+      if (ok) {
+        int acc2 = 0;
+        const size_t lds2 = tc_lds_bytes(own, rt, &acc2);
+        if (lds2 <= kTcLdsBytes) {
+          jobs = own; lds = lds2; acc_off = acc2;
+          rec.prepad = true;
+        }
+      }
       rec.rt = rt;
       rec.lds = lds;
       rec.acc_off = acc_off;
@@ -2278,6 +2371,7 @@ static int tc_prepare_one(iwae_handle* h, const Plan& P, TcLaunch which) {
       plan.acc_off = acc_off;
       for (size_t j = 0; j < jobs.size(); ++j) {
         plan.job[j] = jobs[j].J;
+        tc_resolve_hot(plan.job[j], rec.prepad);
         for (int o = 0; o < jobs[j].J.nop; ++o) rec.kinds |= 1u << jobs[j].J.op[o].kind;
       }
       HIPCHK(hipMalloc(&rec.dev, sizeof(TcPlan)));
@@ -2369,6 +2463,7 @@ static int tc_run(iwae_handle* h, const Plan& P, const EpsSet& E, TcLaunch which
     a.bnd_block = h->tune.tc_xcd && a.xcd_slots > 0 ? 8 * a.xcd_slots : tot;
     a.bnd_ld = r4(P.kS);
     a.bnd_lds = rec.acc_off + (2 + 4 * 8) * 16 * rec.rt;
+    a.bnd_stage = rec.prepad ? rec.acc_off + 2 * 16 * rec.rt : 0;
     a.rng_base = nullptr;
   }
   const bool prof = (which == TCL_FWD || which == TCL_BWD) && h->prof.kind == 10 + which;

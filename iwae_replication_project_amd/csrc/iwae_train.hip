@@ -84,6 +84,15 @@ typedef const TC_CONST TcOp COp;
 typedef const TC_CONST TcJob CJob;
 typedef const TC_CONST TcPlan CPlan;
 typedef const TC_CONST uint32_t CU32;
+typedef unsigned tc_u32x16 __attribute__((ext_vector_type(16)));
+
+// Op s's hot record, read whole: one 64-byte scalar load (the record is a
+// 64-byte-aligned line of the plan), every field in registers after one wait.
+__device__ __forceinline__ TcHot tc_hot(CJob& J, int s) {
+  const tc_u32x16 v = *reinterpret_cast<const TC_CONST tc_u32x16*>(&J.hot[s]);
+  return __builtin_bit_cast(TcHot, v);
+}
+__device__ __forceinline__ int tc_kind(const TcHot& H) { return (int)(H.flags & 0xFFu); }
 
 // Touch every 64-byte line of the job's descriptors once at kernel start: the
 // scalar-cache misses then overlap each other instead of stalling each op's
@@ -106,6 +115,15 @@ __device__ __forceinline__ TcBuf tc_buf(CJob& J, int b) {
   TcBuf B;
   B.ld = J.buf_ld[b];
   B.hi = base + J.buf_off[b];
+  B.lo = B.hi + 16 * RT * B.ld;
+  return B;
+}
+// a Dense op's input / output planes from its hot record
+template <int RT>
+__device__ __forceinline__ TcBuf tc_buf_at(unsigned off, unsigned ld) {
+  TcBuf B;
+  B.ld = (int)ld;
+  B.hi = reinterpret_cast<__bf16*>(tcs) + off;
   B.lo = B.hi + 16 * RT * B.ld;
   return B;
 }
@@ -177,13 +195,6 @@ __device__ __forceinline__ int tc_src_row(COp& S, int f) {
   const int q = f >> 3, w = f & 7, j = 4 * q + (w & 3);
   if (j >= S.d) return -1;
   return w < 4 ? j : S.d + j;
-}
-// byte offset (both planes) of this lane's fragment of column tile t at k0 in
-// the fragment-major copy (FX / GX: [tile][k step][64 lanes][8]), or kOOB
-__device__ __forceinline__ unsigned tc_frag_base(COp& S, int t, int k0) {
-  const int lane = threadIdx.x & 63;
-  const int ntile = (S.N + 15) >> 4;
-  return t < ntile ? (unsigned)(((t * (S.ldk >> 5) + (k0 >> 5)) * 64 + lane) * 16) : kOOB;
 }
 // every register of the set is written (k steps past ns read zeros out of
 // range): a set is never partially live across units
@@ -521,22 +532,41 @@ struct TcUnit {
   int t, k0, ns;
   bool first, last;
 };
-__device__ __forceinline__ TcUnit tc_unit(COp& S, int u, int nch) {
-  const int wave = tc_wave();
-  TcUnit x;
-  const int c = u % nch;
-  x.t = S.t0 + wave + TC_NW * (u / nch);
-  x.k0 = 32 * TC_KS * c;
-  x.ns = min(TC_KS, (S.ldk - x.k0) >> 5);
-  x.first = c == 0;
-  x.last = c == nch - 1;
-  return x;
+// The units of one Dense op for this wave, from the op's hot record (scalar
+// arithmetic only: no load, no division).
+struct TcStream {
+  __amdgpu_buffer_rsrc_t rh, rl;
+  int nch, U;                 // k chunks per tile, this wave's units
+  int ksteps, ntile, tw;      // ldk / 32, column tiles of N, this wave's first tile (t0 + wave)
+};
+__device__ __forceinline__ TcStream tc_stream(const TcHot& H) {
+  TcStream q;
+  q.ksteps = (int)(H.kt & 0xFFFFu);
+  q.nch = (int)(H.kt >> 16);
+  q.ntile = (int)H.ntile;
+  q.tw = (int)H.t0 + tc_wave();
+  q.U = q.tw < q.ntile ? (int)(((unsigned)(q.ntile - 1 - q.tw) / TC_NW + 1) * (unsigned)q.nch) : 0;
+  q.rh = buf_rsrc((const void*)(((uint64_t)H.whi_hi << 32) | H.whi_lo), H.W_bytes);
+  q.rl = buf_rsrc((const void*)(((uint64_t)H.wlo_hi << 32) | H.wlo_lo), H.W_bytes);
+  return q;
 }
-__device__ __forceinline__ void tc_issue(COp& S, __amdgpu_buffer_rsrc_t rh, __amdgpu_buffer_rsrc_t rl,
-                                         const TcUnit& x, TcFrag& f) {
-  const unsigned vb = tc_frag_base(S, x.t, x.k0);
-#pragma unroll
-  for (int u = 0; u < TC_KS; ++u) tc_fetch_step(rh, rl, vb, u, x.ns, f);
+// A unit as (k chunk c, the wave's tile index ti): counters advanced per unit
+// (unit u = ti * nch + c), wave-uniform.
+struct TcCur {
+  int c, ti;
+};
+__device__ __forceinline__ void tc_next(TcCur& x, int nch) {
+  if (++x.c == nch) { x.c = 0; ++x.ti; }
+}
+__device__ __forceinline__ TcCur tc_cur1(int nch) { return nch > 1 ? TcCur{1, 0} : TcCur{0, 1}; }   // unit 1
+__device__ __forceinline__ TcUnit tc_unit(const TcStream& q, const TcCur& c) {
+  TcUnit x;
+  x.t = q.tw + TC_NW * c.ti;
+  x.k0 = 32 * TC_KS * c.c;
+  x.ns = min(TC_KS, q.ksteps - TC_KS * c.c);
+  x.first = c.c == 0;
+  x.last = c.c == q.nch - 1;
+  return x;
 }
 
 // epilogue operands of tile t: pixels (BERN), forward tanh output (TGRAD),
@@ -593,59 +623,55 @@ __device__ __forceinline__ void tc_epilogue(const TcArgs& A, COp& S, const TcBuf
 struct TcSets {              // X, Y live across ops; A, B are local to a Dense op
   TcFrag X, Y;
 };
-struct TcStream {          // the units of one Dense op for this wave
-  __amdgpu_buffer_rsrc_t rh, rl;
-  int nch, U;
-};
-__device__ __forceinline__ TcStream tc_stream(COp& S) {
-  const int wave = tc_wave();
-  TcStream q;
-  const int ntile = (S.N + 15) >> 4;
-  q.nch = (S.ldk + 32 * TC_KS - 1) / (32 * TC_KS);
-  q.U = S.t0 + wave < ntile ? ((ntile - 1 - S.t0 - wave) / TC_NW + 1) * q.nch : 0;
-  q.rh = buf_rsrc(S.Whi, S.W_bytes);
-  q.rl = buf_rsrc(S.Wlo, S.W_bytes);
-  return q;
-}
-// request unit u of op S (past its end: out-of-range loads, the set is still
-// rewritten whole)
-__device__ __forceinline__ void tc_issue_u(COp& S, const TcStream& q, int u, TcFrag& f) {
-  const bool own = u < q.U;
-  const TcUnit x = tc_unit(S, own ? u : 0, q.nch);
-  const unsigned vb = own ? tc_frag_base(S, x.t, x.k0) : kOOB;
+// request unit c of the op (own false: past the op's end -- out-of-range
+// loads, the set is still rewritten whole).  The lane's fragment of column tile
+// t at k step 4 c in the fragment-major copy (FX / GX: [tile][k step][64
+// lanes][8]) is at byte ((t * ksteps + 4 c) * 64 + lane) * 16 of both planes.
+__device__ __forceinline__ void tc_issue_u(const TcStream& q, const TcCur& c, bool own, TcFrag& f) {
+  const int lane = threadIdx.x & 63;
+  const int t = q.tw + TC_NW * c.ti;
+  const unsigned vb = (own && t < q.ntile) ? (unsigned)(((t * q.ksteps + TC_KS * c.c) * 64 + lane) * 16) : kOOB;
+  const int ns = own ? min(TC_KS, q.ksteps - TC_KS * c.c) : 0;
 #pragma unroll
-  for (int k = 0; k < TC_KS; ++k) tc_fetch_step(q.rh, q.rl, vb, k, own ? x.ns : 0, f);
+  for (int k = 0; k < TC_KS; ++k) tc_fetch_step(q.rh, q.rl, vb, k, ns, f);
 }
-// an elementwise op requests the first two units of the next Dense op Sn
-__device__ __forceinline__ int tc_prefetch(COp& Sn, TcSets& F) {
-  const TcStream qn = tc_stream(Sn);
-  if (qn.U > 0) tc_issue_u(Sn, qn, 0, F.X);
-  if (qn.U > 1) tc_issue_u(Sn, qn, 1, F.Y);
+// an elementwise op requests the first two units of the next Dense op
+__device__ __forceinline__ int tc_prefetch(const TcHot& Hn, TcSets& F) {
+  const TcStream qn = tc_stream(Hn);
+  if (qn.U > 0) tc_issue_u(qn, TcCur{0, 0}, true, F.X);
+  if (qn.U > 1) tc_issue_u(qn, tc_cur1(qn.nch), true, F.Y);
   return min(2, qn.U);
 }
 
 // One Dense op (any kind: the fragment pipeline is one piece of code, only the
 // epilogue switches on the kind).  npre: how many of the op's first units (in
-// X, Y) the previous op already requested; Sn: the next op when it is a Dense
-// op whose first units this op requests.  Returns the next op's npre.
+// X, Y) the previous op already requested.  H: the op's hot record; Hn: the
+// next op's, whose first units this op requests when it is a prefetchable
+// Dense op (kTcHotNextDense).  S: the op's cold fields (epilogues).  Returns the
+// next op's npre.
 template <int RT, unsigned KM = kTcKindsAll>
-__device__ __forceinline__ int tc_dense(const TcArgs& A, CJob& J, COp& S, const int kind, uint64_t base,
-                                        TcRows<RT>& R, int row0, int nrows, TcSets& F, int npre, COp* Sn,
-                                        int utr = -1) {
+__device__ __forceinline__ int tc_dense(const TcArgs& A, COp& S, const TcHot& H, const TcHot& Hn, uint64_t base,
+                                        TcRows<RT>& R, int row0, int nrows, TcSets& F, int npre, int utr = -1) {
 #ifdef IWAE_TC_SKIPDENSE  // timing experiment only
   return 0;
 #endif
-  const TcStream q = tc_stream(S);
-  TcStream qn;
-  if (Sn) qn = tc_stream(*Sn);
-  else { qn.U = 0; qn.nch = 1; qn.rh = qn.rl = q.rh; }
+  const int kind = tc_kind(H);
+  const bool next = (H.flags & kTcHotNextDense) != 0;
+  const TcStream q = tc_stream(H);
+  TcStream qn = tc_stream(Hn);
+  if (!next) qn.U = 0;
   const int U = q.U, Un = min(2, qn.U);
-  const TcBuf IN = tc_buf<RT>(J, S.in_buf);
-  const TcBuf OUT = tc_buf<RT>(J, S.out_buf >= 0 ? S.out_buf : S.in_buf);
-  if (npre < 1 && U > 0) tc_issue_u(S, q, 0, F.X);
-  if (npre < 2 && U > 1) tc_issue_u(S, q, 1, F.Y);
-  if (U <= 1 && Un > 1) tc_issue_u(*Sn, qn, 1, F.Y);     // Y is not used by this op
-  if (U == 0 && Un > 0) tc_issue_u(*Sn, qn, 0, F.X);
+  const TcBuf IN = tc_buf_at<RT>(H.in_off, H.in_ld);
+  const TcBuf OUT = tc_buf_at<RT>(H.out_off, H.out_ld);
+  const TcCur c0 = {0, 0};
+  if (npre < 1 && U > 0) tc_issue_u(q, c0, true, F.X);
+  if (npre < 2 && U > 1) tc_issue_u(q, tc_cur1(q.nch), true, F.Y);
+  if (U <= 1 && Un > 1) tc_issue_u(qn, tc_cur1(qn.nch), true, F.Y);     // Y is not used by this op
+  if (U == 0 && Un > 0) tc_issue_u(qn, c0, true, F.X);
+  // the unit being multiplied and the unit to request next (two ahead), advanced per step
+  TcCur cm = c0, ci = c0;
+  tc_next(ci, q.nch);
+  tc_next(ci, q.nch);
   float4 ov[RT];
   float2 tv[RT];
   tc_f32x4 acc[RT];
@@ -656,7 +682,7 @@ __device__ __forceinline__ int tc_dense(const TcArgs& A, CJob& J, COp& S, const 
   // hand X / Y over to the next op's unit u.  Step u >= 2: multiply unit u (in
   // A / B), then request unit u + 2 into the same set.
   auto step = [&](int u, TcFrag& cur, TcFrag& nxt, bool handover) {
-    const TcUnit x = tc_unit(S, u, q.nch);
+    const TcUnit x = tc_unit(q, cm);
 #ifdef IWAE_TC_TRACE
     const bool st = utr >= 0 && (threadIdx.x & 63) == 0 && u < 16;
     if (st) g_tc_utrace[(utr * 16 + u) * 3] = wall_clock64();
@@ -674,16 +700,18 @@ __device__ __forceinline__ int tc_dense(const TcArgs& A, CJob& J, COp& S, const 
 #if IWAE_TC_UNCOND
     // requests past the op's last unit (or the next op's) are out-of-range
     // loads of zeros: unconditional, so the wait counts stay static
-    if (handover) tc_issue_u(S, q, u + 2, nxt);
+    if (handover) tc_issue_u(q, ci, u + 2 < U, nxt);
     tc_mma<RT>(IN, x.k0, x.ns, cur, acc);
-    if (handover && Sn) tc_issue_u(*Sn, qn, u, cur);
-    if (!handover) tc_issue_u(S, q, u + 2, cur);
+    if (handover && next) tc_issue_u(qn, u == 0 ? c0 : tc_cur1(qn.nch), u < Un, cur);
+    if (!handover) tc_issue_u(q, ci, u + 2 < U, cur);
 #else
-    if (handover && u + 2 < U) tc_issue_u(S, q, u + 2, nxt);
+    if (handover && u + 2 < U) tc_issue_u(q, ci, true, nxt);
     tc_mma<RT>(IN, x.k0, x.ns, cur, acc);
-    if (handover && u < Un) tc_issue_u(*Sn, qn, u, cur);
-    if (!handover && u + 2 < U) tc_issue_u(S, q, u + 2, cur);
+    if (handover && u < Un) tc_issue_u(qn, u == 0 ? c0 : tc_cur1(qn.nch), true, cur);
+    if (!handover && u + 2 < U) tc_issue_u(q, ci, true, cur);
 #endif
+    tc_next(cm, q.nch);
+    tc_next(ci, q.nch);
 #ifdef IWAE_TC_TRACE
     if (st) {
       asm volatile("" ::"v"(acc[0][0]) : "memory");
@@ -732,19 +760,21 @@ __device__ __forceinline__ int tc_dense(const TcArgs& A, CJob& J, COp& S, const 
 // multiplied.  No cross-op prefetch (the four-set pipeline of tc_dense spills
 // at these tile counts); an op's first unit waits one round trip.
 template <int RT, unsigned KM = kTcKindsAll>
-__device__ __forceinline__ void tc_dense2(const TcArgs& A, CJob& J, COp& S, const int kind, uint64_t base,
+__device__ __forceinline__ void tc_dense2(const TcArgs& A, COp& S, const TcHot& H, uint64_t base,
                                          TcRows<RT>& R, int row0, int nrows) {
-  const TcStream q = tc_stream(S);
+  const int kind = tc_kind(H);
+  const TcStream q = tc_stream(H);
   const int U = q.U;
-  const TcBuf IN = tc_buf<RT>(J, S.in_buf);
-  const TcBuf OUT = tc_buf<RT>(J, S.out_buf >= 0 ? S.out_buf : S.in_buf);
+  const TcBuf IN = tc_buf_at<RT>(H.in_off, H.in_ld);
+  const TcBuf OUT = tc_buf_at<RT>(H.out_off, H.out_ld);
   float4 ov[RT];
   float2 tv[RT];
   tc_f32x4 acc[RT];
   TcFrag fP, fQ;
-  if (U > 0) tc_issue_u(S, q, 0, fP);
+  TcCur cm = {0, 0}, ci = tc_cur1(q.nch);      // the unit being multiplied, the unit to request (one ahead)
+  if (U > 0) tc_issue_u(q, cm, true, fP);
   auto step = [&](int u, TcFrag& cur, TcFrag& nxt) {
-    const TcUnit x = tc_unit(S, u, q.nch);
+    const TcUnit x = tc_unit(q, cm);
     if (x.first) {
       switch (kind) {
         case TC_BERN: if constexpr ((KM >> TC_BERN) & 1u) tc_epi_loads<RT, TC_BERN>(A, S, x.t, R, row0, nrows, ov, tv); break;
@@ -757,8 +787,10 @@ __device__ __forceinline__ void tc_dense2(const TcArgs& A, CJob& J, COp& S, cons
     }
     // unconditional (past the op's last unit: out-of-range loads of zeros): a
     // conditional request makes the compiler wait for every load in flight
-    tc_issue_u(S, q, u + 1, nxt);
+    tc_issue_u(q, ci, u + 1 < U, nxt);
     tc_mma<RT>(IN, x.k0, x.ns, cur, acc);
+    tc_next(cm, q.nch);
+    tc_next(ci, q.nch);
     if (x.last) {
       switch (kind) {
         case TC_TANH: if constexpr ((KM >> TC_TANH) & 1u) tc_epilogue<RT, TC_TANH>(A, S, OUT, x.t, base, acc, ov, tv, R, row0, nrows); break;
@@ -781,9 +813,9 @@ __device__ __forceinline__ void tc_dense2(const TcArgs& A, CJob& J, COp& S, cons
 // Barrier between ops.  LDS only: global stores (activations for the weight
 // gradients, read by later launches) and the next op's prefetched weights stay
 // in flight.  Ops that read global data written earlier in this launch by this
-// workgroup (the prior head's target h, the encoder head's dL/dh sources) get
-// the full __syncthreads (every store of every wave completed first).
-__device__ __forceinline__ bool tc_needs_global(int kind) { return kind == TC_PRIOR || kind == TC_GBWD_ENC; }
+// workgroup (the prior head's target h, the encoder head's dL/dh sources; ops
+// flagged gsync) get the full __syncthreads (every store of every wave
+// completed first): the host marks the op before them kTcHotFullSync.
 __device__ __forceinline__ void tc_lds_barrier() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
   __builtin_amdgcn_s_barrier();
@@ -1171,8 +1203,18 @@ __device__ __forceinline__ void tc_body(const TcArgs& A, const int bid) {
   // this workgroup's dL/dlw and dpx (the op buffers' space stages the images'
   // log weights: nothing is in them yet).  (Inside the op loop, beside the
   // first op's weight prefetch, it slowed every engine launch by 2-3 us.)
-  if (A.bnd_rows) bound_rows(A.bnd, row0, row0 + nrows, wave, TC_NW, tcs + wave * A.bnd_ld, tcs + A.bnd_lds,
-                             tcs + A.bnd_lds + R);
+  if (A.bnd_rows) bound_rows(A.bnd, row0, row0 + nrows, wave, TC_NW, tcs + A.bnd_stage + wave * A.bnd_ld,
+                             tcs + A.bnd_lds, tcs + A.bnd_lds + R);
+  // padding off the op chain: where every op's output has a buffer of its own,
+  // all the job's zero / ones columns are written here, before the first barrier
+  if constexpr (RT == 1) {
+    const int npad = J.npre;
+    for (int i = 0; i < npad; ++i) {
+      const TC_CONST TcPad& p = J.pre[i];
+      const unsigned pad = p.pad;
+      tc_pad<RT>(tc_buf_at<RT>(p.off, p.ld), (int)(pad & 0xFFFFu), (int)(pad >> 16), p.ones != 0);
+    }
+  }
   const uint64_t base = A.rng_base ? *A.rng_base : 0ull;
   TcRows<RT> Rw;
 #pragma unroll
@@ -1195,9 +1237,14 @@ __device__ __forceinline__ void tc_body(const TcArgs& A, const int bid) {
 #ifdef IWAE_TC_TRACE
   const int trw = __shfl(tr, 0);       // the traced record, on every lane of wave 0
 #endif
-  for (int s = 0; s < J.nop; ++s) {
+  const int nop = J.nop;
+  TcHot H = tc_hot(J, 0);
+  for (int s = 0; s < nop; ++s) {
     COp& S = J.op[s];
-    const int kind = S.kind;
+    // the next op's record, read once: for this op's hand-over prefetch, then
+    // it becomes the current record (past the last op: a record nothing reads)
+    const TcHot Hn = tc_hot(J, min(s + 1, kTcMaxOps - 1));
+    const int kind = tc_kind(H);
 #ifdef IWAE_TC_TRACE
 #define UTR ((trw >= 0 && wave == 0 && s < 8) ? trw * 8 + s : -1)
 #else
@@ -1216,21 +1263,16 @@ __device__ __forceinline__ void tc_body(const TcArgs& A, const int bid) {
     // image-row ops (the first encoder layer folded into a sample-row job) run on
     // the images of this workgroup's rows
     int r0 = row0, nr = nrows;
-    if (S.img) {
+    if (H.flags & kTcHotImg) {
       r0 = row0 / A.kS;
       nr = (row0 + nrows - 1) / A.kS - r0 + 1;
     }
-    COp* Sn = nullptr;
-    if (s + 1 < J.nop && J.op[s + 1].kind <= TC_LAST_DENSE && !tc_needs_global(J.op[s + 1].kind) &&
-        !J.op[s + 1].gsync)
-      Sn = &J.op[s + 1];
     int nx = 0;             // elementwise op: requests the next op's first units
-    if (RT == 1 && kind > TC_LAST_DENSE && Sn) nx = tc_prefetch(*Sn, F);
+    if (RT == 1 && kind > TC_LAST_DENSE && (H.flags & kTcHotNextDense)) nx = tc_prefetch(Hn, F);
 
-    if (kind <= TC_LAST_DENSE && S.out_buf >= 0) {
-      const int width = kind == TC_SAMPLE ? S.d : S.N;
-      tc_pad<RT>(tc_buf<RT>(J, S.out_buf), width, S.next_k, S.ones != 0);
-    }
+    if (H.pad)
+      tc_pad<RT>(tc_buf_at<RT>(H.out_off, H.out_ld), (int)(H.pad & 0xFFFFu), (int)(H.pad >> 16),
+                 (H.flags & kTcHotOnes) != 0);
 #ifdef IWAE_TC_TRACE
     if (tr >= 0 && s < 32) g_tc_ptrace[(tr * 32 + s) * 4 + 1] = wall_clock64();
 #endif
@@ -1242,8 +1284,8 @@ __device__ __forceinline__ void tc_body(const TcArgs& A, const int bid) {
       case TC_TGRAD:
       case TC_LIN:
       case TC_HEADP:
-        if constexpr (RT == 1) nx = tc_dense<RT, KM>(A, J, S, kind, base, Rw, r0, nr, F, npre, Sn, UTR);
-        else tc_dense2<RT, KM>(A, J, S, kind, base, Rw, r0, nr);
+        if constexpr (RT == 1) nx = tc_dense<RT, KM>(A, S, H, Hn, base, Rw, r0, nr, F, npre, UTR);
+        else tc_dense2<RT, KM>(A, S, H, base, Rw, r0, nr);
         break;
 #ifdef IWAE_TC_SKIPELEM    // timing experiment only
       default: break;
@@ -1260,8 +1302,9 @@ __device__ __forceinline__ void tc_body(const TcArgs& A, const int bid) {
     if (tr >= 0 && 3 + 2 * s < 64) g_tc_trace[tr * 64 + 3 + 2 * s] = wall_clock64();
 #endif
     npre = nx;
-    if (s + 1 < J.nop && !tc_needs_global(J.op[s + 1].kind) && !J.op[s + 1].gsync) tc_lds_barrier();
-    else __syncthreads();
+    if (H.flags & kTcHotFullSync) __syncthreads();
+    else tc_lds_barrier();
+    H = Hn;
   }
   if (!J.logq && !J.logp && !J.bern) return;
   // per-row sums: over the 4 lane groups, then over the waves (fixed order)
