@@ -354,6 +354,44 @@ int iwae_reconstruct(iwae_handle* h, const float* x, int B, const float* const* 
 int iwae_generate(iwae_handle* h, int n, const float* h_top, const float* const* eps, int n_eps,
                   const float* u, float* probs, int ld_probs, float* pixels, int ld_pixels,
                   float* const* h_out, int n_out);
+/* The importance-weighted posterior q_IW of an IWAE (Cremer, Morningstar &
+ * Duvenaud 2017): k samples of q(h|x) reweighted by their self-normalised
+ * importance weights.  For image b, lw[b][s] (s < k) are the log weights of
+ * iwae_nll / iwae_nll_eps (F:327-F:351), m = max_s lw, e_s = exp(lw_s - m),
+ * w~_s = e_s / sum e.  Every pointer is a device pointer; every output is
+ * optional, but not all of them NULL:
+ *   weights [N][k] (image-major): w~;
+ *   logpx [N]: m + log sum e - log k (iwae_nll's value);  ess [N]: (sum e)^2 / sum e^2;
+ *   h_mean[i] [N][d_i], encoder order h_1..h_L (n_mean 0 or L): sum_s w~_s h_{i,s};
+ *   probs [N][ld_probs]: sum_s w~_s p(x | h_{1,s}), p = sigmoid(logit) (1 - 1e-6) +
+ *     1e-7 (F:126) of the ENCODER's h_1 of that sample (the one log w is made
+ *     of; iwae_reconstruct re-draws the lower latents from the prior instead).
+ *     iwae_generate's rules: x_dim <= ld_probs <= 2^22, a multiple of 4, 16-byte
+ *     aligned, columns [x_dim, ld) not written;
+ *   h_sir[i] [N][d_i] (n_sir 0 or L): the latents of ONE resampled sample per
+ *     image (sampling-importance-resampling), s* = min{ j : sum_{s <= j} w~_s >
+ *     u_b } clamped to k - 1, the sum taken in sample order in f32.  u [N]:
+ *     uniforms in [0, 1), or NULL: Philox, layer id 2 * IWAE_MAX_LAYERS + 1,
+ *     row = the image's index in its chunk.
+ * Noise: eps NULL (n_eps 0) is iwae_nll's device stream (same seed, base,
+ * chunk-local rows, one advance per chunk); else L buffers [k][N][d_i] as for
+ * iwae_nll_eps.  Images run in chunks of `chunk` images (0: IWAE_KNOB_NLL_IMGS,
+ * else floor(nll_rows / k), at least 1); a chunk holds ALL k samples of its
+ * images; k <= 2^20.  Per chunk: the NLL's forward and log-sum-exp, a small
+ * weights kernel, then a second, weighted pass over the same rows -- fused
+ * (post_kernel: the rows recomputed in LDS from the same noise, bf16x3) where
+ * the fused NLL kernel applies and the second pass's plan fits 160 KB of LDS;
+ * else, and under iwae_set_precision(h, 0) or iwae_set_path(h, 1), weighted
+ * sums over the rows the layer-wise forward left in memory (there a chunk's
+ * probabilities stay within 256 MB).  A path that does not apply is never an
+ * error.  Deterministic.  Weights, Adam state, captured graphs and engine
+ * plans are untouched; the handle's sticky error (iwae_status) is returned
+ * before any work is enqueued. */
+int iwae_posterior(iwae_handle* h, const float* x, int N, int k, int chunk,
+                   const float* const* eps, int n_eps, const float* u,
+                   float* const* h_mean, int n_mean, float* probs, int ld_probs,
+                   float* const* h_sir, int n_sir,
+                   float* weights, float* ess, float* logpx);
 /* get_NLL_without_inactive_units (F:466-F:494): like iwae_nll / iwae_nll_eps
  * with every sampled h_i multiplied by masks[i] ([dev], d_i floats of 0/1). */
 int iwae_nll_masked(iwae_handle* h, const float* x, int N, int k, const float* const* eps,
@@ -392,8 +430,9 @@ double iwae_workspace_bytes(const iwae_handle* h);
  * bound_kernel launches issued by train steps and forward-only bounds (a
  * captured step counts once, at capture; none where the engine's backward
  * launch computes the bound itself), 16 those of them with more than one
- * workgroup (more than 64 images and more than 8192 sample rows); -1 for an
- * unknown id. */
+ * workgroup (more than 64 images and more than 8192 sample rows); 17 fused
+ * second passes of iwae_posterior (post_kernel launches, one per chunk), 18
+ * its layer-wise second passes (one per chunk); -1 for an unknown id. */
 long long iwae_debug_count(const iwae_handle* h, int what);
 /* Live kernel timing: bracket every launch of one kernel class with HIP events
  * on the handle's stream -- a GEMM class (kind: 0 forward, 1 backward-data,

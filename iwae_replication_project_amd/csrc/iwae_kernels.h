@@ -853,4 +853,70 @@ hipError_t launch_gen_pixels(hipStream_t st, const float* p, int ldp, const floa
                              int ldo, uint64_t seed, const uint64_t* rng_base, int layer);
 hipError_t launch_rng_advance(hipStream_t st, uint64_t* rng_base);
 
+// ------------------------- importance-weighted posterior (iwae_posterior.hip) ----
+// Self-normalised weights of a chunk whose images hold all their k samples:
+// from the per-row log weights (LseArgs' sources: lw, or part / logp / logq)
+// and the image's (m, sum e) left by lse_kernel, w~ = exp(lw - m) / sum e per
+// row, ess = (sum e)^2 / sum e^2 and the SIR index min{ j : sum_{s <= j} w~_s >
+// u } (clamped to k - 1; the sum in sample order) per image.  One workgroup per
+// image, fixed reduction order.
+struct PostWArgs {
+  LseArgs src;               // the rows' log weights, kS, Bimg, run_m / run_s (read)
+  float* wt;                 // out: w~ per row [Bimg * kS] (image-major, as the rows)
+  float* ess;                // out [Bimg], or null
+  int* sir;                  // out [Bimg], or null
+  const float* u;            // uniforms [Bimg], or null: Philox (row = image, layer u_layer, quad 0, first value)
+  uint64_t seed; const uint64_t* rng_base; int u_layer;
+};
+hipError_t launch_post_weights(hipStream_t st, const PostWArgs& a);
+
+// post_kernel: the weighted second pass over a chunk's rows, fused.  A
+// workgroup owns up to 16*RT samples of ONE image (workgroup = image * tiles +
+// tile) and runs the encoder chain after the first layer and the output MLP
+// on them as gen_kernel / mega_fwd_kernel do (split bf16 planes in LDS, bf16x3
+// MFMA, FX weights as the A operand); the sampling and output epilogues
+// multiply by the row's w~ (tail rows: 0), reduce over the rows and write one
+// partial vector [h_1 | .. | h_L | probs] per workgroup; the row whose sample
+// index is the image's SIR index stores its latents.  post_merge_kernel sums an
+// image's partials in tile order.
+enum PoAct { PO_TANH = 1, PO_OUT = 2, PO_SAMPLE = 3 };
+struct PoStage {
+  const __bf16* Whi; const __bf16* Wlo; unsigned W_bytes;
+  int ldk, N;                // FX k extent; output features (heads: 8 * ceil(d / 4) permuted)
+  int in_buf, out_buf;       // LDS buffer ids; out_buf: TANH output, SAMPLE destination latent (-1: the top
+                             // latent, which no stage reads: summed and stored by the epilogue only)
+  int act;                   // PoAct
+  int d, layer;              // SAMPLE: latent width, Philox layer id (= encoder layer)
+  int next_k;                // TANH / SAMPLE: padded K of the reader of out_buf
+  int part_off;              // SAMPLE / OUT: float offset of this stage's sums in the partial vector
+};
+struct PoLaunch {
+  PoStage st[kMgMaxStages]; int nst;
+  int buf_off[kMgMaxBufs], buf_ld[kMgMaxBufs];   // bf16 offset of the hi plane / row stride
+  int stage_buf;                                  // buffer that holds h_1 as f32 [rows][buf_ld] during the prologue
+  int w_off;                                      // LDS float offset of the rows' weights [16 RT]
+  int Bimg, kS, tiles;                            // images of the chunk, samples per image, workgroups per image
+  const float* P0; int ldP0; int d0; int h0_buf; int h0_next_k;   // prologue: h_1 from the image's (mu | zs)
+  uint64_t seed; const uint64_t* rng_base;        // the base pass 1 drew with
+  const float* eps[8]; int eps_N, eps_i0;         // injected noise (MgLaunch's convention) or null
+  const float* wt;                                // w~ per row
+  const int* sir;                                 // SIR index per image, or null
+  float* h_sir[8];                                // the chunk's rows of the callers' [N][d_i] buffers, or null
+  int want_mean;                                  // the latents' sums are formed (probs: the plan has the output stages)
+  float* part; int ld_part;                       // [Bimg * tiles][ld_part]
+};
+hipError_t launch_post(hipStream_t st, const PoLaunch& L, int rt, size_t lds_bytes);
+hipError_t post_setup_attributes();
+// Segment g of the partial vector, columns [off, off + width): out[g][b * ldo + j] = the sum over the
+// image's tiles, in tile order, of part[(b * tiles + t) * ld_part + off + j]
+struct PoMerge {
+  const float* part; int ld_part, tiles, Bimg;
+  int nseg; int off[9], width[9], ldo[9]; float* out[9];
+};
+hipError_t launch_post_merge(hipStream_t st, const PoMerge& a);
+// Weighted sibling of group_mean_kernel: out[b][j] = sum_s wt[b*n + s] * H[b*n + s][j] (sample order);
+// sir given: sel[b][j] = H[b*n + sir[b]][j] as well
+hipError_t launch_group_wsum(hipStream_t st, const float* H, int ldH, int n, int d, int N, const float* wt, float* out,
+                             int ldo, const int* sir, float* sel, int ldsel);
+
 }  // namespace iwae

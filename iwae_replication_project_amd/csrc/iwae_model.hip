@@ -207,6 +207,7 @@ struct Counters {
   long long rb_fwd = 0;              // 13: row-block forward launches (rb_fwd_kernel)
   long long upd = 0;                 // 14: fused update launches issued or recorded by run_update
   long long bound = 0, bound_multi = 0;  // 15, 16: bound_kernel launches (all / with more than one workgroup)
+  long long post = 0, post_lw = 0;       // 17, 18: iwae_posterior second passes: post_kernel launches / layer-wise passes
 };
 
 // row-chain train engine plan (device resident, per shape; iwae_train.hip)
@@ -290,6 +291,9 @@ struct iwae_handle {
   unsigned* tcu_ctr = nullptr;       // tcu_kernel's in-launch counters (UpdWait::ctr; zero between launches)
   unsigned* err_host = nullptr;      // host-mapped error word a kernel sets when an in-launch wait gives up
   unsigned* err_dev = nullptr;       // ... its device address (UpdWait::err)
+  char* post_ws = nullptr;           // iwae_posterior's workspace (weights, SIR indices, partial sums, probabilities,
+  size_t post_ws_bytes = 0;          // a chunk's injected noise): its own allocation, so the arena and what was
+                                     // captured over it stay as they are
   float* loss_slots = nullptr;       // multi-step graphs: step j's loss (kGraphSteps floats), then
                                      // [kGraphSteps, 2 kGraphSteps): where a graph's copy node writes
                                      // when the call wants no losses
@@ -3199,6 +3203,7 @@ iwae_handle* iwae_create(const iwae_config* cfg, int device) {
   if (e == hipSuccess) e = upd_setup_attributes();
   if (e == hipSuccess) e = dw_setup_attributes();
   if (e == hipSuccess) e = gen_setup_attributes();
+  if (e == hipSuccess) e = post_setup_attributes();
   if (e != hipSuccess) {
     g_create_error = std::string("hipFuncSetAttribute failed: ") + hipGetErrorString(e);
     iwae_destroy(h);
@@ -3224,6 +3229,7 @@ void iwae_destroy(iwae_handle* h) {
   if (h->tcu_ctr) (void)hipFree(h->tcu_ctr);
   if (h->err_host) (void)hipHostFree(h->err_host);
   if (h->loss_slots) (void)hipFree(h->loss_slots);
+  if (h->post_ws) (void)hipFree(h->post_ws);
   if (h->nr_units) (void)hipFree(h->nr_units);
   if (h->nrb_units) (void)hipFree(h->nrb_units);
   if (h->nre_units) (void)hipFree(h->nre_units);
@@ -4343,6 +4349,271 @@ int iwae_generate(iwae_handle* h, int n, const float* h_top, const float* const*
   return IWAE_OK;
 }
 
+// ------------------------------------------------ importance-weighted posterior
+// Plan of post_kernel for this model (iwae_posterior.hip).  LDS buffers: the
+// latents some stage reads, h_0 .. h_{L-2} (h_0 alone when L = 1: ids 0 .. nl-1;
+// the top latent of a deeper model is summed and stored by its epilogue and
+// needs none), scratch P (id nl) and Q (id nl+1).
+//   encoder i = 1..L-1:  h_{i-1} -> P (tanh) -> Q (tanh) -> head: sample h_i      (enc)
+//   output MLP:          h_0 -> Q -> P -> Dense(x_dim): weighted probabilities    (out)
+// The buffer widths are those of all these stages whatever the call wants, so
+// whether the plan fits is a property of the model; only the wanted stages are
+// emitted.  The partial vector is [h_1 | .. | h_L | probs].  Row strides of 8
+// mod 16 dwords.  RT from {4, 2, 1}: the largest that fits 160 KB of LDS.
+// False if RT = 1 does not fit.
+static bool post_plan(iwae_handle* h, bool enc, bool out, PoLaunch& G, int& rt, size_t& lds) {
+  const int L = h->L;
+  std::memset(&G, 0, sizeof(G));
+  auto r32 = [](int x) { return (x + 31) & ~31; };
+  const int nl = std::max(1, L - 1), bP = nl, bQ = nl + 1, nb = nl + 2;
+  if (nb > kMgMaxBufs || 3 * L > kMgMaxStages) return false;
+  std::vector<int> width(nb, 0);
+  auto stage = [&](int di, int in, int ob, int act, int next_k, bool emit) -> PoStage* {
+    const DenseL& d = h->dense[di];
+    width[in] = std::max(width[in], d.ldF);
+    if (act == PO_TANH) width[ob] = std::max(width[ob], std::max(d.fout, next_k));
+    if (!emit) return nullptr;
+    PoStage& S = G.st[G.nst++];
+    S.Whi = h->fx_hi + d.fx_off; S.Wlo = h->fx_lo + d.fx_off;
+    S.W_bytes = (unsigned)((h->fx_elems - d.fx_off) * (long long)sizeof(__bf16));
+    S.ldk = d.ldF; S.N = d.fout;
+    S.in_buf = in; S.out_buf = ob; S.act = act; S.next_k = next_k;
+    return &S;
+  };
+  const int d0 = h->enc[0].d;
+  int off = d0;                                  // h_1's sums come first (the prologue's)
+  for (int i = 1; i < L; ++i) {
+    const StochL& E = h->enc[i];
+    stage(E.l1, i - 1, bP, PO_TANH, h->dense[E.l2].ldF, enc);
+    stage(E.l2, bP, bQ, PO_TANH, h->dense[E.head].ldF, enc);
+    if (PoStage* S = stage(E.head, bQ, i < nl ? i : -1, PO_SAMPLE, r32(E.d + 1), enc)) {
+      S->N = 8 * ((E.d + 3) / 4);
+      S->d = E.d; S->layer = i; S->part_off = off;
+    }
+    if (i < nl) width[i] = std::max(width[i], r32(E.d + 1));
+    off += E.d;
+  }
+  stage(h->o1, 0, bQ, PO_TANH, h->dense[h->o2].ldF, out);
+  stage(h->o2, bQ, bP, PO_TANH, h->dense[h->o3].ldF, out);
+  if (PoStage* S = stage(h->o3, bP, -1, PO_OUT, 0, out)) S->part_off = off;
+  G.ld_part = r4(off + h->xdim);
+  G.d0 = d0; G.h0_buf = 0; G.h0_next_k = r32(d0 + 1);
+  width[0] = std::max(width[0], G.h0_next_k);
+  // h_1 as f32 [rows][d0] in the scratch buffer the first stage does not write
+  width[bP] = std::max(width[bP], d0);
+  width[bQ] = std::max(width[bQ], d0);
+  G.stage_buf = (G.nst > 0 && G.st[0].out_buf == bQ) ? bP : bQ;
+  int per_row = 0;                               // bf16 units per row: both planes of every buffer
+  for (int b = 0; b < nb; ++b) {
+    int sdw = (std::max(width[b], 32) + 1) / 2;
+    while (sdw % 16 != 8) ++sdw;
+    G.buf_ld[b] = 2 * sdw;
+    per_row += 2 * G.buf_ld[b];
+  }
+  rt = 0;
+  for (int c : {4, 2, 1})
+    if ((size_t)16 * c * (per_row * sizeof(__bf16) + sizeof(float)) <= 160 * 1024) { rt = c; break; }
+  if (!rt) return false;
+  int o = 0;
+  for (int b = 0; b < nb; ++b) {
+    G.buf_off[b] = o;
+    o += 2 * 16 * rt * G.buf_ld[b];
+  }
+  G.w_off = o / 2;                               // the rows' weights, as floats, behind the buffers
+  lds = (size_t)o * sizeof(__bf16) + (size_t)16 * rt * sizeof(float);
+  return true;
+}
+
+// Two passes per chunk of images (all k samples of an image in one chunk):
+// pass 1 is nll_core's / iwae_nll_eps's forward and launch_lse, unchanged;
+// then the weights kernel, and pass 2 on post_kernel (the rows recomputed from
+// the same noise: the base launch_lse left in rng[1]) or, layer-wise, weighted
+// sums over the h_i and o2 outputs pass 1 left in HBM.
+int iwae_posterior(iwae_handle* h, const float* x, int N, int k, int chunk, const float* const* eps, int n_eps,
+                   const float* u, float* const* h_mean, int n_mean, float* probs, int ld_probs,
+                   float* const* h_sir, int n_sir, float* weights, float* ess, float* logpx) {
+  if (!h) return IWAE_EINVAL;
+  CHK(kernel_status(h));
+  const int L = h->L;
+  if (!x) return fail(h, IWAE_EINVAL, "x is NULL");
+  if (N <= 0 || k <= 0) return fail(h, IWAE_EINVAL, "N and k must be positive");
+  if (k > (1 << 20)) return fail(h, IWAE_EINVAL, "k above 2^20 per image is not supported");
+  auto ptrs_ok = [&](const float* const* a, int n, const char* what) {
+    if (n == 0) return IWAE_OK;
+    if (n != L || !a)
+      return fail(h, IWAE_EINVAL, std::string("expected ") + std::to_string(L) + " " + what + " buffers (one per "
+                                  "stochastic layer), got " + std::to_string(n));
+    for (int i = 0; i < L; ++i)
+      if (!a[i]) return fail(h, IWAE_EINVAL, std::string("NULL ") + what + " buffer");
+    return IWAE_OK;
+  };
+  CHK(ptrs_ok(eps, n_eps, "eps"));
+  CHK(ptrs_ok(h_mean, n_mean, "h_mean"));
+  CHK(ptrs_ok(h_sir, n_sir, "h_sir"));
+  const bool injected = n_eps > 0, want_mean = n_mean > 0, want_sir = n_sir > 0;
+  if (!want_mean && !probs && !want_sir && !weights && !ess && !logpx)
+    return fail(h, IWAE_EINVAL, "every output is NULL");
+  constexpr int kMaxLd = 1 << 22;
+  if (probs && (ld_probs < h->xdim || ld_probs > kMaxLd || (ld_probs & 3) || ((uintptr_t)probs & 15)))
+    return fail(h, IWAE_EINVAL, "probs needs x_dim <= ld <= 2^22, a multiple of 4, 16-byte aligned");
+  const bool second = want_mean || probs || want_sir;
+  // ---- path and chunk
+  MgLaunch MG;
+  PoLaunch PO;
+  int mg_rt = 0, mg_waves = 8, po_rt = 0;
+  size_t mg_lds = 0, po_lds = 0;
+  const bool fused = h->x3 && h->nll_fused && h->path != 1 && !h->masked && mega_plan(h, MG, mg_rt, mg_waves, mg_lds) &&
+                     post_plan(h, want_mean || want_sir, probs != nullptr, PO, po_rt, po_lds);
+  if (chunk <= 0) chunk = h->tune.nll_imgs;
+  long long imgs_ll = chunk > 0 ? chunk : std::max<long long>(1, h->tune.nll_rows / k);
+  const int ldp = r4(h->xdim);                   // layer-wise: the rows' probabilities, at most 256 MB of them
+  if (!fused && probs) imgs_ll = std::min(imgs_ll, std::max<long long>(1, (256LL << 20) / ((long long)k * ldp * 4)));
+  const int imgs = (int)std::min<long long>(imgs_ll, N);
+  if ((long long)imgs * k > (1LL << 30)) return fail(h, IWAE_EINVAL, "chunk * k above 2^30 sample rows");
+  const int rows = imgs * k;
+  const int sup = fused ? std::min(N, imgs * std::max(1, kNllFirstLayerImages / imgs)) : imgs;
+  CHK(ensure_capacity(h, sup, rows, false));
+  if (h->x3) CHK(ensure_wsplit(h));
+  if (fused) CHK(ensure_fx(h));
+  NrLaunch NR;
+  const bool ring = fused && k >= 128 && nring_plan(h, NR);
+  // ---- workspace of its own (floats): w~, SIR indices, then the path's
+  const int tiles = fused ? (k + 16 * po_rt - 1) / (16 * po_rt) : 0;
+  const bool gather = !fused && injected && imgs < N;     // a chunk's [k][n][d] noise, contiguous
+  size_t off = 0;
+  auto take = [&](size_t n) { const size_t o = off; off += (n + 63) & ~size_t(63); return o; };
+  const size_t o_wt = take(weights ? 0 : rows), o_sir = take(want_sir ? imgs : 0);
+  const size_t o_part = take(fused && second ? (size_t)imgs * tiles * PO.ld_part : 0);
+  const size_t o_pw = take(!fused && probs ? (size_t)rows * ldp : 0);
+  size_t o_eps[IWAE_MAX_LAYERS] = {};
+  for (int i = 0; i < L; ++i) o_eps[i] = take(gather ? (size_t)rows * h->enc[i].d : 0);
+  if (off * sizeof(float) > h->post_ws_bytes) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (h->post_ws) (void)hipFree(h->post_ws);
+    h->post_ws = nullptr;
+    h->post_ws_bytes = 0;
+    HIPCHK(hipMalloc(&h->post_ws, off * sizeof(float)));
+    h->post_ws_bytes = off * sizeof(float);
+  }
+  float* ws = reinterpret_cast<float*>(h->post_ws);
+  int* sir = want_sir ? reinterpret_cast<int*>(ws + o_sir) : nullptr;
+  for (int i = 0; i < 8; ++i) MG.eps[i] = NR.eps[i] = PO.eps[i] = (injected && i < L) ? eps[i] : nullptr;
+  MG.eps_N = NR.eps_N = PO.eps_N = N;
+  const size_t wbytes = (size_t)h->xdim * sizeof(float);
+  int u0 = 0;                                    // first image of the current first-layer group (fused)
+  for (int i0 = 0; i0 < N; i0 += imgs) {
+    const int n = std::min(imgs, N - i0);
+    if (!fused || i0 - u0 >= sup || i0 == 0) {
+      u0 = i0;
+      const int ng = std::min(sup, N - i0);
+      HIPCHK(hipMemcpy2DAsync(h->x_in.p, (size_t)h->x_in.ld * sizeof(float), x + (size_t)i0 * h->xdim, wbytes,
+                              wbytes, ng, hipMemcpyDeviceToDevice, h->stream));
+      if (fused) CHK(stoch_fwd(h, h->enc[0], h->x_in, ng, h->eb[0]));
+    }
+    const int io = i0 - u0;                      // the chunk's rows in x_in / eb[0]
+    // ---- pass 1: the chunk's log weights and (m, sum e), as nll_core / iwae_nll_eps
+    Plan P;
+    P.B = n; P.Bimg = n; P.Bsplit = n; P.kS = k;
+    LseArgs a{};
+    if (fused) {
+      MG.rows = n * k; MG.kS = k; MG.eps_i0 = i0; MG.eps_s0 = 0;
+      MG.P0 = h->eb[0].P.p + (size_t)io * h->eb[0].P.ld; MG.ldP0 = h->eb[0].P.ld;
+      MG.x = h->x_in.p + (size_t)io * h->x_in.ld; MG.ldx = h->x_in.ld;
+      MG.seed = h->seed; MG.rng_base = &h->ds->rng[0];
+      MG.lw = h->lw;
+      if (ring) {
+        NR.rows = MG.rows; NR.kS = MG.kS; NR.eps_i0 = i0; NR.eps_s0 = 0;
+        NR.P0 = MG.P0; NR.ldP0 = MG.ldP0; NR.x = MG.x; NR.ldx = MG.ldx;
+        NR.seed = MG.seed; NR.rng_base = MG.rng_base; NR.lw = MG.lw;
+        HIPCHK(launch_nring(h->stream, NR));
+        ++h->count.nring;
+      } else {
+        HIPCHK(launch_mega_fwd(h->stream, MG, mg_rt, mg_waves, mg_lds));
+      }
+      ++h->count.mega;
+      if (injected) ++h->count.mega_eps;
+      a.lw = h->lw;
+    } else {
+      EpsSet E;
+      std::memset(&E, 0, sizeof(E));
+      for (int i = 0; injected && i < L; ++i) {
+        E.a[i] = eps[i];
+        if (gather) {                            // sample s of the chunk's images: n * d floats at (s * N + i0) * d
+          const size_t rb = (size_t)n * h->enc[i].d * sizeof(float);
+          HIPCHK(hipMemcpy2DAsync(ws + o_eps[i], rb, eps[i] + (size_t)i0 * h->enc[i].d,
+                                  (size_t)N * h->enc[i].d * sizeof(float), rb, k, hipMemcpyDeviceToDevice, h->stream));
+          E.a[i] = ws + o_eps[i];
+        }
+      }
+      CHK(forward_core(h, P, E, false));
+    }
+    a.part = h->part; a.ldpart = h->ldpart; a.npart = h->npart; a.logp = h->logp; a.logq = h->logq;
+    a.kS = k; a.Bimg = n; a.run_m = h->run_m; a.run_s = h->run_s; a.init = 1;
+    a.ticket = &h->ds->tickets[1]; a.rng_base = &h->ds->rng[0];
+    HIPCHK(launch_lse(h->stream, a));
+    if (logpx) HIPCHK(launch_lse_final(h->stream, h->run_m, h->run_s, n, logf((float)k), logpx + i0));
+    if (!second && !weights && !ess) continue;
+    // ---- the weights (pass 1 drew with the base now in rng[1])
+    PostWArgs w{};
+    w.src = a;
+    w.wt = weights ? weights + (size_t)i0 * k : ws + o_wt;
+    w.ess = ess ? ess + i0 : nullptr;
+    w.sir = sir;
+    w.u = u ? u + i0 : nullptr;
+    w.seed = h->seed; w.rng_base = &h->ds->rng[1]; w.u_layer = 2 * IWAE_MAX_LAYERS + 1;
+    HIPCHK(launch_post_weights(h->stream, w));
+    if (!second) continue;
+    // ---- pass 2
+    if (fused) {
+      PO.Bimg = n; PO.kS = k; PO.tiles = tiles;
+      PO.P0 = MG.P0; PO.ldP0 = MG.ldP0;
+      PO.seed = h->seed; PO.rng_base = &h->ds->rng[1];
+      PO.eps_i0 = i0;
+      PO.wt = w.wt; PO.sir = sir;
+      for (int i = 0; i < L; ++i) PO.h_sir[i] = want_sir ? h_sir[i] + (size_t)i0 * h->enc[i].d : nullptr;
+      PO.want_mean = want_mean;
+      PO.part = ws + o_part;
+      HIPCHK(launch_post(h->stream, PO, po_rt, po_lds));
+      ++h->count.post;
+      PoMerge M{};
+      M.part = PO.part; M.ld_part = PO.ld_part; M.tiles = tiles; M.Bimg = n;
+      int po = 0;
+      for (int i = 0; i < L; ++i) {
+        const int d = h->enc[i].d;
+        if (want_mean) {
+          M.off[M.nseg] = po; M.width[M.nseg] = d; M.ldo[M.nseg] = d;
+          M.out[M.nseg++] = h_mean[i] + (size_t)i0 * d;
+        }
+        po += d;
+      }
+      if (probs) {
+        M.off[M.nseg] = po; M.width[M.nseg] = h->xdim; M.ldo[M.nseg] = ld_probs;
+        M.out[M.nseg++] = probs + (size_t)i0 * ld_probs;
+      }
+      HIPCHK(launch_post_merge(h->stream, M));
+    } else {
+      ++h->count.post_lw;
+      for (int i = 0; (want_mean || want_sir) && i < L; ++i) {
+        const int d = h->enc[i].d;
+        HIPCHK(launch_group_wsum(h->stream, h->h[i].p, h->h[i].ld, k, d, n, w.wt,
+                                 want_mean ? h_mean[i] + (size_t)i0 * d : nullptr, d, sir,
+                                 want_sir ? h_sir[i] + (size_t)i0 * d : nullptr, d));
+      }
+      if (probs) {
+        // the output MLP's o1 / o2 outputs of these rows are pass 1's (its Bernoulli
+        // GEMM read them from ob.y2): the output Dense again, storing the logits
+        Mat pm;
+        pm.p = ws + o_pw; pm.ld = ldp;
+        CHK(gemm_fwd(h, EPI_STORE, h->ob.y2, n * k, h->dense[h->o3], pm));
+        HIPCHK(launch_bern_probs(h->stream, pm.p, n * k, h->xdim, ldp));
+        HIPCHK(launch_group_wsum(h->stream, pm.p, ldp, k, h->xdim, n, w.wt, probs + (size_t)i0 * ld_probs, ld_probs,
+                                 nullptr, nullptr, 0));
+      }
+    }
+  }
+  return IWAE_OK;
+}
+
 // get_NLL_without_inactive_units (F:466-F:494): k-sample log p(x) with every
 // sampled h_i multiplied by its 0/1 active-unit mask masks[i] ([dev], d_i).
 int iwae_nll_masked(iwae_handle* h, const float* x, int N, int k, const float* const* eps, int n_eps,
@@ -4400,6 +4671,8 @@ long long iwae_debug_count(const iwae_handle* h, int what) {
     case 14: return h->count.upd;
     case 15: return h->count.bound;
     case 16: return h->count.bound_multi;
+    case 17: return h->count.post;
+    case 18: return h->count.post_lw;
     default: return -1;
   }
 }

@@ -718,6 +718,67 @@ class Flexible_Model:
         self._stream.synchronize()
         return outs
 
+    # ------------------------------------------ importance-weighted posterior
+    POSTERIOR_OUTPUTS = ("h_mean", "probs", "h_sir", "weights", "ess", "log_px")
+
+    def posterior(self, x, k, eps=None, u=None, chunk=0, want=POSTERIOR_OUTPUTS):
+        """The importance-weighted posterior q_IW of each image (iwae_posterior):
+        k samples of q(h|x) reweighted by w~ = softmax_k(log w).  Returns a dict of
+        device tensors with the entries named in ``want``:
+
+        - ``"weights"`` [N, k]: w~;  ``"log_px"`` [N]: the k-sample log p(x) of
+          ``log_px``;  ``"ess"`` [N]: the effective sample size 1 / sum_s w~_s^2;
+        - ``"h_mean"``: per stochastic layer [N, d_i], sum_s w~_s h_{i,s};
+        - ``"probs"`` [N, x_dim]: sum_s w~_s p(x | h_{1,s}) with h_1 the encoder's
+          sample (the quantity log w is made of);
+        - ``"h_sir"``: per layer [N, d_i], the latents of one sample per image
+          drawn from q_IW by sampling-importance-resampling: sample
+          min{j : sum_{s<=j} w~_s > u}.
+
+        ``eps``: L arrays [k, N, d_i] (default: device noise, the stream of
+        ``log_px``); ``u``: [N] uniforms in [0, 1) for the resampling (default:
+        device noise); ``chunk``: images per chunk (0: automatic)."""
+        xd = self._x(x)
+        N, k = xd.shape[0], int(k)
+        want = (want,) if isinstance(want, str) else tuple(want)
+        bad = [w for w in want if w not in self.POSTERIOR_OUTPUTS]
+        if bad or not want:
+            raise ValueError(f"want must name some of {self.POSTERIOR_OUTPUTS}, got {want}")
+        if N <= 0 or k <= 0:
+            raise ValueError("N and k must be positive")
+        if k > 1 << 20:
+            raise ValueError("k above 2^20 per image is not supported")
+        arr, n, keep = self._eps(eps, N, k)
+        ut = None
+        if u is not None:
+            with torch.cuda.stream(self._stream):
+                ut = torch.as_tensor(u).to(device=self.device, dtype=torch.float32).contiguous()
+            if tuple(ut.shape) != (N,):
+                raise ValueError(f"u must be [N={N}], got {tuple(ut.shape)}")
+        dims = self.n_latent_encoder
+        with torch.cuda.stream(self._stream):
+            ld = (self.x_dim + 3) // 4 * 4
+            hm = [torch.empty(N, d, device=self.device) for d in dims] if "h_mean" in want else []
+            hs = [torch.empty(N, d, device=self.device) for d in dims] if "h_sir" in want else []
+            probs = torch.empty(N, ld, device=self.device) if "probs" in want else None
+            wts = torch.empty(N, k, device=self.device) if "weights" in want else None
+            ess = torch.empty(N, device=self.device) if "ess" in want else None
+            lpx = torch.empty(N, device=self.device) if "log_px" in want else None
+        marr, nm = _lib.fptr_array(hm)
+        sarr, ns = _lib.fptr_array(hs)
+        self._call(self._lib.iwae_posterior(self._h, _lib.fptr(xd), N, k, int(chunk), arr, n, _lib.fptr(ut), marr, nm,
+                                            _lib.fptr(probs), ld if probs is not None else 0, sarr, ns,
+                                            _lib.fptr(wts), _lib.fptr(ess), _lib.fptr(lpx)))
+        self._stream.synchronize()
+        out = {"h_mean": hm, "h_sir": hs, "probs": probs[:, :self.x_dim] if probs is not None else None,
+               "weights": wts, "ess": ess, "log_px": lpx}
+        return {name: out[name] for name in want}
+
+    def reconstructed_x_probs_iw(self, x, k, eps=None):
+        """Importance-weighted reconstruction [N, x_dim]: sum_s w~_s p(x | h_{1,s})
+        over k samples of q(h|x) (``posterior(...)["probs"]``)."""
+        return self.posterior(x, k, eps=eps, want=("probs",))["probs"]
+
     def get_levels_of_units_activity(self, x, n_samples, eps=None):
         """F:264-F:281: per stochastic layer, the variance over the batch of
         E_q[h_i] and the PCA eigenvalues of those means (host float64 on the
