@@ -392,6 +392,45 @@ int iwae_posterior(iwae_handle* h, const float* x, int N, int k, int chunk,
                    float* const* h_mean, int n_mean, float* probs, int ld_probs,
                    float* const* h_sir, int n_sir,
                    float* weights, float* ess, float* logpx);
+/* Imputation of missing pixels (Mattei & Frellsen 2019, MIWAE): iwae_posterior
+ * under the likelihood of the OBSERVED pixels alone.  mask [N][x_dim] (device,
+ * required: NULL is IWAE_EINVAL, an all-observed call is iwae_posterior's):
+ * non-zero = observed, 0 = missing.  The encoder sees x (.) mask (zero
+ * imputation); missing entries of x are selected away, never multiplied, so
+ * any value there (NaN, Inf) gives the bits a 0 gives.  The log weights are
+ *   lw[b][s] = log p(h) + sum_j [mask_bj != 0] log Bern(x_bj | p_j(h_{1,s}))
+ *              - log q(h | x (.) mask),   p = sigmoid(logit) (1 - 1e-6) + 1e-7 (F:126),
+ * and weights, ess, logpx (the k-sample estimate of log p(x_obs)), h_mean and
+ * h_sir are iwae_posterior's, formed from them; N, k, chunk, eps, n_eps, u,
+ * n_mean, n_sir follow its conventions (k <= 2^20, eps [k][N][d_i], u [N]).
+ *   x_mean [N][ld_mean]: the single imputation: x_bj where observed (copied bit
+ *     for bit), sum_s w~_s p_j(h_{1,s}) where missing;
+ *   x_draw [N][ld_draw]: one multiple-imputation draw: x_bj where observed,
+ *     (u_pix[b][j] < p_j(h_{1,s*})) as 0.0 / 1.0 where missing, s* the SIR
+ *     sample of h_sir (the same u_b, whether or not h_sir is asked for).
+ *     u_pix [N][x_dim]: uniforms in [0, 1), or NULL: Philox, layer id
+ *     2 * IWAE_MAX_LAYERS + 2, row = the image's index in its chunk, column
+ *     quad j / 4 as the counter's group and j % 4 the value within it
+ *     (iwae_generate's pixel layout), the base the chunk's first pass drew with.
+ * Both follow iwae_generate's ld rules (x_dim <= ld <= 2^22, a multiple of 4,
+ * 16-byte aligned; columns [x_dim, ld) not written).  Every output is optional,
+ * not all of them NULL.  Repeat the call with another u / u_pix for more draws.
+ * Per chunk: the images staged twice by select (mask ? x : 0 for the encoder,
+ * mask ? x : -1 for the likelihood), the first pass on the masked
+ * instantiation of mega_fwd_kernel where iwae_posterior's fused path applies
+ * (the weight-ring kernel is not used, whatever k) or, elsewhere and under
+ * iwae_set_precision(h, 0) / iwae_set_path(h, 1), layer-wise with the output
+ * Dense's logits stored (at most 256 MB per chunk) and a masked row sum; then
+ * iwae_posterior's weights kernel and second pass unchanged, and the fill /
+ * draw epilogues (the draw's output MLP runs on the layer-wise GEMMs: N rows).
+ * A path that does not apply is never an error.  Deterministic.  Weights, Adam
+ * state, captured graphs and engine plans are untouched; the handle's sticky
+ * error (iwae_status) is returned before any work is enqueued. */
+int iwae_impute(iwae_handle* h, const float* x, const float* mask, int N, int k, int chunk,
+                const float* const* eps, int n_eps, const float* u, const float* u_pix,
+                float* x_mean, int ld_mean, float* x_draw, int ld_draw,
+                float* const* h_mean, int n_mean, float* const* h_sir, int n_sir,
+                float* weights, float* ess, float* logpx);
 /* get_NLL_without_inactive_units (F:466-F:494): like iwae_nll / iwae_nll_eps
  * with every sampled h_i multiplied by masks[i] ([dev], d_i floats of 0/1). */
 int iwae_nll_masked(iwae_handle* h, const float* x, int N, int k, const float* const* eps,
@@ -432,7 +471,10 @@ double iwae_workspace_bytes(const iwae_handle* h);
  * launch computes the bound itself), 16 those of them with more than one
  * workgroup (more than 64 images and more than 8192 sample rows); 17 fused
  * second passes of iwae_posterior (post_kernel launches, one per chunk), 18
- * its layer-wise second passes (one per chunk); -1 for an unknown id. */
+ * its layer-wise second passes (one per chunk; both also count iwae_impute's
+ * second passes); 19 masked fused first passes of iwae_impute (masked
+ * mega_fwd_kernel launches, one per chunk; not counted under 0), 20 its
+ * masked layer-wise first passes (one per chunk); -1 for an unknown id. */
 long long iwae_debug_count(const iwae_handle* h, int what);
 /* Live kernel timing: bracket every launch of one kernel class with HIP events
  * on the handle's stream -- a GEMM class (kind: 0 forward, 1 backward-data,

@@ -98,6 +98,8 @@ SIGNATURES = {
     "iwae_generate": (c_int, [H, c_int, FP, FPP, c_int, FP, FP, c_int, FP, c_int, FPP, c_int]),
     "iwae_posterior": (c_int, [H, FP, c_int, c_int, c_int, FPP, c_int, FP, FPP, c_int, FP, c_int, FPP, c_int,
                                FP, FP, FP]),
+    "iwae_impute": (c_int, [H, FP, FP, c_int, c_int, c_int, FPP, c_int, FP, FP, FP, c_int, FP, c_int, FPP, c_int,
+                            FPP, c_int, FP, FP, FP]),
     "iwae_nll_masked": (c_int, [H, FP, c_int, c_int, FPP, c_int, FPP, c_int, FP]),
     "iwae_debug_gemm": (c_int, [H, FP, c_int, FP, c_int, FP, c_int, c_int, c_int, c_int]),
     "iwae_workspace_bytes": (c_double, [H]),

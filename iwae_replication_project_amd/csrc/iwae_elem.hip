@@ -742,14 +742,7 @@ __global__ __launch_bounds__(256) void gen_pixels_kernel(const float* p, int ldp
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long long)n * ng) return;
   const int r = (int)(i / ng), g = (int)(i - (long long)r * ng);
-  float4 u4;
-  if (u) {
-    const float* s = u + (size_t)r * xdim;
-    const int j = 4 * g;
-    u4 = make_float4(s[j], s[min(j + 1, xdim - 1)], s[min(j + 2, xdim - 1)], s[min(j + 3, xdim - 1)]);
-  } else {
-    u4 = philox_uniform4(seed, *rng_base, (unsigned)r, (unsigned)layer, (unsigned)g);
-  }
+  const float4 u4 = pixel_uniform4(u, r, g, xdim, seed, rng_base, layer);
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int j = 4 * g + q;

@@ -121,6 +121,18 @@ __device__ __forceinline__ float4 philox_uniform4(uint64_t seed, uint64_t base, 
   return make_float4(((float)c0 + 0.5f) * k2m32, ((float)c1 + 0.5f) * k2m32, ((float)c2 + 0.5f) * k2m32,
                      ((float)c3 + 0.5f) * k2m32);
 }
+// The four uniforms of pixel columns 4g .. 4g + 3 of row r: the caller's [rows][xdim] buffer (columns
+// past xdim repeat the last), else Philox (row, layer, group g) -- the one pixel layout of gen_kernel,
+// gen_pixels_kernel and impute_draw_kernel.
+__device__ __forceinline__ float4 pixel_uniform4(const float* __restrict__ u, int r, int g, int xdim, uint64_t seed,
+                                                 const uint64_t* rng_base, int layer) {
+  if (u) {
+    const float* s = u + (size_t)r * xdim;
+    const int j = 4 * g;
+    return make_float4(s[j], s[min(j + 1, xdim - 1)], s[min(j + 2, xdim - 1)], s[min(j + 3, xdim - 1)]);
+  }
+  return philox_uniform4(seed, *rng_base, (unsigned)r, (unsigned)layer, (unsigned)g);
+}
 __device__ __forceinline__ float f4_at(const float4& v, int q) {
   return q == 0 ? v.x : q == 1 ? v.y : q == 2 ? v.z : v.w;
 }
@@ -560,6 +572,8 @@ struct MgLaunch {
   float* lw;                                      // out: log w per row
 };
 hipError_t launch_mega_fwd(hipStream_t st, const MgLaunch& L, int rt, int waves, size_t lds_bytes);
+// The pixel-masked variant (iwae_impute): L.x is the staged copy with -1 at the missing pixels
+hipError_t launch_mega_fwd_masked(hipStream_t st, const MgLaunch& L, int rt, int waves, size_t lds_bytes);
 hipError_t mega_setup_attributes();
 
 // ------------------------------- weight-ring k-sample forward (NLL) ----
@@ -918,5 +932,28 @@ hipError_t launch_post_merge(hipStream_t st, const PoMerge& a);
 // sir given: sel[b][j] = H[b*n + sir[b]][j] as well
 hipError_t launch_group_wsum(hipStream_t st, const float* H, int ldH, int n, int d, int N, const float* wt, float* out,
                              int ldo, const int* sir, float* sel, int ldsel);
+
+
+// ---------------------- imputation of missing pixels (iwae_impute.hip) ----
+// mask [n][xdim]: non-zero = observed.  Every kernel selects by the mask, so a
+// missing entry of x (NaN and Inf included) never reaches an output.
+// Staging: x_in[r][j] = mask ? x : 0 (the encoder's input; columns past xdim,
+// the ones column among them, are left alone) and, when xm is given, xm[r][j] =
+// mask ? x : -1 for j < xdim, 0 for xdim <= j < ld_m (the masked
+// mega_fwd_kernel's pixels).
+hipError_t launch_impute_stage(hipStream_t st, const float* x, const float* mask, int n, int xdim, float* x_in,
+                               int ld_in, float* xm, int ld_m);
+// Layer-wise first pass: part[r] = (sum_j [mask] x log p + (1 - x) log(1 - p), 0, 0, 0) of the row's logits
+// Z[r][0..xdim) (row r = image r / kS), p = sigmoid(z) (1 - 1e-6) + 1e-7 (F:126), one wave per row in a fixed
+// order; to_probs: the logits are replaced by p (bern_probs_kernel's value) for the second pass.
+hipError_t launch_impute_rowsum(hipStream_t st, float* Z, int ldz, int rows, int kS, const float* x_in, int ld_in,
+                                const float* mask, int xdim, float* part, int to_probs);
+// out[b][j] = mask ? x : out[b][j] (the weighted probabilities already there), j < xdim
+hipError_t launch_impute_fill(hipStream_t st, const float* x, const float* mask, int n, int xdim, float* out, int ldo);
+// out[b][j] = mask ? x : (u < p[b][j]) as 0.0 / 1.0; u: [n][xdim] or null: Philox uniforms (row b, `layer`,
+// column quad j / 4, value j % 4: gen_kernel's layout)
+hipError_t launch_impute_draw(hipStream_t st, const float* x, const float* mask, const float* p, int ldp,
+                              const float* u, int n, int xdim, float* out, int ldo, uint64_t seed,
+                              const uint64_t* rng_base, int layer);
 
 }  // namespace iwae

@@ -212,8 +212,11 @@ struct MgRows {
 // four of them are multiplied (>= 1e-28) before one log2.  Both forms sum
 // log2 terms; the row total is scaled by ln 2 once.
 constexpr float kBernOff0 = 9.1327896e-7f;   // 1 - 0.999999f - 1e-7f (f32 constants, F:126)
-
-template <int RT>
+//
+// MASK (iwae_impute): xv is the staged copy whose missing pixels hold -1
+// (impute_stage_kernel).  A negative pixel is the factor 1 of the binarised
+// product and the term 0 of the fractional sum: the pixel leaves log p(x|h).
+template <int RT, bool MASK>
 __device__ __forceinline__ void mg_bern(const MgLaunch& L, const MgStage& S, int t, const mg_f32x4 (&acc)[RT],
                                         const float4 (&xv)[RT], MgRows<RT>& R) {
   const int g = (threadIdx.x & 63) >> 4;
@@ -221,8 +224,12 @@ __device__ __forceinline__ void mg_bern(const MgLaunch& L, const MgStage& S, int
   bool bin = true;
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt)
-    bin = bin && (xv[rt].x == 0.f || xv[rt].x == 1.f) && (xv[rt].y == 0.f || xv[rt].y == 1.f) &&
-          (xv[rt].z == 0.f || xv[rt].z == 1.f) && (xv[rt].w == 0.f || xv[rt].w == 1.f);
+    if (MASK)
+      bin = bin && (xv[rt].x <= 0.f || xv[rt].x == 1.f) && (xv[rt].y <= 0.f || xv[rt].y == 1.f) &&
+            (xv[rt].z <= 0.f || xv[rt].z == 1.f) && (xv[rt].w <= 0.f || xv[rt].w == 1.f);
+    else
+      bin = bin && (xv[rt].x == 0.f || xv[rt].x == 1.f) && (xv[rt].y == 0.f || xv[rt].y == 1.f) &&
+            (xv[rt].z == 0.f || xv[rt].z == 1.f) && (xv[rt].w == 0.f || xv[rt].w == 1.f);
   if (__all(bin)) {
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
@@ -230,11 +237,11 @@ __device__ __forceinline__ void mg_bern(const MgLaunch& L, const MgStage& S, int
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const float x = f4_at(xv[rt], i);
-        const bool one = x != 0.f;
+        const bool one = MASK ? x > 0.f : x != 0.f;
         const float z = one ? acc[rt][i] : -acc[rt][i];
         const float s = frcp(1.f + fexp(-z));
         const float p = __builtin_fmaf(s, kProbScale, one ? kProbShift : kBernOff0);
-        prod *= (f0 + i < S.N) ? p : 1.f;
+        prod *= (f0 + i < S.N && !(MASK && x < 0.f)) ? p : 1.f;
       }
       R.l2[rt] += __builtin_amdgcn_logf(prod);
     }
@@ -251,7 +258,7 @@ __device__ __forceinline__ void mg_bern(const MgLaunch& L, const MgStage& S, int
         const float p1 = __builtin_fmaf(sp, kProbScale, kProbShift);
         const float p0 = __builtin_fmaf(e * sp, kProbScale, kBernOff0);
         const float v = x * __builtin_amdgcn_logf(p1) + (1.f - x) * __builtin_amdgcn_logf(p0);
-        R.l2[rt] += (f0 + i < S.N) ? v : 0.f;
+        R.l2[rt] += (f0 + i < S.N && !(MASK && x < 0.f)) ? v : 0.f;
       }
   }
 }
@@ -378,7 +385,7 @@ __device__ __forceinline__ void mg_lds_barrier() {
 
 // One column tile: x operands (Bernoulli stage) requested first, MFMAs over
 // the whole K, epilogue.
-template <int RT, int ACT>
+template <int RT, int ACT, bool MASK>
 __device__ __forceinline__ void mg_tile(const MgLaunch& L, const MgStage& S, const MgBuf& IN, const MgBuf& OUT,
                                         int t, MgFrag& f, __amdgpu_buffer_rsrc_t ph, __amdgpu_buffer_rsrc_t pl,
                                         bool pf, unsigned pf_vb, int pf_ns, uint64_t base, MgRows<RT>& R) {
@@ -395,14 +402,14 @@ __device__ __forceinline__ void mg_tile(const MgLaunch& L, const MgStage& S, con
   for (int rt = 0; rt < RT; ++rt) acc[rt] = (mg_f32x4){0.f, 0.f, 0.f, 0.f};
   mg_mma<RT>(IN, 0, min(MG_KS, S.ldk >> 5), f, acc, ph, pl, pf, pf_vb, pf_ns);
   if (ACT == MG_TANH) mg_store_tanh<RT>(OUT, S, t, acc);
-  else if (ACT == MG_BERN) mg_bern<RT>(L, S, t, acc, xv, R);
+  else if (ACT == MG_BERN) mg_bern<RT, MASK>(L, S, t, acc, xv, R);
   else mg_head<RT, ACT>(L, S, t, base, acc, R);
 }
 
 // One Dense stage.  Wave w owns the column tiles w, w + 8, ...; when the whole
 // K fits one fetch (ldk <= 256) the first MG_PF steps of the wave's next tile
 // are requested during the current tile's MFMAs (mg_mma).
-template <int RT, int ACT, int NW>
+template <int RT, int ACT, int NW, bool MASK>
 __device__ __forceinline__ void mg_dense(const MgLaunch& L, const MgStage& S, uint64_t base, MgRows<RT>& R) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int ntile = (S.N + 15) >> 4;
@@ -422,7 +429,7 @@ __device__ __forceinline__ void mg_dense(const MgLaunch& L, const MgStage& S, ui
       const unsigned vb = mg_frag_base(S, t, 0);
 #pragma unroll
       for (int u = MG_PF; u < MG_KS; ++u) mg_fetch_step(rh, rl, vb, u, ns, f);
-      mg_tile<RT, ACT>(L, S, IN, OUT, t, f, rh, rl, tn < ntile, mg_frag_base(S, tn, 0), ns, base, R);
+      mg_tile<RT, ACT, MASK>(L, S, IN, OUT, t, f, rh, rl, tn < ntile, mg_frag_base(S, tn, 0), ns, base, R);
     }
   } else {
     // wide K: 256-deep fetches, no prefetch across tiles
@@ -444,7 +451,7 @@ __device__ __forceinline__ void mg_dense(const MgLaunch& L, const MgStage& S, ui
         mg_mma<RT>(IN, k0, min(MG_KS, (S.ldk - k0) >> 5), f, acc, rh, rl, false, kOOB, 0);
       }
       if (ACT == MG_TANH) mg_store_tanh<RT>(OUT, S, t, acc);
-      else if (ACT == MG_BERN) mg_bern<RT>(L, S, t, acc, xv, R);
+      else if (ACT == MG_BERN) mg_bern<RT, MASK>(L, S, t, acc, xv, R);
       else mg_head<RT, ACT>(L, S, t, base, acc, R);
     }
   }
@@ -453,7 +460,11 @@ __device__ __forceinline__ void mg_dense(const MgLaunch& L, const MgStage& S, ui
 // NW = 8: one 64-row workgroup per CU (LDS-bound).  NW = 4 with RT = 2: two
 // independent 32-row workgroups per CU, whose weight waits, MFMA loops and
 // epilogues interleave instead of running in lock step behind one barrier.
-template <int RT, int NW>
+// MASK: the pixel-masked likelihood of iwae_impute; L.x is then the staged copy
+// with -1 at the missing pixels (the first layer, run ahead of this kernel,
+// read the copy with 0 there).  A compile-time variant: the unmasked
+// instantiations are what they were.
+template <int RT, int NW, bool MASK>
 __global__ __launch_bounds__(NW * 64) void mega_fwd_kernel(MgLaunch L) {
   constexpr int R = 16 * RT;
   constexpr int TPR = (NW * 64) / R;            // threads per row in the prologue
@@ -553,10 +564,10 @@ __global__ __launch_bounds__(NW * 64) void mega_fwd_kernel(MgLaunch L) {
     if (S.act == MG_TANH) mg_pad<RT, NW>(mg_buf<RT>(L, S.out_buf), S.N, S.next_k);
     else if (S.act == MG_SAMPLE) mg_pad<RT, NW>(mg_buf<RT>(L, S.out_buf), S.d, S.next_k);
     switch (S.act) {     // one instantiation per stage kind: one epilogue per tile loop
-      case MG_TANH: mg_dense<RT, MG_TANH, NW>(L, S, base, Rw); break;
-      case MG_SAMPLE: mg_dense<RT, MG_SAMPLE, NW>(L, S, base, Rw); break;
-      case MG_PRIOR: mg_dense<RT, MG_PRIOR, NW>(L, S, base, Rw); break;
-      default: mg_dense<RT, MG_BERN, NW>(L, S, base, Rw); break;
+      case MG_TANH: mg_dense<RT, MG_TANH, NW, MASK>(L, S, base, Rw); break;
+      case MG_SAMPLE: mg_dense<RT, MG_SAMPLE, NW, MASK>(L, S, base, Rw); break;
+      case MG_PRIOR: mg_dense<RT, MG_PRIOR, NW, MASK>(L, S, base, Rw); break;
+      default: mg_dense<RT, MG_BERN, NW, MASK>(L, S, base, Rw); break;
     }
     MG_TRACE(3 + 3 * s)
     mg_lds_barrier();
@@ -585,28 +596,37 @@ __global__ __launch_bounds__(NW * 64) void mega_fwd_kernel(MgLaunch L) {
   MG_TRACE(127)
 }
 
-hipError_t launch_mega_fwd(hipStream_t st, const MgLaunch& L, int rt, int waves, size_t lds_bytes) {
+template <bool MASK>
+static hipError_t launch_mega_fwd_t(hipStream_t st, const MgLaunch& L, int rt, int waves, size_t lds_bytes) {
   if (L.rows <= 0) return hipSuccess;
   const int R = 16 * rt;
   const dim3 grid((L.rows + R - 1) / R), block(waves * 64);
   if (waves == 4) {
     if (rt != 2) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((mega_fwd_kernel<2, 4>), grid, block, lds_bytes, st, L);
+    hipLaunchKernelGGL((mega_fwd_kernel<2, 4, MASK>), grid, block, lds_bytes, st, L);
     return hipGetLastError();
   }
   if (waves != MG_WAVES) return hipErrorInvalidValue;
   switch (rt) {
-    case 1: hipLaunchKernelGGL((mega_fwd_kernel<1, MG_WAVES>), grid, block, lds_bytes, st, L); break;
-    case 2: hipLaunchKernelGGL((mega_fwd_kernel<2, MG_WAVES>), grid, block, lds_bytes, st, L); break;
-    case 4: hipLaunchKernelGGL((mega_fwd_kernel<4, MG_WAVES>), grid, block, lds_bytes, st, L); break;
+    case 1: hipLaunchKernelGGL((mega_fwd_kernel<1, MG_WAVES, MASK>), grid, block, lds_bytes, st, L); break;
+    case 2: hipLaunchKernelGGL((mega_fwd_kernel<2, MG_WAVES, MASK>), grid, block, lds_bytes, st, L); break;
+    case 4: hipLaunchKernelGGL((mega_fwd_kernel<4, MG_WAVES, MASK>), grid, block, lds_bytes, st, L); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
+hipError_t launch_mega_fwd(hipStream_t st, const MgLaunch& L, int rt, int waves, size_t lds_bytes) {
+  return launch_mega_fwd_t<false>(st, L, rt, waves, lds_bytes);
+}
+hipError_t launch_mega_fwd_masked(hipStream_t st, const MgLaunch& L, int rt, int waves, size_t lds_bytes) {
+  return launch_mega_fwd_t<true>(st, L, rt, waves, lds_bytes);
+}
 
 hipError_t mega_setup_attributes() {
-  const void* fns[] = {(const void*)mega_fwd_kernel<1, MG_WAVES>, (const void*)mega_fwd_kernel<2, MG_WAVES>,
-                       (const void*)mega_fwd_kernel<4, MG_WAVES>, (const void*)mega_fwd_kernel<2, 4>};
+  const void* fns[] = {(const void*)mega_fwd_kernel<1, MG_WAVES, false>, (const void*)mega_fwd_kernel<2, MG_WAVES, false>,
+                       (const void*)mega_fwd_kernel<4, MG_WAVES, false>, (const void*)mega_fwd_kernel<2, 4, false>,
+                       (const void*)mega_fwd_kernel<1, MG_WAVES, true>, (const void*)mega_fwd_kernel<2, MG_WAVES, true>,
+                       (const void*)mega_fwd_kernel<4, MG_WAVES, true>, (const void*)mega_fwd_kernel<2, 4, true>};
   for (const void* f : fns) {
     const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;

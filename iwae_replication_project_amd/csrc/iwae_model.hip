@@ -208,6 +208,7 @@ struct Counters {
   long long upd = 0;                 // 14: fused update launches issued or recorded by run_update
   long long bound = 0, bound_multi = 0;  // 15, 16: bound_kernel launches (all / with more than one workgroup)
   long long post = 0, post_lw = 0;       // 17, 18: iwae_posterior second passes: post_kernel launches / layer-wise passes
+  long long imp = 0, imp_lw = 0;         // 19, 20: iwae_impute first passes: masked mega_fwd_kernel launches / layer-wise passes
 };
 
 // row-chain train engine plan (device resident, per shape; iwae_train.hip)
@@ -810,11 +811,9 @@ static int encoder_fwd(iwae_handle* h, const Plan& P, const EpsSet& E, bool trai
   return IWAE_OK;
 }
 
-static int forward_core(iwae_handle* h, const Plan& P, const EpsSet& E, bool train) {
-  if (use_fused(h, P)) return fused_forward(h, P, E, train);
-  const int L = h->L, kS = P.kS, M = P.Bimg * kS;
-  CHK(encoder_fwd(h, P, E, train));
-  // prior log p(h) (F:134-F:142)
+// Layer-wise prior log p(h) of the M sampled rows into h->logp (F:134-F:142)
+static int prior_fwd(iwae_handle* h, int M) {
+  const int L = h->L;
   {
     GaussArgs g{};
     g.d = h->enc[L - 1].d; g.H = h->h[L - 1].p; g.ldH = h->h[L - 1].ld;
@@ -829,6 +828,14 @@ static int forward_core(iwae_handle* h, const Plan& P, const EpsSet& E, bool tra
     g.out = h->logp; g.accumulate = 1; g.M = M;
     HIPCHK(launch_gauss_fwd(h->stream, 1, g));
   }
+  return IWAE_OK;
+}
+
+static int forward_core(iwae_handle* h, const Plan& P, const EpsSet& E, bool train) {
+  if (use_fused(h, P)) return fused_forward(h, P, E, train);
+  const int kS = P.kS, M = P.Bimg * kS;
+  CHK(encoder_fwd(h, P, E, train));
+  CHK(prior_fwd(h, M));
   // output MLP + Bernoulli (F:89-F:96, F:123-F:129)
   CHK(gemm_fwd(h, EPI_TANH, h->h[0], M, h->dense[h->o1], h->ob.y1));
   CHK(gemm_fwd(h, EPI_TANH, h->ob.y1, M, h->dense[h->o2], h->ob.y2));
@@ -843,6 +850,23 @@ static int forward_core(iwae_handle* h, const Plan& P, const EpsSet& E, bool tra
     if (!train) { gm.p = nullptr; gm.ld = 0; }
     CHK(gemm_fwd(h, EPI_BERN, h->ob.y2, M, h->dense[h->o3], gm, ex));
   }
+  return IWAE_OK;
+}
+
+// Layer-wise first pass of iwae_impute: forward_core's encoder and prior on
+// x_in (already mask ? x : 0), the output Dense storing its logits in Z, then
+// the masked Bernoulli row sums where lse_kernel reads a row's likelihood term
+// ([rows][4], one partial).  No GEMM instantiation of the train step changes.
+static int impute_layerwise_fwd(iwae_handle* h, const Plan& P, const EpsSet& E, const float* mask, Mat Z, float* part,
+                                bool to_probs) {
+  const int M = P.Bimg * P.kS;
+  CHK(encoder_fwd(h, P, E, false));
+  CHK(prior_fwd(h, M));
+  CHK(gemm_fwd(h, EPI_TANH, h->h[0], M, h->dense[h->o1], h->ob.y1));
+  CHK(gemm_fwd(h, EPI_TANH, h->ob.y1, M, h->dense[h->o2], h->ob.y2));
+  CHK(gemm_fwd(h, EPI_STORE, h->ob.y2, M, h->dense[h->o3], Z));
+  HIPCHK(launch_impute_rowsum(h->stream, Z.p, Z.ld, M, P.kS, h->x_in.p, h->x_in.ld, mask, h->xdim, part,
+                              to_probs ? 1 : 0));
   return IWAE_OK;
 }
 
@@ -4429,11 +4453,18 @@ static bool post_plan(iwae_handle* h, bool enc, bool out, PoLaunch& G, int& rt, 
 // then the weights kernel, and pass 2 on post_kernel (the rows recomputed from
 // the same noise: the base launch_lse left in rng[1]) or, layer-wise, weighted
 // sums over the h_i and o2 outputs pass 1 left in HBM.
-int iwae_posterior(iwae_handle* h, const float* x, int N, int k, int chunk, const float* const* eps, int n_eps,
-                   const float* u, float* const* h_mean, int n_mean, float* probs, int ld_probs,
-                   float* const* h_sir, int n_sir, float* weights, float* ess, float* logpx) {
-  if (!h) return IWAE_EINVAL;
-  CHK(kernel_status(h));
+//
+// With a pixel mask (iwae_impute) pass 1 is the masked one -- the chunk's
+// images staged by select, then the masked mega_fwd_kernel (never the weight
+// ring) or impute_layerwise_fwd, whose stored logits become the second pass's
+// probabilities -- pass 2 is the same, and two small epilogues follow: probs
+// (the caller's x_mean) keeps x at the observed pixels, and x_draw is drawn
+// from p(x | h_1 of the resampled sample) on the layer-wise GEMMs (n rows).
+// mask == NULL is iwae_posterior launch for launch.
+static int posterior_core(iwae_handle* h, const float* x, const float* mask, int N, int k, int chunk,
+                          const float* const* eps, int n_eps, const float* u, const float* u_pix,
+                          float* const* h_mean, int n_mean, float* probs, int ld_probs, float* x_draw, int ld_draw,
+                          float* const* h_sir, int n_sir, float* weights, float* ess, float* logpx) {
   const int L = h->L;
   if (!x) return fail(h, IWAE_EINVAL, "x is NULL");
   if (N <= 0 || k <= 0) return fail(h, IWAE_EINVAL, "N and k must be positive");
@@ -4450,13 +4481,19 @@ int iwae_posterior(iwae_handle* h, const float* x, int N, int k, int chunk, cons
   CHK(ptrs_ok(eps, n_eps, "eps"));
   CHK(ptrs_ok(h_mean, n_mean, "h_mean"));
   CHK(ptrs_ok(h_sir, n_sir, "h_sir"));
-  const bool injected = n_eps > 0, want_mean = n_mean > 0, want_sir = n_sir > 0;
-  if (!want_mean && !probs && !want_sir && !weights && !ess && !logpx)
+  const bool injected = n_eps > 0, want_mean = n_mean > 0, want_sir = n_sir > 0, draw = x_draw != nullptr;
+  if (!want_mean && !probs && !draw && !want_sir && !weights && !ess && !logpx)
     return fail(h, IWAE_EINVAL, "every output is NULL");
   constexpr int kMaxLd = 1 << 22;
-  if (probs && (ld_probs < h->xdim || ld_probs > kMaxLd || (ld_probs & 3) || ((uintptr_t)probs & 15)))
-    return fail(h, IWAE_EINVAL, "probs needs x_dim <= ld <= 2^22, a multiple of 4, 16-byte aligned");
-  const bool second = want_mean || probs || want_sir;
+  auto ld_ok = [&](const float* p, int ld, const char* what) {
+    if (p && (ld < h->xdim || ld > kMaxLd || (ld & 3) || ((uintptr_t)p & 15)))
+      return fail(h, IWAE_EINVAL, std::string(what) + " needs x_dim <= ld <= 2^22, a multiple of 4, 16-byte aligned");
+    return IWAE_OK;
+  };
+  CHK(ld_ok(probs, ld_probs, mask ? "x_mean" : "probs"));
+  CHK(ld_ok(x_draw, ld_draw, "x_draw"));
+  const bool need_sir = want_sir || draw;        // the SIR index, and h_1 of the resampled sample
+  const bool second = want_mean || probs || need_sir;
   // ---- path and chunk
   MgLaunch MG;
   PoLaunch PO;
@@ -4467,7 +4504,8 @@ int iwae_posterior(iwae_handle* h, const float* x, int N, int k, int chunk, cons
   if (chunk <= 0) chunk = h->tune.nll_imgs;
   long long imgs_ll = chunk > 0 ? chunk : std::max<long long>(1, h->tune.nll_rows / k);
   const int ldp = r4(h->xdim);                   // layer-wise: the rows' probabilities, at most 256 MB of them
-  if (!fused && probs) imgs_ll = std::min(imgs_ll, std::max<long long>(1, (256LL << 20) / ((long long)k * ldp * 4)));
+  const bool rows_px = !fused && (probs || mask);          // (masked: the rows' logits, whatever the call wants)
+  if (rows_px) imgs_ll = std::min(imgs_ll, std::max<long long>(1, (256LL << 20) / ((long long)k * ldp * 4)));
   const int imgs = (int)std::min<long long>(imgs_ll, N);
   if ((long long)imgs * k > (1LL << 30)) return fail(h, IWAE_EINVAL, "chunk * k above 2^30 sample rows");
   const int rows = imgs * k;
@@ -4476,17 +4514,24 @@ int iwae_posterior(iwae_handle* h, const float* x, int N, int k, int chunk, cons
   if (h->x3) CHK(ensure_wsplit(h));
   if (fused) CHK(ensure_fx(h));
   NrLaunch NR;
-  const bool ring = fused && k >= 128 && nring_plan(h, NR);
+  const bool ring = fused && !mask && k >= 128 && nring_plan(h, NR);
   // ---- workspace of its own (floats): w~, SIR indices, then the path's
   const int tiles = fused ? (k + 16 * po_rt - 1) / (16 * po_rt) : 0;
   const bool gather = !fused && injected && imgs < N;     // a chunk's [k][n][d] noise, contiguous
+  const int d0 = h->enc[0].d, ldx = h->x_in.ld;
   size_t off = 0;
   auto take = [&](size_t n) { const size_t o = off; off += (n + 63) & ~size_t(63); return o; };
-  const size_t o_wt = take(weights ? 0 : rows), o_sir = take(want_sir ? imgs : 0);
+  const size_t o_wt = take(weights ? 0 : rows), o_sir = take(need_sir ? imgs : 0);
   const size_t o_part = take(fused && second ? (size_t)imgs * tiles * PO.ld_part : 0);
-  const size_t o_pw = take(!fused && probs ? (size_t)rows * ldp : 0);
+  const size_t o_pw = take(rows_px ? (size_t)rows * ldp : 0);
   size_t o_eps[IWAE_MAX_LAYERS] = {};
   for (int i = 0; i < L; ++i) o_eps[i] = take(gather ? (size_t)rows * h->enc[i].d : 0);
+  // masked calls: the -1 copy of the staged images (fused), the rows' Bernoulli sums (layer-wise),
+  // h_1 of the resampled samples when the caller keeps no h_sir, and the draw's probabilities
+  const size_t o_xm = take(mask && fused ? (size_t)sup * ldx : 0);
+  const size_t o_rs = take(mask && !fused ? (size_t)rows * 4 : 0);
+  const size_t o_h1 = take(draw && !want_sir ? (size_t)imgs * d0 : 0);
+  const size_t o_dp = take(draw ? (size_t)imgs * ldp : 0);
   if (off * sizeof(float) > h->post_ws_bytes) {
     HIPCHK(hipStreamSynchronize(h->stream));
     if (h->post_ws) (void)hipFree(h->post_ws);
@@ -4496,18 +4541,23 @@ int iwae_posterior(iwae_handle* h, const float* x, int N, int k, int chunk, cons
     h->post_ws_bytes = off * sizeof(float);
   }
   float* ws = reinterpret_cast<float*>(h->post_ws);
-  int* sir = want_sir ? reinterpret_cast<int*>(ws + o_sir) : nullptr;
+  int* sir = need_sir ? reinterpret_cast<int*>(ws + o_sir) : nullptr;
   for (int i = 0; i < 8; ++i) MG.eps[i] = NR.eps[i] = PO.eps[i] = (injected && i < L) ? eps[i] : nullptr;
   MG.eps_N = NR.eps_N = PO.eps_N = N;
   const size_t wbytes = (size_t)h->xdim * sizeof(float);
   int u0 = 0;                                    // first image of the current first-layer group (fused)
   for (int i0 = 0; i0 < N; i0 += imgs) {
     const int n = std::min(imgs, N - i0);
+    const float* xc = x + (size_t)i0 * h->xdim;                         // the chunk's images and mask rows
+    const float* mc = mask ? mask + (size_t)i0 * h->xdim : nullptr;
     if (!fused || i0 - u0 >= sup || i0 == 0) {
       u0 = i0;
       const int ng = std::min(sup, N - i0);
-      HIPCHK(hipMemcpy2DAsync(h->x_in.p, (size_t)h->x_in.ld * sizeof(float), x + (size_t)i0 * h->xdim, wbytes,
-                              wbytes, ng, hipMemcpyDeviceToDevice, h->stream));
+      if (mask)
+        HIPCHK(launch_impute_stage(h->stream, xc, mc, ng, h->xdim, h->x_in.p, ldx, fused ? ws + o_xm : nullptr, ldx));
+      else
+        HIPCHK(hipMemcpy2DAsync(h->x_in.p, (size_t)h->x_in.ld * sizeof(float), x + (size_t)i0 * h->xdim, wbytes,
+                                wbytes, ng, hipMemcpyDeviceToDevice, h->stream));
       if (fused) CHK(stoch_fwd(h, h->enc[0], h->x_in, ng, h->eb[0]));
     }
     const int io = i0 - u0;                      // the chunk's rows in x_in / eb[0]
@@ -4518,20 +4568,25 @@ int iwae_posterior(iwae_handle* h, const float* x, int N, int k, int chunk, cons
     if (fused) {
       MG.rows = n * k; MG.kS = k; MG.eps_i0 = i0; MG.eps_s0 = 0;
       MG.P0 = h->eb[0].P.p + (size_t)io * h->eb[0].P.ld; MG.ldP0 = h->eb[0].P.ld;
-      MG.x = h->x_in.p + (size_t)io * h->x_in.ld; MG.ldx = h->x_in.ld;
+      MG.x = (mask ? ws + o_xm : h->x_in.p) + (size_t)io * ldx; MG.ldx = ldx;
       MG.seed = h->seed; MG.rng_base = &h->ds->rng[0];
       MG.lw = h->lw;
-      if (ring) {
-        NR.rows = MG.rows; NR.kS = MG.kS; NR.eps_i0 = i0; NR.eps_s0 = 0;
-        NR.P0 = MG.P0; NR.ldP0 = MG.ldP0; NR.x = MG.x; NR.ldx = MG.ldx;
-        NR.seed = MG.seed; NR.rng_base = MG.rng_base; NR.lw = MG.lw;
-        HIPCHK(launch_nring(h->stream, NR));
-        ++h->count.nring;
+      if (mask) {
+        HIPCHK(launch_mega_fwd_masked(h->stream, MG, mg_rt, mg_waves, mg_lds));
+        ++h->count.imp;
       } else {
-        HIPCHK(launch_mega_fwd(h->stream, MG, mg_rt, mg_waves, mg_lds));
+        if (ring) {
+          NR.rows = MG.rows; NR.kS = MG.kS; NR.eps_i0 = i0; NR.eps_s0 = 0;
+          NR.P0 = MG.P0; NR.ldP0 = MG.ldP0; NR.x = MG.x; NR.ldx = MG.ldx;
+          NR.seed = MG.seed; NR.rng_base = MG.rng_base; NR.lw = MG.lw;
+          HIPCHK(launch_nring(h->stream, NR));
+          ++h->count.nring;
+        } else {
+          HIPCHK(launch_mega_fwd(h->stream, MG, mg_rt, mg_waves, mg_lds));
+        }
+        ++h->count.mega;
+        if (injected) ++h->count.mega_eps;
       }
-      ++h->count.mega;
-      if (injected) ++h->count.mega_eps;
       a.lw = h->lw;
     } else {
       EpsSet E;
@@ -4545,9 +4600,17 @@ int iwae_posterior(iwae_handle* h, const float* x, int N, int k, int chunk, cons
           E.a[i] = ws + o_eps[i];
         }
       }
-      CHK(forward_core(h, P, E, false));
+      if (mask) {
+        Mat Z;
+        Z.p = ws + o_pw; Z.ld = ldp;
+        CHK(impute_layerwise_fwd(h, P, E, mc, Z, ws + o_rs, probs != nullptr));
+        ++h->count.imp_lw;
+      } else {
+        CHK(forward_core(h, P, E, false));
+      }
     }
     a.part = h->part; a.ldpart = h->ldpart; a.npart = h->npart; a.logp = h->logp; a.logq = h->logq;
+    if (mask && !fused) { a.part = ws + o_rs; a.ldpart = 4; a.npart = 1; }
     a.kS = k; a.Bimg = n; a.run_m = h->run_m; a.run_s = h->run_s; a.init = 1;
     a.ticket = &h->ds->tickets[1]; a.rng_base = &h->ds->rng[0];
     HIPCHK(launch_lse(h->stream, a));
@@ -4563,6 +4626,11 @@ int iwae_posterior(iwae_handle* h, const float* x, int N, int k, int chunk, cons
     w.seed = h->seed; w.rng_base = &h->ds->rng[1]; w.u_layer = 2 * IWAE_MAX_LAYERS + 1;
     HIPCHK(launch_post_weights(h->stream, w));
     if (!second) continue;
+    // where layer i's resampled latents go: the caller's buffer, or (h_1, for the draw alone) the workspace
+    auto sel = [&](int i) -> float* {
+      if (want_sir) return h_sir[i] + (size_t)i0 * h->enc[i].d;
+      return draw && i == 0 ? ws + o_h1 : nullptr;
+    };
     // ---- pass 2
     if (fused) {
       PO.Bimg = n; PO.kS = k; PO.tiles = tiles;
@@ -4570,7 +4638,7 @@ int iwae_posterior(iwae_handle* h, const float* x, int N, int k, int chunk, cons
       PO.seed = h->seed; PO.rng_base = &h->ds->rng[1];
       PO.eps_i0 = i0;
       PO.wt = w.wt; PO.sir = sir;
-      for (int i = 0; i < L; ++i) PO.h_sir[i] = want_sir ? h_sir[i] + (size_t)i0 * h->enc[i].d : nullptr;
+      for (int i = 0; i < L; ++i) PO.h_sir[i] = sel(i);
       PO.want_mean = want_mean;
       PO.part = ws + o_part;
       HIPCHK(launch_post(h->stream, PO, po_rt, po_lds));
@@ -4593,25 +4661,66 @@ int iwae_posterior(iwae_handle* h, const float* x, int N, int k, int chunk, cons
       HIPCHK(launch_post_merge(h->stream, M));
     } else {
       ++h->count.post_lw;
-      for (int i = 0; (want_mean || want_sir) && i < L; ++i) {
+      for (int i = 0; (want_mean || need_sir) && i < L; ++i) {
         const int d = h->enc[i].d;
         HIPCHK(launch_group_wsum(h->stream, h->h[i].p, h->h[i].ld, k, d, n, w.wt,
-                                 want_mean ? h_mean[i] + (size_t)i0 * d : nullptr, d, sir,
-                                 want_sir ? h_sir[i] + (size_t)i0 * d : nullptr, d));
+                                 want_mean ? h_mean[i] + (size_t)i0 * d : nullptr, d, sir, sel(i), d));
       }
       if (probs) {
-        // the output MLP's o1 / o2 outputs of these rows are pass 1's (its Bernoulli
-        // GEMM read them from ob.y2): the output Dense again, storing the logits
         Mat pm;
         pm.p = ws + o_pw; pm.ld = ldp;
-        CHK(gemm_fwd(h, EPI_STORE, h->ob.y2, n * k, h->dense[h->o3], pm));
-        HIPCHK(launch_bern_probs(h->stream, pm.p, n * k, h->xdim, ldp));
+        if (!mask) {
+          // the output MLP's o1 / o2 outputs of these rows are pass 1's (its Bernoulli
+          // GEMM read them from ob.y2): the output Dense again, storing the logits
+          CHK(gemm_fwd(h, EPI_STORE, h->ob.y2, n * k, h->dense[h->o3], pm));
+          HIPCHK(launch_bern_probs(h->stream, pm.p, n * k, h->xdim, ldp));
+        }                                        // (masked: pass 1 left the rows' probabilities there)
         HIPCHK(launch_group_wsum(h->stream, pm.p, ldp, k, h->xdim, n, w.wt, probs + (size_t)i0 * ld_probs, ld_probs,
                                  nullptr, nullptr, 0));
       }
     }
+    if (!mask) continue;
+    // ---- imputation epilogues
+    if (probs) HIPCHK(launch_impute_fill(h->stream, xc, mc, n, h->xdim, probs + (size_t)i0 * ld_probs, ld_probs));
+    if (draw) {
+      // p(x | h_1) of the n resampled rows: the output MLP layer-wise (every
+      // reader of this chunk's h[0] / ob rows is ahead on the stream)
+      HIPCHK(hipMemcpy2DAsync(h->h[0].p, (size_t)h->h[0].ld * sizeof(float), sel(0), (size_t)d0 * sizeof(float),
+                              (size_t)d0 * sizeof(float), n, hipMemcpyDeviceToDevice, h->stream));
+      CHK(gemm_fwd(h, EPI_TANH, h->h[0], n, h->dense[h->o1], h->ob.y1));
+      CHK(gemm_fwd(h, EPI_TANH, h->ob.y1, n, h->dense[h->o2], h->ob.y2));
+      Mat pm;
+      pm.p = ws + o_dp; pm.ld = ldp;
+      CHK(gemm_fwd(h, EPI_STORE, h->ob.y2, n, h->dense[h->o3], pm));
+      HIPCHK(launch_bern_probs(h->stream, pm.p, n, h->xdim, ldp));
+      HIPCHK(launch_impute_draw(h->stream, xc, mc, pm.p, ldp, u_pix ? u_pix + (size_t)i0 * h->xdim : nullptr, n,
+                                h->xdim, x_draw + (size_t)i0 * ld_draw, ld_draw, h->seed, &h->ds->rng[1],
+                                2 * IWAE_MAX_LAYERS + 2));
+    }
   }
   return IWAE_OK;
+}
+
+int iwae_posterior(iwae_handle* h, const float* x, int N, int k, int chunk, const float* const* eps, int n_eps,
+                   const float* u, float* const* h_mean, int n_mean, float* probs, int ld_probs,
+                   float* const* h_sir, int n_sir, float* weights, float* ess, float* logpx) {
+  if (!h) return IWAE_EINVAL;
+  CHK(kernel_status(h));
+  return posterior_core(h, x, nullptr, N, k, chunk, eps, n_eps, u, nullptr, h_mean, n_mean, probs, ld_probs, nullptr, 0,
+                        h_sir, n_sir, weights, ess, logpx);
+}
+
+// Imputation of missing pixels (Mattei & Frellsen 2019): iwae_posterior under
+// the likelihood of the observed pixels alone.
+int iwae_impute(iwae_handle* h, const float* x, const float* mask, int N, int k, int chunk, const float* const* eps,
+                int n_eps, const float* u, const float* u_pix, float* x_mean, int ld_mean, float* x_draw, int ld_draw,
+                float* const* h_mean, int n_mean, float* const* h_sir, int n_sir, float* weights, float* ess,
+                float* logpx) {
+  if (!h) return IWAE_EINVAL;
+  CHK(kernel_status(h));
+  if (!mask) return fail(h, IWAE_EINVAL, "mask is NULL (an all-observed call is iwae_posterior's)");
+  return posterior_core(h, x, mask, N, k, chunk, eps, n_eps, u, u_pix, h_mean, n_mean, x_mean, ld_mean, x_draw, ld_draw,
+                        h_sir, n_sir, weights, ess, logpx);
 }
 
 // get_NLL_without_inactive_units (F:466-F:494): k-sample log p(x) with every
@@ -4673,6 +4782,8 @@ long long iwae_debug_count(const iwae_handle* h, int what) {
     case 16: return h->count.bound_multi;
     case 17: return h->count.post;
     case 18: return h->count.post_lw;
+    case 19: return h->count.imp;
+    case 20: return h->count.imp_lw;
     default: return -1;
   }
 }

@@ -779,6 +779,83 @@ class Flexible_Model:
         over k samples of q(h|x) (``posterior(...)["probs"]``)."""
         return self.posterior(x, k, eps=eps, want=("probs",))["probs"]
 
+    # ------------------------------------------- imputation of missing pixels
+    IMPUTE_OUTPUTS = ("x_mean", "x_draw", "h_mean", "h_sir", "weights", "ess", "log_px")
+
+    def impute(self, x, mask, k, eps=None, u=None, u_pix=None, chunk=0, want=IMPUTE_OUTPUTS):
+        """Missing-pixel imputation under the importance-weighted posterior
+        (iwae_impute; Mattei & Frellsen 2019).  ``mask`` [N, x_dim] (or x's
+        shape): non-zero = observed, 0 = missing; whatever ``x`` holds at a missing
+        pixel is ignored (NaN included).  The encoder sees x * mask, the log
+        weights use the likelihood of the observed pixels alone.  Returns a dict
+        of device tensors with the entries named in ``want``:
+
+        - ``"x_mean"`` [N, x_dim]: x where observed, sum_s w~_s p(x | h_{1,s})
+          where missing (the single imputation E[x_miss | x_obs]);
+        - ``"x_draw"`` [N, x_dim]: x where observed, one Bernoulli draw from
+          p(x | h_1 of the resampled sample) where missing (one multiple-imputation
+          draw; call again with another ``u`` / ``u_pix`` for more);
+        - ``"log_px"`` [N]: the k-sample estimate of log p(x_obs); ``"weights"``,
+          ``"ess"``, ``"h_mean"``, ``"h_sir"`` as in ``posterior``.
+
+        ``eps``: L arrays [k, N, d_i]; ``u``: [N] uniforms for the resampling;
+        ``u_pix``: [N, x_dim] uniforms for the pixel draws (defaults: device
+        noise); ``chunk``: images per chunk (0: automatic)."""
+        xd = self._x(x)
+        N, k = xd.shape[0], int(k)
+        want = (want,) if isinstance(want, str) else tuple(want)
+        bad = [w for w in want if w not in self.IMPUTE_OUTPUTS]
+        if bad or not want:
+            raise ValueError(f"want must name some of {self.IMPUTE_OUTPUTS}, got {want}")
+        if N <= 0 or k <= 0:
+            raise ValueError("N and k must be positive")
+        if k > 1 << 20:
+            raise ValueError("k above 2^20 per image is not supported")
+        if mask is None:
+            raise ValueError("mask is required (an all-observed call is posterior's)")
+        with torch.cuda.stream(self._stream):
+            mt = torch.as_tensor(mask).to(device=self.device, dtype=torch.float32).contiguous()
+        if mt.dim() < 2 or mt.shape[0] != N or mt.numel() != N * self.x_dim:
+            raise ValueError(f"mask must be [N={N}, {self.x_dim}], got {tuple(mt.shape)}")
+        mt = mt.reshape(N, self.x_dim)
+        arr, n, keep = self._eps(eps, N, k)
+        ut = up = None
+        with torch.cuda.stream(self._stream):
+            if u is not None:
+                ut = torch.as_tensor(u).to(device=self.device, dtype=torch.float32).contiguous()
+            if u_pix is not None:
+                up = torch.as_tensor(u_pix).to(device=self.device, dtype=torch.float32).contiguous()
+        if ut is not None and tuple(ut.shape) != (N,):
+            raise ValueError(f"u must be [N={N}], got {tuple(ut.shape)}")
+        if up is not None and tuple(up.shape) != (N, self.x_dim):
+            raise ValueError(f"u_pix must be [N={N}, {self.x_dim}], got {tuple(up.shape)}")
+        dims = self.n_latent_encoder
+        with torch.cuda.stream(self._stream):
+            ld = (self.x_dim + 3) // 4 * 4
+            hm = [torch.empty(N, d, device=self.device) for d in dims] if "h_mean" in want else []
+            hs = [torch.empty(N, d, device=self.device) for d in dims] if "h_sir" in want else []
+            xm = torch.empty(N, ld, device=self.device) if "x_mean" in want else None
+            xw = torch.empty(N, ld, device=self.device) if "x_draw" in want else None
+            wts = torch.empty(N, k, device=self.device) if "weights" in want else None
+            ess = torch.empty(N, device=self.device) if "ess" in want else None
+            lpx = torch.empty(N, device=self.device) if "log_px" in want else None
+        marr, nm = _lib.fptr_array(hm)
+        sarr, ns = _lib.fptr_array(hs)
+        self._call(self._lib.iwae_impute(self._h, _lib.fptr(xd), _lib.fptr(mt), N, k, int(chunk), arr, n,
+                                         _lib.fptr(ut), _lib.fptr(up), _lib.fptr(xm), ld if xm is not None else 0,
+                                         _lib.fptr(xw), ld if xw is not None else 0, marr, nm, sarr, ns,
+                                         _lib.fptr(wts), _lib.fptr(ess), _lib.fptr(lpx)))
+        self._stream.synchronize()
+        out = {"x_mean": xm[:, :self.x_dim] if xm is not None else None,
+               "x_draw": xw[:, :self.x_dim] if xw is not None else None,
+               "h_mean": hm, "h_sir": hs, "weights": wts, "ess": ess, "log_px": lpx}
+        return {name: out[name] for name in want}
+
+    def log_px_observed(self, x, mask, k=5000, eps=None, chunk=0):
+        """The k-sample estimate of log p(x_obs) per image, device [N]
+        (``impute(..., want="log_px")["log_px"]``)."""
+        return self.impute(x, mask, k, eps=eps, chunk=chunk, want="log_px")["log_px"]
+
     def get_levels_of_units_activity(self, x, n_samples, eps=None):
         """F:264-F:281: per stochastic layer, the variance over the batch of
         E_q[h_i] and the PCA eigenvalues of those means (host float64 on the
