@@ -431,6 +431,39 @@ int iwae_impute(iwae_handle* h, const float* x, const float* mask, int N, int k,
                 float* x_mean, int ld_mean, float* x_draw, int ld_draw,
                 float* const* h_mean, int n_mean, float* const* h_sir, int n_sir,
                 float* weights, float* ess, float* logpx);
+/* Training with missing pixels (Mattei & Frellsen 2019, MIWAE proper): the
+ * train step, forward + backward and forward-only bound of incomplete images,
+ * under iwae_impute's semantics.  Arguments as iwae_train_step /
+ * iwae_forward_backward / iwae_bound, with mask [B][x_dim] (device, required:
+ * NULL is IWAE_EINVAL) after x: non-zero = observed, 0 = missing.  The encoder
+ * sees x (.) mask; missing entries of x are selected away, never multiplied,
+ * so any value there (NaN, Inf) gives the bits a 0 gives.  The log weights are
+ *   lw[s][b] = log p(h) + sum_j [mask_bj != 0] log Bern(x_bj | p_j(h_{1,s}))
+ *              - log q(h | x (.) mask),
+ * and every loss id (path-gradient estimators included) is its function of
+ * these lw; the Keras-BCE term of L_alpha / VAE_V1 (F:317-F:323) sums the
+ * observed pixels only, VAE_V1's analytic KL is unchanged.  The loss is the
+ * batch mean over images, not renormalised by the number of observed pixels;
+ * an image with every pixel missing is legal (its likelihood term is 0).
+ * Per call one staging launch writes the images twice by select (mask ? x : 0
+ * for the first encoder layer, its backward and its weight gradient; mask ? x
+ * : -1 for the likelihood) -- no launch reads the caller's x -- and the output
+ * Dense runs the pixel-masked Bernoulli epilogue of the tiled GEMM, which
+ * selects a missing pixel's log-probability, Keras-BCE term and dLoss/dlogit
+ * to 0, so the pixel is absent from the bound, every backward chain and the
+ * weight gradients.  Paths: the fused row-block kernels or the layer-wise ones
+ * by iwae_set_path's rules; the row-chain engine and the weight-ring kernels
+ * are never used.  With device noise and iwae_set_graphs(h, 1) a single step
+ * is captured and replayed (the staging stays outside the graph, so later
+ * calls may pass other x / mask buffers).  After iwae_dp_init with world > 1:
+ * IWAE_EINVAL (masked data-parallel steps are not built).  The handle's sticky
+ * error (iwae_status) is returned before any work is enqueued. */
+int iwae_train_step_masked(iwae_handle* h, const iwae_loss_config* lc, const float* x, const float* mask, int B,
+                           const float* const* eps, int n_eps, float* loss_dev);
+int iwae_forward_backward_masked(iwae_handle* h, const iwae_loss_config* lc, const float* x, const float* mask,
+                                 int B, const float* const* eps, int n_eps, float* loss_dev);
+int iwae_bound_masked(iwae_handle* h, const iwae_loss_config* lc, const float* x, const float* mask, int B,
+                      const float* const* eps, int n_eps, float* value_dev);
 /* get_NLL_without_inactive_units (F:466-F:494): like iwae_nll / iwae_nll_eps
  * with every sampled h_i multiplied by masks[i] ([dev], d_i floats of 0/1). */
 int iwae_nll_masked(iwae_handle* h, const float* x, int N, int k, const float* const* eps,
@@ -474,7 +507,10 @@ double iwae_workspace_bytes(const iwae_handle* h);
  * its layer-wise second passes (one per chunk; both also count iwae_impute's
  * second passes); 19 masked fused first passes of iwae_impute (masked
  * mega_fwd_kernel launches, one per chunk; not counted under 0), 20 its
- * masked layer-wise first passes (one per chunk); -1 for an unknown id. */
+ * masked layer-wise first passes (one per chunk); 21 pixel-masked Bernoulli
+ * output launches (the tiled GEMM's masked epilogue) issued by
+ * iwae_train_step_masked / iwae_forward_backward_masked / iwae_bound_masked (a
+ * captured step counts once, at capture); -1 for an unknown id. */
 long long iwae_debug_count(const iwae_handle* h, int what);
 /* Live kernel timing: bracket every launch of one kernel class with HIP events
  * on the handle's stream -- a GEMM class (kind: 0 forward, 1 backward-data,

@@ -24,6 +24,13 @@
 //                  (F:127-F:128) [+ Keras BCE, F:323] row partials per 32
 //                  columns, and the per-element dLoss/dlogit factor g for the
 //                  backward pass; the [rows][784] probabilities never hit HBM.
+//   EPI_BERN_MASK  EPI_BERN with missing pixels (train steps and bounds on
+//                  incomplete images): aux holds mask ? x : -1, and where it is
+//                  negative the element's log-probability, Keras-BCE term and g
+//                  are selected to 0 (cond ? v : 0 on values computed for every
+//                  element: a -1 pixel keeps every expression finite).  A
+//                  compile-time variant: the EPI_BERN instantiations are the
+//                  code they were.
 #include "iwae_kernels.h"
 
 #include <algorithm>
@@ -69,6 +76,8 @@ __device__ __forceinline__ void split4(const float4& v, bf16x4& hi, bf16x4& lo) 
 template <int WM, int WN, int TM, int TN, bool TA, bool TB, int EPI, bool KSCALE, bool X3>
 __device__ __forceinline__ void gemm_body(const GemmArgs& a, const int bx, const int by, const int bz) {
   constexpr int NTH = WM * WN * 64;
+  constexpr bool BERN = EPI == EPI_BERN || EPI == EPI_BERN_MASK;
+  constexpr bool PIX = EPI == EPI_BERN_MASK;     // aux < 0: a missing pixel
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   constexpr int BK = X3 ? 32 : ((TM == 1 && TN == 1) ? 64 : 16);
   // k-major LDS images.  Transposed (scalar) writes want a row stride = 2 mod 32
@@ -297,7 +306,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& a, const int bx, const
   };
   // one tile per wave: its pixels are requested now, in flight during the K loop
   float xs_pre[16];
-  if constexpr (EPI == EPI_BERN && TM == 1 && TN == 1) load_x(0, 0, xs_pre);
+  if constexpr (BERN && TM == 1 && TN == 1) load_x(0, 0, xs_pre);
 
   const int nk = kend > kbeg ? (kend - kbeg + BK - 1) / BK : 0;
   if (nk > 0) {
@@ -378,7 +387,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& a, const int bx, const
   // ---------------------------------------------------------------- epilogue
   float* C = a.C + (size_t)bz * a.c_split_stride;
   const int rowq = 4 * (lane >> 5);
-  if (EPI != EPI_BERN) {
+  if (!BERN) {
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -439,10 +448,11 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& a, const int bx, const
           load_x(i, j, xs);
         }
         // binarised pixels (every image of the hot path), decided once per wave tile
-        // (bitwise, not short-circuit: no branch per pixel)
+        // (bitwise, not short-circuit: no branch per pixel); a missing pixel's -1
+        // counts as binarised, else every masked tile took the logf / log1pf branch
         bool bin = true;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) bin = bin & ((xs[r] == 0.f) | (xs[r] == 1.f));
+        for (int r = 0; r < 16; ++r) bin = bin & ((xs[r] == 0.f) | (xs[r] == 1.f) | (PIX && xs[r] < 0.f));
         bin = __all(bin);
         if (bin && !a.need_bce && a.wb == 0.f) {
           // p = sigmoid(l)*(1-1e-6)+1e-7 >= 1e-7, so the raw v_log / v_rcp are exact
@@ -452,14 +462,16 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& a, const int bx, const
             const int ml = (r & 3) + 8 * (r >> 2) + rowq;
             const int m = mt + ml;
             const bool ok = (m < M && n < N);
+            const bool obs = !PIX || xs[r] >= 0.f;
             const float s = frcp(1.f + fexp(-t[r]));
             const float p = __fadd_rn(__fmul_rn(s, kProbScale), kProbShift);
             const bool one = xs[r] != 0.f;
             const float sel = one ? p : 1.f - p;
-            S[ml * 33 + (lane & 31)] = ok ? kLn2 * __builtin_amdgcn_logf(sel) : 0.f;
+            S[ml * 33 + (lane & 31)] = (ok && obs) ? kLn2 * __builtin_amdgcn_logf(sel) : 0.f;
             if (a.store_g && ok) {
               const float g = one ? frcp(sel) : -frcp(sel);
-              C[(size_t)m * a.ldc + n] = (a.wa * g) * (kProbScale * (s * (1.f - s)));
+              const float gv = (a.wa * g) * (kProbScale * (s * (1.f - s)));
+              C[(size_t)m * a.ldc + n] = obs ? gv : 0.f;
             }
             vb[r] = 0.f;
           }
@@ -468,12 +480,12 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& a, const int bx, const
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int ml = (r & 3) + 8 * (r >> 2) + rowq;
-            const bool ok = (mt + ml < M && n < N);
             const float xv = xs[r];
+            const bool ok = (mt + ml < M && n < N) && (!PIX || xv >= 0.f);
             const float sg = __fdividef(1.f, 1.f + __expf(-t[r]));
             const float p = __fadd_rn(__fmul_rn(sg, kProbScale), kProbShift);
             float val;
-            if (__all((xv == 0.f) || (xv == 1.f))) {
+            if (__all((xv == 0.f) || (xv == 1.f) || (PIX && xv < 0.f))) {
               val = __logf(xv != 0.f ? p : 1.f - p);
             } else {
               val = __fadd_rn(__fmul_rn(log1pf(-p), 1.f - xv), __fmul_rn(logf(p), xv));
@@ -489,12 +501,13 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& a, const int bx, const
           float val = 0.f, bce = 0.f;
           const bool ok = (m < M && n < N);
           const float xv = xs[r];
+          const bool obs = !PIX || xv >= 0.f;
           const float l = t[r];
           const float s = __fdividef(1.f, 1.f + __expf(-l));
           const float p = __fadd_rn(__fmul_rn(s, kProbScale), kProbShift);
           const float dsig = kProbScale * (s * (1.f - s));
           float g = 0.f;
-          if (__all((xv == 0.f) || (xv == 1.f))) {
+          if (__all((xv == 0.f) || (xv == 1.f) || (PIX && xv < 0.f))) {
             // binarised pixels (every wave of the hot path): one log per element.
             // log(1-p) stands in for log1p(-p); they differ by <1e-7 absolute here.
             const float sel = xv != 0.f ? p : 1.f - p;
@@ -505,18 +518,19 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& a, const int bx, const
             val = __fadd_rn(__fmul_rn(lp0, 1.f - xv), __fmul_rn(lp1, xv));
             g = xv / p - (1.f - xv) / (1.f - p);
           }
-          if (!ok) val = 0.f;
+          if (!(ok && obs)) val = 0.f;
           if (a.need_bce || a.wb != 0.f) {
             const float pc = fminf(fmaxf(p, kKerasEps), 1.f - kKerasEps);
             if (a.need_bce && ok)
               bce = xv * logf(pc + kKerasEps) + (1.f - xv) * logf(1.f - pc + kKerasEps);
+            if (!obs) bce = 0.f;
             const bool inr = (p >= kKerasEps) && (p <= 1.f - kKerasEps);
             const float gb = inr ? (xv / (pc + kKerasEps) - (1.f - xv) / (1.f - pc + kKerasEps)) : 0.f;
             g = a.wa * g + a.wb * gb;
           } else {
             g = a.wa * g;
           }
-          if (a.store_g && ok) C[(size_t)m * a.ldc + n] = g * dsig;
+          if (a.store_g && ok) C[(size_t)m * a.ldc + n] = obs ? g * dsig : 0.f;
           S[ml * 33 + (lane & 31)] = val;
           vb[r] = bce;
         }
@@ -623,6 +637,7 @@ static hipError_t dispatch_tile(hipStream_t st, GemmKind kind, GemmEpi epi, int 
     case GEMM_FWD:
       if (epi == EPI_TANH) return launch_t<WM, WN, TM, TN, false, false, EPI_TANH, false>(st, splits, a);
       if (epi == EPI_BERN) return launch_t<WM, WN, TM, TN, false, false, EPI_BERN, false>(st, splits, a);
+      if (epi == EPI_BERN_MASK) return launch_t<WM, WN, TM, TN, false, false, EPI_BERN_MASK, false>(st, splits, a);
       if (epi == EPI_STORE) return launch_t<WM, WN, TM, TN, false, false, EPI_STORE, false>(st, splits, a);
       break;
     case GEMM_BWD_DATA:

@@ -169,7 +169,9 @@ __device__ __forceinline__ float normal_logp(float h, float mu, float sc) {
 
 // ---------------------------------------------------------------- GEMM ----
 enum GemmKind { GEMM_FWD = 0, GEMM_BWD_DATA = 1, GEMM_BWD_WEIGHT = 2 };
-enum GemmEpi { EPI_STORE = 0, EPI_TANH = 1, EPI_BERN = 2, EPI_TANH_GRAD = 3 };
+// EPI_BERN_MASK: EPI_BERN over a pixel-masked image (aux < 0 marks a missing
+// pixel: its log-probability, Keras-BCE term and g are selected to 0)
+enum GemmEpi { EPI_STORE = 0, EPI_TANH = 1, EPI_BERN = 2, EPI_TANH_GRAD = 3, EPI_BERN_MASK = 4 };
 
 struct GemmArgs {
   const float* A; const float* B; float* C;
@@ -177,7 +179,7 @@ struct GemmArgs {
   int M, N, K;
   int kchunk;                 // K range per blockIdx.z (multiple of 64)
   long long c_split_stride;   // C offset per blockIdx.z (split-K slabs)
-  const float* aux; int ldaux;  // TANH_GRAD: Y (tanh output); BERN: x_in
+  const float* aux; int ldaux;  // TANH_GRAD: Y (tanh output); BERN: x_in; BERN_MASK: mask ? x : -1
   const float* rowscale;      // STORE/TANH_GRAD: C[m][:] *= rowscale[m]
   const float* kscale;        // BWD_WEIGHT: B[k][:] *= kscale[k]
   float* part; float* part2; int ldpart;  // BERN: per-32-column row partials

@@ -88,6 +88,7 @@ struct Plan {
   int kl = 0;                  // VAE_V1 analytic KL on the last encoder layer
   int piwae = 0;               // two backward passes: dlw / dpx for the decoder, dlw2 / dpx2 (mode2) for the encoder
   int path = 0;                // IWAE_STL / IWAE_DREG: the encoder's gradient through the sampling path only
+  int pix = 0;                 // pixel-masked call (MIWAE): x_in holds mask ? x : 0, x_lik mask ? x : -1
 };
 
 // Tuning knobs (iwae_set_tuning; ids, ranges and the measurements behind the
@@ -209,6 +210,7 @@ struct Counters {
   long long bound = 0, bound_multi = 0;  // 15, 16: bound_kernel launches (all / with more than one workgroup)
   long long post = 0, post_lw = 0;       // 17, 18: iwae_posterior second passes: post_kernel launches / layer-wise passes
   long long imp = 0, imp_lw = 0;         // 19, 20: iwae_impute first passes: masked mega_fwd_kernel launches / layer-wise passes
+  long long bern_mask = 0;               // 21: pixel-masked Bernoulli output launches (EPI_BERN_MASK) of train steps and bounds
 };
 
 // row-chain train engine plan (device resident, per shape; iwae_train.hip)
@@ -309,6 +311,7 @@ struct iwae_handle {
   bool cap_train = false;
   bool cap_path = false;             // the workspace holds the path-gradient losses' buffers (dh_encq, dPq)
   Mat x_in;
+  Mat x_lik;                         // pixel-masked calls: the likelihood's copy of the images, mask ? x : -1
   std::vector<LayerBufs> eb, db;
   LayerBufs ob;                      // output MLP: y1 = o1, y2 = o2, P = g
   std::vector<Mat> h, eps_st, dh_out, dh_prior, dh_dec, dh_enc;
@@ -538,6 +541,9 @@ static int ensure_capacity(iwae_handle* h, int Bimg, int rows, bool train, bool 
     }
   }
   size_t slab_base = take(slab_total);
+  // (last, so every other buffer keeps its offset: a few images, always there,
+  // so a pixel-masked call never regrows the arena under a captured graph)
+  mat(h->x_lik, Bimg, h->xdim + 1);
   const size_t bytes = off * sizeof(float);
   HIPCHK(hipMalloc(&h->arena, bytes));
   h->arena_bytes = bytes;
@@ -841,14 +847,17 @@ static int forward_core(iwae_handle* h, const Plan& P, const EpsSet& E, bool tra
   CHK(gemm_fwd(h, EPI_TANH, h->ob.y1, M, h->dense[h->o2], h->ob.y2));
   {
     GemmArgs ex{};
-    ex.aux = h->x_in.p; ex.ldaux = h->x_in.ld; ex.x_row_div = kS;
+    // (a pixel-masked call: the -1 copy and the epilogue that selects by it)
+    const Mat& xl = P.pix ? h->x_lik : h->x_in;
+    ex.aux = xl.p; ex.ldaux = xl.ld; ex.x_row_div = kS;
     ex.part = h->part; ex.part2 = h->part2; ex.ldpart = h->ldpart;
     ex.wa = P.wa; ex.wb = P.wb;
     ex.store_g = train ? 1 : 0;
     ex.need_bce = P.need_bce;
     Mat gm = h->ob.P;
     if (!train) { gm.p = nullptr; gm.ld = 0; }
-    CHK(gemm_fwd(h, EPI_BERN, h->ob.y2, M, h->dense[h->o3], gm, ex));
+    CHK(gemm_fwd(h, P.pix ? EPI_BERN_MASK : EPI_BERN, h->ob.y2, M, h->dense[h->o3], gm, ex));
+    if (P.pix) h->count.bern_mask++;
   }
   return IWAE_OK;
 }
@@ -1179,6 +1188,25 @@ static int copy_x(iwae_handle* h, const Plan& P, const float* x) {
   return IWAE_OK;
 }
 
+// copy_x of a pixel-masked call (mask [B][x_dim], non-zero = observed), by
+// select: x_in = mask ? x : 0 for every reader of the image (first encoder
+// layer, its backward and weight gradient), x_lik = mask ? x : -1 for the
+// masked Bernoulli epilogue.  One launch per copy of the batch (CIWAE: two).
+static int stage_masked(iwae_handle* h, const Plan& P, const float* x, const float* mask) {
+  for (int r0 = 0; r0 < P.Bimg; r0 += P.B)
+    HIPCHK(launch_impute_stage(h->stream, x, mask, P.B, h->xdim, h->x_in.p + (size_t)r0 * h->x_in.ld, h->x_in.ld,
+                               h->x_lik.p + (size_t)r0 * h->x_lik.ld, h->x_lik.ld));
+  return IWAE_OK;
+}
+
+// pixel-masked entry points: the checks they share
+static int check_masked(iwae_handle* h, const float* mask) {
+  if (!mask) return fail(h, IWAE_EINVAL, "mask is NULL");
+  if (h->dp_world > 1)
+    return fail(h, IWAE_EINVAL, "pixel-masked steps and bounds are not built for data parallelism (world > 1)");
+  return IWAE_OK;
+}
+
 // The node the capture on the handle's stream enqueued last (null unless it
 // is exactly one): the launch or copy just issued, kept to re-point on replay.
 static int last_captured_node(iwae_handle* h, hipGraphNode_t* node) {
@@ -1494,14 +1522,17 @@ static int fused_forward(iwae_handle* h, const Plan& P, const EpsSet& E, bool tr
   // (5) output layer 200 -> 784 with the fused Bernoulli epilogue
   {
     GemmArgs ex{};
-    ex.aux = h->x_in.p; ex.ldaux = h->x_in.ld; ex.x_row_div = kS;
+    // (a pixel-masked call: the -1 copy and the epilogue that selects by it)
+    const Mat& xl = P.pix ? h->x_lik : h->x_in;
+    ex.aux = xl.p; ex.ldaux = xl.ld; ex.x_row_div = kS;
     ex.part = h->part; ex.part2 = h->part2; ex.ldpart = h->ldpart;
     ex.wa = P.wa; ex.wb = P.wb;
     ex.store_g = train ? 1 : 0;
     ex.need_bce = P.need_bce;
     Mat gm = h->ob.P;
     if (!train) { gm.p = nullptr; gm.ld = 0; }
-    CHK(gemm_fwd(h, EPI_BERN, h->ob.y2, M, h->dense[h->o3], gm, ex));
+    CHK(gemm_fwd(h, P.pix ? EPI_BERN_MASK : EPI_BERN, h->ob.y2, M, h->dense[h->o3], gm, ex));
+    if (P.pix) h->count.bern_mask++;
   }
   return IWAE_OK;
 }
@@ -1917,6 +1948,7 @@ static bool use_engine(const iwae_handle* h, const Plan& P) {
   if (!h->tune.engine || !h->x3 || h->path == 1 || h->path == 2 || h->masked) return false;
   if (P.kl) return false;       // VAE_V1's analytic KL: fused row-block path
   if (P.path) return false;     // IWAE_STL / IWAE_DREG: the engine's Gaussian backward has no gradient modes
+  if (P.pix) return false;      // pixel-masked steps: the engine's and the ring's Bernoulli epilogues know no mask
   // L_power_p with p < 0: the row weights softmax(p lw) sit on each image's smallest
   // log-weights, the ones of the largest magnitude, and scale the engine's bf16x3
   // rounding of lw by |p| (3 layers, p = -1.5: gradient 1.7e-4 off float64 against
@@ -2962,30 +2994,37 @@ static int prepare_engine(iwae_handle* h, const Plan& P) {
   return IWAE_OK;
 }
 
+// (mask: a pixel-masked step, [B][x_dim], non-zero = observed; null: none)
 static int do_train(iwae_handle* h, const iwae_loss_config* lc, const float* x, int B,
-                    const float* const* eps, int n_eps, float* loss_dev, bool adam) {
+                    const float* const* eps, int n_eps, float* loss_dev, bool adam, const float* mask = nullptr) {
   if (!x) return fail(h, IWAE_EINVAL, "x is NULL");
   if (adam && h->dp_weighted && !h->comm)
     return fail(h, IWAE_EINVAL, "data parallel without a library communicator: call iwae_forward_backward, "
                                 "all-reduce the gradient buffer, then iwae_apply_adam(h, 0)");
   Plan P;
   CHK(make_plan(h, lc, B, P));
+  P.pix = mask ? 1 : 0;
   EpsSet E;
   CHK(parse_eps(h, P, eps, n_eps, E));
   CHK(ensure_capacity(h, P.Bimg, P.Bimg * P.kS, true, P.path != 0));
   const bool engine = use_engine(h, P);
   if (engine) CHK(prepare_engine(h, P));
   // the fused step's first kernel reads the caller's x itself (and fills x_in);
-  // every other path stages x into x_in first
-  const bool direct = P.Bimg == P.B && (((engine || use_fused(h, P)) && smallm_ok(h, P.Bimg)) || gemm_direct(h, P));
-  if (!direct) CHK(copy_x(h, P, x));
+  // every other path stages x into x_in first.  A pixel-masked step always
+  // stages (outside the captured region, like copy_x): no launch reads the
+  // caller's x, so a replay needs no re-pointing for new x / mask buffers.
+  const bool direct =
+      !mask && P.Bimg == P.B && (((engine || use_fused(h, P)) && smallm_ok(h, P.Bimg)) || gemm_direct(h, P));
+  if (mask) CHK(stage_masked(h, P, x, mask));
+  else if (!direct) CHK(copy_x(h, P, x));
   StepScope scope{h};
   h->step.x_user = direct ? x : nullptr;
   const bool philox = (E.a[0] == nullptr);
   h->step.loss_out = loss_dev;
   h->step.in_train_step = true;
   if (!(h->use_graphs && philox && h->prof.kind < 0)) return train_body(h, P, E, adam);
-  const auto key = graph_key(adam ? 1 : 0, lc, B, {(long long)(uintptr_t)loss_dev, direct ? 1 : 0, engine ? 1 : 0});
+  const auto key =
+      graph_key(adam ? 1 : 0, lc, B, {(long long)(uintptr_t)loss_dev, direct ? 1 : 0, engine ? 1 : 0, P.pix});
   auto it = h->graphs.find(key);
   GraphRec* g = it == h->graphs.end() ? nullptr : &it->second;
   if (!g) CHK(capture_graph(h, key, [&](GraphRec& r) { return capture_step(h, P, E, adam, r); }, &g));
@@ -3539,6 +3578,22 @@ int iwae_train_step(iwae_handle* h, const iwae_loss_config* lc, const float* x, 
   return do_train(h, lc, x, B, eps, n_eps, loss_dev, true);
 }
 
+int iwae_train_step_masked(iwae_handle* h, const iwae_loss_config* lc, const float* x, const float* mask, int B,
+                           const float* const* eps, int n_eps, float* loss_dev) {
+  if (!h) return IWAE_EINVAL;
+  CHK(kernel_status(h));
+  CHK(check_masked(h, mask));
+  return do_train(h, lc, x, B, eps, n_eps, loss_dev, true, mask);
+}
+
+int iwae_forward_backward_masked(iwae_handle* h, const iwae_loss_config* lc, const float* x, const float* mask, int B,
+                                 const float* const* eps, int n_eps, float* loss_dev) {
+  if (!h) return IWAE_EINVAL;
+  CHK(kernel_status(h));
+  CHK(check_masked(h, mask));
+  return do_train(h, lc, x, B, eps, n_eps, loss_dev, false, mask);
+}
+
 int iwae_train_steps(iwae_handle* h, const iwae_loss_config* lc, const float* x, int B, int nsteps,
                      float* loss_dev) {
   if (!h) return IWAE_EINVAL;
@@ -3667,13 +3722,15 @@ int iwae_dp_world(const iwae_handle* h, int* world, int* comm_ranks) {
   return IWAE_OK;
 }
 
+// (mask: a pixel-masked plan's mask, P.pix set; null otherwise)
 static int eval_forward(iwae_handle* h, const Plan& P, const float* x, const float* const* eps, int n_eps,
-                        EpsSet& E) {
+                        EpsSet& E, const float* mask = nullptr) {
   if (!x) return fail(h, IWAE_EINVAL, "x is NULL");
   if (h->x3) CHK(ensure_wsplit(h));
   CHK(parse_eps(h, P, eps, n_eps, E));
   CHK(ensure_capacity(h, P.Bimg, P.Bimg * P.kS, false));
-  CHK(copy_x(h, P, x));
+  if (mask) CHK(stage_masked(h, P, x, mask));
+  else CHK(copy_x(h, P, x));
   return forward_core(h, P, E, false);
 }
 
@@ -3699,6 +3756,21 @@ int iwae_bound(iwae_handle* h, const iwae_loss_config* lc, const float* x, int B
   CHK(make_plan(h, lc, B, P));
   EpsSet E;
   CHK(eval_forward(h, P, x, eps, n_eps, E));
+  CHK(run_bound(h, P, false, 1.f, value_dev));
+  return IWAE_OK;
+}
+
+int iwae_bound_masked(iwae_handle* h, const iwae_loss_config* lc, const float* x, const float* mask, int B,
+                      const float* const* eps, int n_eps, float* value_dev) {
+  if (!h) return IWAE_EINVAL;
+  CHK(kernel_status(h));
+  CHK(check_masked(h, mask));
+  if (!value_dev) return fail(h, IWAE_EINVAL, "value_dev is NULL");
+  Plan P;
+  CHK(make_plan(h, lc, B, P));
+  P.pix = 1;
+  EpsSet E;
+  CHK(eval_forward(h, P, x, eps, n_eps, E, mask));
   CHK(run_bound(h, P, false, 1.f, value_dev));
   return IWAE_OK;
 }
@@ -3865,7 +3937,7 @@ static bool nring_train_forward(iwae_handle* h, const Plan& P, const EpsSet& E, 
   ran = false;
   const long long rows = (long long)P.Bimg * P.kS;
   if (!h->tune.nring_train || !h->x3 || rows < h->tune.nr_train_rows || P.kS < 43 || P.need_bce || use_fold0(h, P) ||
-      P.Bsplit != P.Bimg)
+      P.Bsplit != P.Bimg || P.pix)
     return true;
   if (E.a[0] && (h->L >= 2 && !E.a[1])) return true;
   NrLaunch NR;
@@ -4784,6 +4856,7 @@ long long iwae_debug_count(const iwae_handle* h, int what) {
     case 18: return h->count.post_lw;
     case 19: return h->count.imp;
     case 20: return h->count.imp_lw;
+    case 21: return h->count.bern_mask;
     default: return -1;
   }
 }

@@ -278,6 +278,14 @@ class Flexible_Model:
         with torch.cuda.stream(self._stream):
             return t.to(device=self.device, dtype=torch.float32, non_blocking=True).contiguous()
 
+    def _mask(self, mask, N):
+        """A pixel mask as a device [N, x_dim] float tensor (non-zero = observed)."""
+        with torch.cuda.stream(self._stream):
+            mt = torch.as_tensor(mask).to(device=self.device, dtype=torch.float32, non_blocking=True).contiguous()
+        if mt.dim() < 2 or mt.shape[0] != N or mt.numel() != N * self.x_dim:
+            raise ValueError(f"mask must be [N={N}, {self.x_dim}], got {tuple(mt.shape)}")
+        return mt.reshape(N, self.x_dim)
+
     def _eps(self, eps, B, k, n_draws=1):
         if eps is None:
             return None, 0, []
@@ -370,15 +378,25 @@ class Flexible_Model:
         o = self.optimizer
         self._call(self._lib.iwae_set_adam(self._h, o.learning_rate, o.beta_1, o.beta_2, o.epsilon))
 
-    def train_step(self, x, eps=None, sync=True):
-        """F:221-F:247: one optimisation step; returns {loss_function: loss}."""
+    def train_step(self, x, eps=None, sync=True, mask=None):
+        """F:221-F:247: one optimisation step; returns {loss_function: loss}.
+        ``mask`` [B, x_dim] (non-zero = observed): the step on incomplete images
+        (iwae_train_step_masked; Mattei & Frellsen 2019): the encoder sees
+        x * mask, the likelihood sums the observed pixels, whatever ``x`` holds
+        at a missing pixel is ignored (NaN included)."""
         if self.optimizer is None:
             self.compile()
         xd = self._x(x)
         B = xd.shape[0]
         lc = self._lc()
         arr, n, keep = self._eps(eps, B, lc.k, 2 if self.loss_function == "CIWAE" else 1)
-        if self._dp is not None:
+        if mask is not None:
+            if self._dp is not None:
+                raise ValueError("train_step(mask=...) is not supported under data parallelism")
+            mt = self._mask(mask, B)
+            self._call(self._lib.iwae_train_step_masked(self._h, lc, _lib.fptr(xd), _lib.fptr(mt), B, arr, n,
+                                                        _lib.fptr(self._loss_buf)))
+        elif self._dp is not None:
             self._dp.step(self, lc, xd, B, arr, n)
         else:
             self._call(self._lib.iwae_train_step(self._h, lc, _lib.fptr(xd), B, arr, n, _lib.fptr(self._loss_buf)))
@@ -390,12 +408,14 @@ class Flexible_Model:
         self._call(self._lib.iwae_status(self._h))      # an in-launch wait that gave up raises
         return {self.loss_function: loss}
 
-    def train_steps(self, x, batch_size, sync=True):
+    def train_steps(self, x, batch_size, sync=True, mask=None):
         """len(x) // batch_size consecutive train steps (F:221-F:247 each) on the
         batches x[i*batch_size:(i+1)*batch_size] with device noise: fit's inner
         loop (E:82) as one library call (iwae_train_steps: up to 32 steps per
         captured graph).  Returns the per-step losses (device tensor if
-        sync=False)."""
+        sync=False).  ``mask`` [len(x), x_dim]: pixel-masked steps (see
+        train_step), one iwae_train_step_masked per batch on the stream with no
+        synchronisation between them."""
         if self.optimizer is None:
             self.compile()
         xd = self._x(x)
@@ -407,7 +427,18 @@ class Flexible_Model:
             losses = torch.empty(n, device=self.device)
         if n == 0:
             return losses if not sync else losses.cpu().numpy()
-        if self._dp is not None and self._dp.comm != "library":
+        if mask is not None:
+            if self._dp is not None:
+                raise ValueError("train_steps(mask=...) is not supported under data parallelism")
+            mt = self._mask(mask, xd.shape[0])
+            lc = self._lc()
+            for i in range(n):
+                self._call(self._lib.iwae_train_step_masked(
+                    self._h, lc, _lib.fptr(xd[i * B:(i + 1) * B]), _lib.fptr(mt[i * B:(i + 1) * B]), B, None, 0,
+                    _lib.fptr(self._loss_buf)))
+                with torch.cuda.stream(self._stream):
+                    losses[i] = self._loss_buf[0]
+        elif self._dp is not None and self._dp.comm != "library":
             for i in range(n):
                 self._dp.step(self, self._lc(), xd[i * B:(i + 1) * B], B, None, 0)
                 with torch.cuda.stream(self._stream):
@@ -449,12 +480,15 @@ class Flexible_Model:
         if n:
             raise _lib.IwaeError(f"{n} in-launch wait(s) gave up")
 
-    def fit(self, x, epochs=1, batch_size=100, shuffle=True, verbose=0, seed=None):
+    def fit(self, x, epochs=1, batch_size=100, shuffle=True, verbose=0, seed=None, mask=None):
         """Keras-style loop (E:82): per epoch shuffle, batches of batch_size
         (last partial batch included), one train step each (the whole batches
-        through train_steps, the partial one through train_step)."""
+        through train_steps, the partial one through train_step).  ``mask``
+        [N, x_dim]: training on incomplete images (see train_step); the epoch's
+        permutation is applied to x and mask alike."""
         xd = self._x(x)
         N = xd.shape[0]
+        md = self._mask(mask, N) if mask is not None else None
         g = torch.Generator(device="cpu")
         if seed is not None:
             g.manual_seed(int(seed))
@@ -463,14 +497,16 @@ class Flexible_Model:
             perm = torch.randperm(N, generator=g) if shuffle else torch.arange(N)
             with torch.cuda.stream(self._stream):
                 xs = xd[perm.to(self.device)] if shuffle else xd
+                ms = None if md is None else (md[perm.to(self.device)] if shuffle else md)
                 losses = torch.zeros((N + batch_size - 1) // batch_size, device=self.device)
             nfull = N // batch_size
+            ncut = nfull * batch_size
             if nfull:
-                full = self.train_steps(xs[:nfull * batch_size], batch_size, sync=False)
+                full = self.train_steps(xs[:ncut], batch_size, sync=False, mask=None if ms is None else ms[:ncut])
                 with torch.cuda.stream(self._stream):
                     losses[:nfull] = full
             if N % batch_size:
-                out = self.train_step(xs[nfull * batch_size:], sync=False)[self.loss_function]
+                out = self.train_step(xs[ncut:], sync=False, mask=None if ms is None else ms[ncut:])[self.loss_function]
                 with torch.cuda.stream(self._stream):
                     losses[nfull] = out[0]
             self._stream.synchronize()
@@ -505,43 +541,48 @@ class Flexible_Model:
         """F:429-F:430."""
         return torch.mean(torch.as_tensor(log_weights))
 
-    def _bound(self, lc, x, eps, n_draws=1):
+    def _bound(self, lc, x, eps, n_draws=1, mask=None):
+        """A forward-only bound; ``mask`` [B, x_dim] (non-zero = observed): of
+        the observed pixels of incomplete images (iwae_bound_masked)."""
         xd = self._x(x)
         B = xd.shape[0]
         arr, n, keep = self._eps(eps, B, lc.k, n_draws)
+        if mask is not None:
+            mt = self._mask(mask, B)
+            return self._scalar(self._lib.iwae_bound_masked, lc, _lib.fptr(xd), _lib.fptr(mt), B, arr, n)
         return self._scalar(self._lib.iwae_bound, lc, _lib.fptr(xd), B, arr, n)
 
-    def get_L_k(self, x, k, eps=None):
+    def get_L_k(self, x, k, eps=None, mask=None):
         """F:354-F:361."""
-        return self._bound(self._lc("IWAE", k=k), x, eps)
+        return self._bound(self._lc("IWAE", k=k), x, eps, mask=mask)
 
-    def get_L(self, x, k=5000, eps=None):
+    def get_L(self, x, k=5000, eps=None, mask=None):
         """F:419-F:427."""
-        return self._bound(self._lc("VAE", k=k), x, eps)
+        return self._bound(self._lc("VAE", k=k), x, eps, mask=mask)
 
-    def get_L_median(self, x, k, eps=None):
+    def get_L_median(self, x, k, eps=None, mask=None):
         """F:373-F:379."""
-        return self._bound(self._lc("L_median", k=k), x, eps)
+        return self._bound(self._lc("L_median", k=k), x, eps, mask=mask)
 
-    def get_L_CIWAE(self, x, n_samples, beta, eps=None):
+    def get_L_CIWAE(self, x, n_samples, beta, eps=None, mask=None):
         """F:382-F:383 (two independent draws: eps = draw1 + draw2)."""
-        return self._bound(self._lc("CIWAE", k=n_samples, beta=beta), x, eps, 2)
+        return self._bound(self._lc("CIWAE", k=n_samples, beta=beta), x, eps, 2, mask=mask)
 
-    def get_L_alpha(self, x, n_samples, alpha, eps=None):
+    def get_L_alpha(self, x, n_samples, alpha, eps=None, mask=None):
         """F:386-F:402."""
-        return self._bound(self._lc("L_alpha", k=n_samples, alpha=alpha), x, eps)
+        return self._bound(self._lc("L_alpha", k=n_samples, alpha=alpha), x, eps, mask=mask)
 
-    def get_L_power_p(self, x, k, p, eps=None):
+    def get_L_power_p(self, x, k, p, eps=None, mask=None):
         """F:405-F:409."""
-        return self._bound(self._lc("L_power_p", k=k, p=p), x, eps)
+        return self._bound(self._lc("L_power_p", k=k, p=p), x, eps, mask=mask)
 
-    def get_L_V1(self, x, n_samples, eps=None):
+    def get_L_V1(self, x, n_samples, eps=None, mask=None):
         """F:434-F:460."""
-        return self._bound(self._lc("VAE_V1", k=n_samples), x, eps)
+        return self._bound(self._lc("VAE_V1", k=n_samples), x, eps, mask=mask)
 
-    def get_L_MIWAE(self, x, k1, k2, eps=None):
+    def get_L_MIWAE(self, x, k1, k2, eps=None, mask=None):
         """MIWAE(k1, k2) (IWAE_replication.pdf p7)."""
-        return self._bound(self._lc("MIWAE", k1=k1, k2=k2), x, eps)
+        return self._bound(self._lc("MIWAE", k1=k1, k2=k2), x, eps, mask=mask)
 
     def get_E_qhIx_log_pxIh(self, x, n_samples, eps=None):
         """F:304-F:325 (Keras binary cross-entropy form)."""
