@@ -354,6 +354,38 @@ int iwae_reconstruct(iwae_handle* h, const float* x, int B, const float* const* 
 int iwae_generate(iwae_handle* h, int n, const float* h_top, const float* const* eps, int n_eps,
                   const float* u, float* probs, int ld_probs, float* pixels, int ld_pixels,
                   float* const* h_out, int n_out);
+/* Dynamic binarisation (the stochastic "MNIST" setting, PDF p7 s3.1): gather
+ * the caller's grey-level rows and draw every pixel ~ Bernoulli(grey level),
+ * one streaming launch.  Every pointer is a device pointer.  x [n_src][x_dim]
+ * grey levels; perm: n int64 row indices into x (what torch.randperm gives), or
+ * NULL: the identity, which needs n <= n_src; 0 <= n <= 2^24.  Output row i is
+ * drawn from source row perm[i]:
+ *   out[i][j] = (u_ij < x[perm[i]][j] || x[perm[i]][j] >= 1) ? 1.0f : 0.0f,
+ * so NaN, 0 and negative grey levels give 0.  The x >= 1 clause: the uniform
+ * of a Philox word c is ((float)c + 0.5f) * 2^-32, which rounds to exactly 1.0f
+ * for c >= 0xFFFFFF80 (about 3e-8 of the draws); with the clause a grey level
+ * of 1 always gives 1 and a 0/1 image set comes back bit for bit.  An index
+ * outside [0, n_src) gives a row of zeros (a select: nothing outside x is ever
+ * read).  out [n][ld_out] follows iwae_generate's rules: x_dim <= ld_out <=
+ * 2^22, a multiple of 4, 16-byte aligned, columns [x_dim, ld_out) not written;
+ * out == x is legal when perm is NULL and ld_out == x_dim (a thread reads its
+ * own column quad before it writes it).  u [n][x_dim]: uniforms in [0, 1)
+ * (parity tests), or NULL: Philox on the handle's key (seed and current noise
+ * stream), layer id 2 * IWAE_MAX_LAYERS + 3, row = the OUTPUT row i, column
+ * quad j / 4 as the counter's group and j % 4 the value within it
+ * (iwae_generate's pixel layout).  Every call with n > 0 advances the noise
+ * position once (with u given as well); n == 0 succeeds, launches nothing and
+ * leaves the position alone.  x is loaded as float4 when x_dim is a multiple
+ * of 4 and x is 16-byte aligned, by scalar loads otherwise, with the same
+ * result.  Weights, Adam state, captured graphs, engine plans and the workspace
+ * are untouched.  The handle's sticky error (iwae_status) is returned before
+ * any work is enqueued; IWAE_EINVAL: x or out NULL, n or n_src negative, n >
+ * 2^24, n > n_src without perm, a bad ld_out or a misaligned out, or n *
+ * ceil(x_dim / 4) >= 2^32 - 255 (the launch's thread count).  After iwae_dp_init
+ * the current noise stream is the rank, so ranks binarise their shards
+ * independently. */
+int iwae_binarize(iwae_handle* h, const float* x, long long n_src, const long long* perm,
+                  int n, const float* u, float* out, int ld_out);
 /* The importance-weighted posterior q_IW of an IWAE (Cremer, Morningstar &
  * Duvenaud 2017): k samples of q(h|x) reweighted by their self-normalised
  * importance weights.  For image b, lw[b][s] (s < k) are the log weights of
@@ -510,7 +542,8 @@ double iwae_workspace_bytes(const iwae_handle* h);
  * masked layer-wise first passes (one per chunk); 21 pixel-masked Bernoulli
  * output launches (the tiled GEMM's masked epilogue) issued by
  * iwae_train_step_masked / iwae_forward_backward_masked / iwae_bound_masked (a
- * captured step counts once, at capture); -1 for an unknown id. */
+ * captured step counts once, at capture); 22 binarize_kernel launches issued by
+ * iwae_binarize (one per call with n > 0); -1 for an unknown id. */
 long long iwae_debug_count(const iwae_handle* h, int what);
 /* Live kernel timing: bracket every launch of one kernel class with HIP events
  * on the handle's stream -- a GEMM class (kind: 0 forward, 1 backward-data,

@@ -96,6 +96,7 @@ SIGNATURES = {
     "iwae_encoder_means": (c_int, [H, FP, c_int, c_int, FPP, c_int, FPP, c_int]),
     "iwae_reconstruct": (c_int, [H, FP, c_int, FPP, c_int, FP, c_int, FP]),
     "iwae_generate": (c_int, [H, c_int, FP, FPP, c_int, FP, FP, c_int, FP, c_int, FPP, c_int]),
+    "iwae_binarize": (c_int, [H, FP, c_longlong, POINTER(c_longlong), c_int, FP, FP, c_int]),
     "iwae_posterior": (c_int, [H, FP, c_int, c_int, c_int, FPP, c_int, FP, FPP, c_int, FP, c_int, FPP, c_int,
                                FP, FP, FP]),
     "iwae_impute": (c_int, [H, FP, FP, c_int, c_int, c_int, FPP, c_int, FP, FP, FP, c_int, FP, c_int, FPP, c_int,

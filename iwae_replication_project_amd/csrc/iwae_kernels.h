@@ -958,4 +958,12 @@ hipError_t launch_impute_draw(hipStream_t st, const float* x, const float* mask,
                               const float* u, int n, int xdim, float* out, int ldo, uint64_t seed,
                               const uint64_t* rng_base, int layer);
 
+// ------------------------------- dynamic binarisation (iwae_binarize.hip) ----
+// out[i][j] = (u < v || v >= 1) as 0.0 / 1.0, v = x[perm[i]][j] (perm null: row i), j < xdim; x [n_src][xdim],
+// a perm[i] outside [0, n_src) reads nothing and gives zeros; u: [n][xdim] or null: Philox uniforms (row i,
+// `layer`, column quad j / 4, value j % 4: gen_kernel's layout).  out may be x when perm is null and ldo == xdim.
+// Fewer than 2^32 - 255 (row, quad) threads, else hipErrorInvalidValue.
+hipError_t launch_binarize(hipStream_t st, const float* x, long long n_src, const long long* perm, const float* u,
+                           int n, int xdim, float* out, int ldo, uint64_t seed, const uint64_t* rng_base, int layer);
+
 }  // namespace iwae

@@ -211,6 +211,7 @@ struct Counters {
   long long post = 0, post_lw = 0;       // 17, 18: iwae_posterior second passes: post_kernel launches / layer-wise passes
   long long imp = 0, imp_lw = 0;         // 19, 20: iwae_impute first passes: masked mega_fwd_kernel launches / layer-wise passes
   long long bern_mask = 0;               // 21: pixel-masked Bernoulli output launches (EPI_BERN_MASK) of train steps and bounds
+  long long binarize = 0;                // 22: binarize_kernel launches (iwae_binarize)
 };
 
 // row-chain train engine plan (device resident, per shape; iwae_train.hip)
@@ -4445,6 +4446,29 @@ int iwae_generate(iwae_handle* h, int n, const float* h_top, const float* const*
   return IWAE_OK;
 }
 
+// Dynamic binarisation: one gather-and-draw launch on the caller's buffers (no
+// workspace, no plan), then the noise position's advance.
+int iwae_binarize(iwae_handle* h, const float* x, long long n_src, const long long* perm, int n, const float* u,
+                  float* out, int ld_out) {
+  if (!h) return IWAE_EINVAL;
+  CHK(kernel_status(h));
+  if (!x) return fail(h, IWAE_EINVAL, "x is NULL");
+  if (!out) return fail(h, IWAE_EINVAL, "out is NULL");
+  if (n < 0 || n > (1 << 24)) return fail(h, IWAE_EINVAL, "n must be in [0, 2^24]");
+  if (n_src < 0) return fail(h, IWAE_EINVAL, "n_src must not be negative");
+  if (!perm && n > n_src) return fail(h, IWAE_EINVAL, "n > n_src needs perm");
+  if (ld_out < h->xdim || ld_out > (1 << 22) || (ld_out & 3) || ((uintptr_t)out & 15))
+    return fail(h, IWAE_EINVAL, "out needs x_dim <= ld <= 2^22, a multiple of 4, 16-byte aligned");
+  if ((long long)n * ((h->xdim + 3) >> 2) + 255 >= (1LL << 32))
+    return fail(h, IWAE_EINVAL, "n * ceil(x_dim / 4) must stay below 2^32 - 255 (one launch)");
+  if (n == 0) return IWAE_OK;
+  HIPCHK(launch_binarize(h->stream, x, n_src, perm, u, n, h->xdim, out, ld_out, h->seed, &h->ds->rng[0],
+                         2 * IWAE_MAX_LAYERS + 3));
+  ++h->count.binarize;
+  HIPCHK(launch_rng_advance(h->stream, &h->ds->rng[0]));
+  return IWAE_OK;
+}
+
 // ------------------------------------------------ importance-weighted posterior
 // Plan of post_kernel for this model (iwae_posterior.hip).  LDS buffers: the
 // latents some stage reads, h_0 .. h_{L-2} (h_0 alone when L = 1: ids 0 .. nl-1;
@@ -4857,6 +4881,7 @@ long long iwae_debug_count(const iwae_handle* h, int what) {
     case 19: return h->count.imp;
     case 20: return h->count.imp_lw;
     case 21: return h->count.bern_mask;
+    case 22: return h->count.binarize;
     default: return -1;
   }
 }

@@ -2,7 +2,8 @@
 local-file dataset loaders, stochastic binarisation, the output-bias
 initialiser, and the reference's learning-rate-stage training driver.
 
-Nothing here is on the GPU path; it feeds ``Flexible_Model`` the same arrays
+Nothing here is on the GPU path (train_schedule(binarize=True) hands the
+re-binarisation to the model's device route instead of numpy); it feeds ``Flexible_Model`` the same arrays
 the reference builds from TF datasets (F:147-F:175, E:20-E:31), but only from
 files already on disk -- there is no network.
 """
@@ -85,17 +86,25 @@ def stage_passes(i):
 
 
 def train_schedule(model, x_train, stages=8, batch_size=100, x_test=None, k_test=None, on_stage=None,
-                   save_prefix=None, stochastic_rng=None, passes=stage_passes, verbose=0):
+                   save_prefix=None, stochastic_rng=None, passes=stage_passes, verbose=0, binarize=False):
     """The reference's training driver (E:73-E:97): for stage i = 1..stages set
     the Adam learning rate (E:76), run passes(i) epochs of fit (E:82), then
     optionally evaluate get_training_statistics(x_test, k_test) (E:87),
     call on_stage(i, total_passes, res) and save the weights (E:95) and the
     statistics so far (E:96-E:97: the reference pickles (res1s, res2s); here
     they are JSON, `<save_prefix>.res2.json`).  With stochastic_rng the
-    training set is re-binarised every epoch.  Returns the list of per-stage
-    statistics ((res1, res2) pairs, or None without x_test)."""
+    training set is re-binarised every epoch on the host (numpy).  With
+    binarize=True it is re-binarised every epoch on the device instead: x_train
+    (grey levels) is uploaded to the model's device once and every pass is
+    model.fit(..., binarize=True), one gather-and-draw launch per epoch on the
+    model's noise stream; the two together raise ValueError.  Returns the list
+    of per-stage statistics ((res1, res2) pairs, or None without x_test)."""
+    if binarize and stochastic_rng is not None:
+        raise ValueError("binarize=True (device) and stochastic_rng (host) both re-binarise the training set: "
+                         "pass one of them")
     if model.optimizer is None:
         model.compile()
+    x_dev = model._x(x_train) if binarize else None        # the one upload
     results = []
     total = 0
     for i in range(1, stages + 1):
@@ -103,6 +112,9 @@ def train_schedule(model, x_train, stages=8, batch_size=100, x_test=None, k_test
         model._push_adam()
         n = passes(i)
         for _ in range(n):
+            if binarize:
+                model.fit(x_dev, epochs=1, batch_size=batch_size, verbose=verbose, binarize=True)
+                continue
             xs = stochastic_binarize(x_train, stochastic_rng) if stochastic_rng is not None else x_train
             model.fit(xs, epochs=1, batch_size=batch_size, verbose=verbose)
         total += n

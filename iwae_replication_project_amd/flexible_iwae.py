@@ -29,6 +29,7 @@ Differences a user of the reference should know about (all deliberate):
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import os
 
@@ -480,12 +481,75 @@ class Flexible_Model:
         if n:
             raise _lib.IwaeError(f"{n} in-launch wait(s) gave up")
 
-    def fit(self, x, epochs=1, batch_size=100, shuffle=True, verbose=0, seed=None, mask=None):
+    def _binarize(self, x, perm, u, out):
+        """binarize without the final synchronize (fit's per-epoch call)."""
+        xd = self._x(x)
+        n_src, xdim = xd.shape[0], self.x_dim
+        pt = None
+        if perm is not None:
+            with torch.cuda.stream(self._stream):
+                pt = torch.as_tensor(perm)
+                if pt.dim() != 1 or pt.dtype.is_floating_point or pt.dtype.is_complex or pt.dtype == torch.bool:
+                    raise ValueError(f"perm must be a 1-d integer array, got {tuple(pt.shape)} of {pt.dtype}")
+                pt = pt.to(device=self.device, dtype=torch.int64).contiguous()
+        n = n_src if pt is None else int(pt.shape[0])
+        if n > 1 << 24:
+            raise ValueError("more than 2^24 output rows per call are not supported")
+        ut = None
+        if u is not None:
+            with torch.cuda.stream(self._stream):
+                ut = torch.as_tensor(u).to(device=self.device, dtype=torch.float32).contiguous()
+            if tuple(ut.shape) != (n, xdim):
+                raise ValueError(f"u must be [n={n}, {xdim}], got {tuple(ut.shape)}")
+        ld = (xdim + 3) // 4 * 4
+        if out is None:
+            with torch.cuda.stream(self._stream):
+                out = torch.empty(n, ld, device=self.device)[:, :xdim]
+        else:
+            if (not isinstance(out, torch.Tensor) or out.device != self.device or out.dtype != torch.float32
+                    or tuple(out.shape) != (n, xdim) or (xdim > 1 and out.stride(1) != 1)):
+                raise ValueError(f"out must be a float32 tensor [n={n}, {xdim}] on {self.device} with unit column "
+                                 "stride")
+            if n > 1:
+                ld = out.stride(0)
+        if n > 0:
+            rc = self._lib.iwae_binarize(self._h, _lib.fptr(xd), n_src,
+                                         None if pt is None else ctypes.cast(ctypes.c_void_p(pt.data_ptr()),
+                                                                             ctypes.POINTER(ctypes.c_longlong)),
+                                         n, _lib.fptr(ut), _lib.fptr(out), int(ld))
+            if rc != 0:              # the shapes passed above: what is left is a layout the library refuses
+                msg = self._lib.iwae_last_error(self._h)
+                raise _lib.IwaeError(f"libiwae_hip error {rc}: {msg.decode() if msg else 'unknown error'}")
+        return out
+
+    def binarize(self, x, perm=None, u=None, out=None):
+        """Dynamic binarisation on the device (iwae_binarize; the stochastic
+        "MNIST" setting, PDF p7 s3.1): row i of the result is drawn from the
+        grey levels ``x[perm[i]]`` (``perm``: any 1-d integer tensor or array,
+        converted to int64 on the device; None: every row of x in order), pixel
+        = (u < x or x >= 1) as 0.0 / 1.0 -- Bernoulli(x), with 0/1 images a fixed
+        point; an index outside x gives a row of zeros.  One launch, one advance
+        of the model's noise position.  Returns a device float32 [n, x_dim]
+        tensor on the model's stream.  ``u``: [n, x_dim] uniforms in [0, 1)
+        instead of the device's Philox draws (tests).  ``out``: a float32 device
+        tensor [n, x_dim] to write into (unit column stride; its row stride is
+        the leading dimension: a multiple of 4, its storage 16-byte aligned,
+        else IwaeError); ``out=x`` binarises in place when ``perm`` is None."""
+        out = self._binarize(x, perm, u, out)
+        self._stream.synchronize()
+        return out
+
+    def fit(self, x, epochs=1, batch_size=100, shuffle=True, verbose=0, seed=None, mask=None, binarize=False):
         """Keras-style loop (E:82): per epoch shuffle, batches of batch_size
         (last partial batch included), one train step each (the whole batches
         through train_steps, the partial one through train_step).  ``mask``
         [N, x_dim]: training on incomplete images (see train_step); the epoch's
-        permutation is applied to x and mask alike."""
+        permutation is applied to x and mask alike.  ``binarize``: x holds grey
+        levels and every epoch trains on a fresh dynamic binarisation of it
+        (see binarize): one iwae_binarize launch per epoch gathers by the
+        epoch's permutation and draws the pixels into a buffer reused across
+        epochs, then the epoch's steps follow (noise: one advance for the
+        binarisation, then the steps')."""
         xd = self._x(x)
         N = xd.shape[0]
         md = self._mask(mask, N) if mask is not None else None
@@ -493,10 +557,14 @@ class Flexible_Model:
         if seed is not None:
             g.manual_seed(int(seed))
         hist = []
+        xb = None
         for ep in range(int(epochs)):
             perm = torch.randperm(N, generator=g) if shuffle else torch.arange(N)
             with torch.cuda.stream(self._stream):
-                xs = xd[perm.to(self.device)] if shuffle else xd
+                if binarize:
+                    xs = xb = self._binarize(xd, perm if shuffle else None, None, xb)
+                else:
+                    xs = xd[perm.to(self.device)] if shuffle else xd
                 ms = None if md is None else (md[perm.to(self.device)] if shuffle else md)
                 losses = torch.zeros((N + batch_size - 1) // batch_size, device=self.device)
             nfull = N // batch_size
