@@ -496,6 +496,66 @@ int iwae_forward_backward_masked(iwae_handle* h, const iwae_loss_config* lc, con
                                  int B, const float* const* eps, int n_eps, float* loss_dev);
 int iwae_bound_masked(iwae_handle* h, const iwae_loss_config* lc, const float* x, const float* mask, int B,
                       const float* const* eps, int n_eps, float* value_dev);
+/* Densities of caller-supplied latents: Decoder.get_log_pxIh / get_log_ph /
+ * get_log_pxh (F:123-F:145), Decoder.call's probabilities (F:100-F:105) and the
+ * encoder's log q (F:60 / F:70) at latents the caller chose -- prior samples,
+ * another model's samples, a resampled or perturbed set, the state of an MCMC
+ * chain.  Every pointer is a device pointer.  lat[i] is [k][N][d_i], sample-
+ * major (the reference's layout of h_i and this ABI's of eps); n_lat must equal
+ * L.  Row (b, s) is scored at h_i = lat[i][(s N + b) d_i ..]:
+ *   log_q[b][s]  = log N(h_1; enc_0(x_b)) + sum_{i>=1} log N(h_{i+1}; enc_i(h_i))
+ *   log_ph[b][s] = log N(h_L; 0, 1) + sum_j log N(h_{L-1-j}; dec_j(h_{L-j}))
+ *   log_px[b][s] = sum_pixels log Bern(x_b | p(h_1)),  p = sigmoid(logit) (1 - 1e-6) + 1e-7
+ * each [N][k] (image-major, as iwae_log_weights' lw), so log_ph + log_px -
+ * log_q is the row's log weight; probs [N k][ld_probs], row b k + s: p(h_1) of
+ * that row (iwae_generate's ld rules: x_dim <= ld <= 2^22, a multiple of 4,
+ * 16-byte aligned, columns [x_dim, ld) not written).  Every output is optional,
+ * not all of them NULL; x may be NULL when neither log_q nor log_px is asked
+ * for.  Work an absent output needs is left out of the launch (log_ph alone
+ * runs no encoder and no output-MLP stage), and a present output's value does
+ * not depend on which others are present, bit for bit.  Each density is
+ * evaluated at the caller's float32 latent; the bf16 hi / lo split of a latent
+ * feeds the matrix products only.  Images run in chunks of `chunk` images (0:
+ * IWAE_KNOB_NLL_IMGS, else floor(nll_rows / k), at least 1); a chunk holds all
+ * k rows of its images; k <= 2^20, a chunk at most 2^30 rows; the result does
+ * not depend on chunk, bit for bit.  Paths: one score_kernel launch per chunk
+ * (mega_fwd_kernel's pipeline and LDS plan with every head a density head,
+ * the latents' tiles loaded by its prologue; the weight-ring kernel is not
+ * used, whatever k) where iwae_posterior's fused first pass applies; else, and
+ * under iwae_set_precision(h, 0) or iwae_set_path(h, 1), layer-wise: one
+ * gather launch of the latents into the workspace's rows, then per layer the
+ * GEMMs and the density kernel, the output MLP with the Bernoulli epilogue and
+ * its row sums; probs: the output Dense's logits stored into the caller's
+ * buffer and turned into probabilities in place.  A path that does not apply
+ * is never an error.  Rows are independent: non-finite latents in one row give
+ * non-finite outputs for that row only.  Nothing is drawn and the noise
+ * position stays; weights, Adam state, captured graphs and engine plans are
+ * untouched; the handle's sticky error (iwae_status) is returned before any
+ * work is enqueued.  IWAE_EINVAL: every output NULL, x NULL with log_q or
+ * log_px asked for, n_lat != L, a NULL lat[i], N <= 0 or k <= 0, k or the chunk
+ * above the limits, a bad ld_probs or a misaligned probs. */
+int iwae_score(iwae_handle* h, const float* x, int N, int k, int chunk,
+               const float* const* lat, int n_lat,
+               float* log_q, float* log_ph, float* log_px,
+               float* probs, int ld_probs);
+/* Encoder.call (F:56-F:75): k samples of q(h|x) per image, with device noise
+ * (eps NULL, n_eps 0) or injected eps[i] [k][N][d_i].  lat_out[i] [k][N][d_i],
+ * sample-major (n_lat 0 or L); log_q [N][k]; loc_top / scale_top: the
+ * parameters of distributions[-1] (F:75), [N][d_1] when L = 1 and [k][N][d_L]
+ * otherwise, scale = exp(zs) + 1e-6.  Every output is optional, not all of
+ * them NULL.  Chunks as iwae_score's.  The rows have to reach memory, so the
+ * call runs on the layer-wise kernels whatever the path: per encoder layer the
+ * three GEMMs and the sampling kernel, then one relayout launch ([rows][ld] ->
+ * [k][N][d]); no decoder work.  With device noise the noise position advances
+ * once per chunk, as a forward pass's does, and Philox is addressed as the
+ * layer-wise forward does (row in chunk, layer id i, column quad): a layer-wise
+ * iwae_log_weights call of the same seed, N and k (one chunk) weighs exactly
+ * these samples.  State and error rules are iwae_score's otherwise (x is
+ * required). */
+int iwae_encode(iwae_handle* h, const float* x, int N, int k, int chunk,
+                const float* const* eps, int n_eps,
+                float* const* lat_out, int n_lat, float* log_q,
+                float* loc_top, float* scale_top);
 /* get_NLL_without_inactive_units (F:466-F:494): like iwae_nll / iwae_nll_eps
  * with every sampled h_i multiplied by masks[i] ([dev], d_i floats of 0/1). */
 int iwae_nll_masked(iwae_handle* h, const float* x, int N, int k, const float* const* eps,
@@ -543,7 +603,9 @@ double iwae_workspace_bytes(const iwae_handle* h);
  * output launches (the tiled GEMM's masked epilogue) issued by
  * iwae_train_step_masked / iwae_forward_backward_masked / iwae_bound_masked (a
  * captured step counts once, at capture); 22 binarize_kernel launches issued by
- * iwae_binarize (one per call with n > 0); -1 for an unknown id. */
+ * iwae_binarize (one per call with n > 0); 23 fused iwae_score launches
+ * (score_kernel, one per chunk), 24 its layer-wise passes (one per chunk); -1
+ * for an unknown id. */
 long long iwae_debug_count(const iwae_handle* h, int what);
 /* Live kernel timing: bracket every launch of one kernel class with HIP events
  * on the handle's stream -- a GEMM class (kind: 0 forward, 1 backward-data,

@@ -578,6 +578,49 @@ hipError_t launch_mega_fwd(hipStream_t st, const MgLaunch& L, int rt, int waves,
 hipError_t launch_mega_fwd_masked(hipStream_t st, const MgLaunch& L, int rt, int waves, size_t lds_bytes);
 hipError_t mega_setup_attributes();
 
+// ------------------------ densities of caller-supplied latents (iwae_score) ----
+// score_kernel (iwae_score.hip): mega_fwd_kernel's pipeline with every latent
+// given.  The prologue loads the h_i tiles the stage list reads from the
+// caller's [k][N][d_i] buffers into their LDS buffers (hi / lo planes, ones
+// column, zero padding); every head is a density head -- encoder heads
+// (MG_DENSQ) add log N(h_i; enc_{i-1}(h_{i-1})) to the row's log q, prior heads
+// (MG_DENSP) add log N(h_t; dec_j(.)) to its log p(h) -- whose target is the
+// caller's f32 value, read from memory (the split LDS copy feeds the matrix
+// products only); the output stage (MG_BERNS) adds the Bernoulli terms to
+// log p(x|h) and / or stores the probabilities from its accumulators.  The
+// three sums are stored separately.  The 2 L chains are independent, so the
+// stage list holds only the chains of the outputs asked for, the first prior
+// chain ahead of the encoder's (it reads h_L from the scratch buffer the
+// encoder chains write).  Stage fields: MgStage's, with layer = the target
+// latent's index for the density heads.  The base's eps / eps_N / eps_i0 are
+// the latents and their addressing (eps_s0 = 0), lw is unused.
+enum ScAct { MG_DENSQ = 5, MG_DENSP = 6, MG_BERNS = 7 };
+struct ScLaunch : MgLaunch {
+  int n_lat;                         // stochastic layers
+  int lat_d[8], lat_buf[8];          // latent widths; LDS buffer of h_i's tile, -1: no stage reads it
+  int lat_next_k[8];                 // padded K of the tile's readers
+  int want_q, want_ph;               // prologue: log N(h_1; P0) into log q / log N(h_L; 0, 1) into log p(h)
+  float* log_q; float* log_ph; float* log_px;   // out: [rows] each, or null
+  float* probs; int ld_probs;        // out: p(h_1) of the rows [rows][ld_probs], or null
+};
+hipError_t launch_score(hipStream_t st, const ScLaunch& L, int rt, int waves, size_t lds_bytes);
+hipError_t score_setup_attributes();
+
+// Relayouts between the callers' sample-major [k][N][d] buffers and the
+// workspace's image-major rows (iwae_score.hip).  Segment g, for b < n, s < k,
+// j < d: gather: rows[(b k + s) ld + j] = ext[((s N) + i0 + b) d + j]; else
+// ext[...] = f(rows[(b k + s) ld + col0 + j]), f the identity or (expo)
+// exp(.) + 1e-6 (a head's scale).  img: the rows are image rows, ext is [N][d]:
+// ext[(i0 + b) d + j] = f(rows[b ld + col0 + j]).
+struct ScSeg { float* rows; int ld, col0, d; float* ext; int expo, img; };
+struct ScRelayout {
+  ScSeg seg[2 * 8 + 2]; int nseg;
+  int n, k, N, i0, gather;
+};
+hipError_t launch_score_relayout(hipStream_t st, const ScRelayout& a);
+// out[r] = the row's Bernoulli partial sums in column order (forward_core's row sum), r < rows
+hipError_t launch_score_rowsum(hipStream_t st, const float* part, int ldpart, int npart, int rows, float* out);
+
 // ------------------------------- weight-ring k-sample forward (NLL) ----
 // nring_kernel (iwae_nring.hip): the same per-row work as mega_fwd_kernel for
 // 1- and 2-layer models, activations of 16 rows per wave in registers, the

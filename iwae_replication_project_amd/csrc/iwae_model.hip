@@ -212,6 +212,7 @@ struct Counters {
   long long imp = 0, imp_lw = 0;         // 19, 20: iwae_impute first passes: masked mega_fwd_kernel launches / layer-wise passes
   long long bern_mask = 0;               // 21: pixel-masked Bernoulli output launches (EPI_BERN_MASK) of train steps and bounds
   long long binarize = 0;                // 22: binarize_kernel launches (iwae_binarize)
+  long long score = 0, score_lw = 0;     // 23, 24: iwae_score chunks: score_kernel launches / layer-wise passes
 };
 
 // row-chain train engine plan (device resident, per shape; iwae_train.hip)
@@ -818,13 +819,14 @@ static int encoder_fwd(iwae_handle* h, const Plan& P, const EpsSet& E, bool trai
   return IWAE_OK;
 }
 
-// Layer-wise prior log p(h) of the M sampled rows into h->logp (F:134-F:142)
-static int prior_fwd(iwae_handle* h, int M) {
+// Layer-wise prior log p(h) of the M sampled rows into h->logp, or out (F:134-F:142)
+static int prior_fwd(iwae_handle* h, int M, float* out = nullptr) {
   const int L = h->L;
+  if (!out) out = h->logp;
   {
     GaussArgs g{};
     g.d = h->enc[L - 1].d; g.H = h->h[L - 1].p; g.ldH = h->h[L - 1].ld;
-    g.out = h->logp; g.accumulate = 0; g.M = M;
+    g.out = out; g.accumulate = 0; g.M = M;
     HIPCHK(launch_gauss_fwd(h->stream, 2, g));
   }
   for (int i = 0; i < L - 1; ++i) {
@@ -832,7 +834,7 @@ static int prior_fwd(iwae_handle* h, int M) {
     GaussArgs g{};
     g.P = h->db[i].P.p; g.ldP = h->db[i].P.ld; g.prow_div = 1; g.d = h->dec[i].d;
     g.H = h->h[L - 2 - i].p; g.ldH = h->h[L - 2 - i].ld;
-    g.out = h->logp; g.accumulate = 1; g.M = M;
+    g.out = out; g.accumulate = 1; g.M = M;
     HIPCHK(launch_gauss_fwd(h->stream, 1, g));
   }
   return IWAE_OK;
@@ -3261,6 +3263,7 @@ iwae_handle* iwae_create(const iwae_config* cfg, int device) {
   h->fx_lo = h->fx_hi + h->fx_elems;
   e = rb_setup_attributes();
   if (e == hipSuccess) e = mega_setup_attributes();
+  if (e == hipSuccess) e = score_setup_attributes();
   if (e == hipSuccess) e = nring_setup_attributes();
   if (e == hipSuccess) e = smallm_setup_attributes();
   if (e == hipSuccess) e = tc_setup_attributes();
@@ -4819,6 +4822,224 @@ int iwae_impute(iwae_handle* h, const float* x, const float* mask, int N, int k,
                         h_sir, n_sir, weights, ess, logpx);
 }
 
+// ------------------------------------------------ scoring given latents
+// Images per chunk of iwae_score / iwae_encode (iwae_posterior's rule); 0 with the error set.
+static int score_chunk(iwae_handle* h, int N, int k, int chunk) {
+  if (N <= 0 || k <= 0) { fail(h, IWAE_EINVAL, "N and k must be positive"); return 0; }
+  if (k > (1 << 20)) { fail(h, IWAE_EINVAL, "k above 2^20 per image is not supported"); return 0; }
+  if (chunk <= 0) chunk = h->tune.nll_imgs;
+  const long long imgs_ll = chunk > 0 ? chunk : std::max<long long>(1, h->tune.nll_rows / k);
+  const int imgs = (int)std::min<long long>(imgs_ll, N);
+  if ((long long)imgs * k > (1LL << 30)) { fail(h, IWAE_EINVAL, "chunk * k above 2^30 sample rows"); return 0; }
+  return imgs;
+}
+
+// score_kernel's launch from mega_fwd_kernel's plan MG (same buffers, row
+// tiles and LDS): the chains of the outputs asked for, heads as density heads.
+// mega_plan's stage order: encoder layers 1 .. L-1, prior layers 0 .. L-2, the
+// output MLP, three stages each.
+static void score_plan(const iwae_handle* h, const MgLaunch& MG, bool q, bool ph, bool out, ScLaunch& S) {
+  const int L = h->L;
+  static_cast<MgLaunch&>(S) = MG;
+  S.nst = 0;
+  S.n_lat = L;
+  for (int i = 0; i < 8; ++i) { S.lat_d[i] = i < L ? h->enc[i].d : 0; S.lat_buf[i] = -1; S.lat_next_k[i] = 0; }
+  auto chain = [&](int s0, int src, int act, int target) {      // src: the latent the chain reads
+    for (int u = 0; u < 3; ++u) S.st[S.nst + u] = MG.st[s0 + u];
+    S.lat_buf[src] = MG.st[s0].in_buf;
+    S.lat_next_k[src] = std::max(S.lat_next_k[src], MG.st[s0].ldk);
+    MgStage& H = S.st[S.nst + 2];
+    H.act = act; H.layer = target; H.stdnormal = 0;
+    S.nst += 3;
+  };
+  const int e0 = 0, d0 = 3 * (L - 1), o0 = 6 * (L - 1);
+  // (the first prior chain reads h_L from the scratch buffer the encoder chains write: it goes first)
+  if (ph && L > 1) chain(d0, L - 1, MG_DENSP, L - 2);
+  for (int i = 1; q && i < L; ++i) chain(e0 + 3 * (i - 1), i - 1, MG_DENSQ, i);
+  for (int j = 1; ph && j < L - 1; ++j) chain(d0 + 3 * j, L - 1 - j, MG_DENSP, L - 2 - j);
+  if (out) chain(o0, 0, MG_BERNS, 0);
+  S.want_q = q ? 1 : 0;
+  S.want_ph = ph ? 1 : 0;
+}
+
+int iwae_score(iwae_handle* h, const float* x, int N, int k, int chunk, const float* const* lat, int n_lat,
+               float* log_q, float* log_ph, float* log_px, float* probs, int ld_probs) {
+  if (!h) return IWAE_EINVAL;
+  CHK(kernel_status(h));
+  const int L = h->L;
+  if (!log_q && !log_ph && !log_px && !probs) return fail(h, IWAE_EINVAL, "every output is NULL");
+  if (!x && (log_q || log_px)) return fail(h, IWAE_EINVAL, "x is NULL (log_q and log_px need the images)");
+  if (n_lat != L || !lat)
+    return fail(h, IWAE_EINVAL, "expected " + std::to_string(L) + " latent buffers (one per stochastic layer), got " +
+                                   std::to_string(n_lat));
+  for (int i = 0; i < L; ++i)
+    if (!lat[i]) return fail(h, IWAE_EINVAL, "NULL latent buffer");
+  if (probs && (ld_probs < h->xdim || ld_probs > (1 << 22) || (ld_probs & 3) || ((uintptr_t)probs & 15)))
+    return fail(h, IWAE_EINVAL, "probs needs x_dim <= ld <= 2^22, a multiple of 4, 16-byte aligned");
+  const int imgs = score_chunk(h, N, k, chunk);
+  if (!imgs) return IWAE_EINVAL;
+  const bool want_out = log_px || probs;
+  MgLaunch MG;
+  int mg_rt = 0, mg_waves = 8;
+  size_t mg_lds = 0;
+  const bool fused = h->x3 && h->nll_fused && h->path != 1 && !h->masked && mega_plan(h, MG, mg_rt, mg_waves, mg_lds);
+  const int rows = imgs * k;
+  // fused: the first encoder layer runs once per group of images, as nll_core's; no row buffer is used
+  const int sup = fused ? std::min(N, imgs * std::max(1, kNllFirstLayerImages / imgs)) : imgs;
+  CHK(ensure_capacity(h, sup, fused ? 1 : rows, false));
+  if (h->x3) CHK(ensure_wsplit(h));
+  if (fused) CHK(ensure_fx(h));
+  ScLaunch SC;
+  if (fused) {
+    score_plan(h, MG, log_q != nullptr, log_ph != nullptr, want_out, SC);
+    for (int i = 0; i < 8; ++i) SC.eps[i] = i < L ? lat[i] : nullptr;
+    SC.eps_N = N; SC.eps_s0 = 0;
+    SC.rng_base = nullptr; SC.seed = 0; SC.lw = nullptr;
+  }
+  const size_t wbytes = (size_t)h->xdim * sizeof(float);
+  int u0 = 0;                                    // first image of the current first-layer group (fused)
+  for (int i0 = 0; i0 < N; i0 += imgs) {
+    const int n = std::min(imgs, N - i0), M = n * k;
+    const size_t r0 = (size_t)i0 * k;            // the chunk's first row of the [N][k] outputs
+    if (x && (!fused || i0 - u0 >= sup || i0 == 0)) {
+      u0 = i0;
+      const int ng = std::min(sup, N - i0);
+      HIPCHK(hipMemcpy2DAsync(h->x_in.p, (size_t)h->x_in.ld * sizeof(float), x + (size_t)i0 * h->xdim, wbytes, wbytes,
+                              ng, hipMemcpyDeviceToDevice, h->stream));
+      if (log_q) CHK(stoch_fwd(h, h->enc[0], h->x_in, ng, h->eb[0]));
+    }
+    const int io = x ? i0 - u0 : 0;              // the chunk's rows in x_in / eb[0]
+    if (fused) {
+      SC.rows = M; SC.kS = k; SC.eps_i0 = i0;
+      SC.P0 = h->eb[0].P.p + (size_t)io * h->eb[0].P.ld; SC.ldP0 = h->eb[0].P.ld;
+      SC.x = h->x_in.p + (size_t)io * h->x_in.ld; SC.ldx = h->x_in.ld;
+      SC.log_q = log_q ? log_q + r0 : nullptr;
+      SC.log_ph = log_ph ? log_ph + r0 : nullptr;
+      SC.log_px = log_px ? log_px + r0 : nullptr;
+      SC.probs = probs ? probs + r0 * ld_probs : nullptr; SC.ld_probs = ld_probs;
+      HIPCHK(launch_score(h->stream, SC, mg_rt, mg_waves, mg_lds));
+      ++h->count.score;
+      continue;
+    }
+    // ---- layer-wise: the latents into the workspace's rows, then forward_core's launches as density passes
+    ++h->count.score_lw;
+    ScRelayout G{};
+    G.n = n; G.k = k; G.N = N; G.i0 = i0; G.gather = 1;
+    for (int i = 0; i < L; ++i)
+      G.seg[G.nseg++] = ScSeg{h->h[i].p, h->h[i].ld, 0, h->enc[i].d, const_cast<float*>(lat[i]), 0, 0};
+    HIPCHK(launch_score_relayout(h->stream, G));
+    for (int i = 0; log_q && i < L; ++i) {
+      if (i > 0) CHK(stoch_fwd(h, h->enc[i], h->h[i - 1], M, h->eb[i]));
+      GaussArgs g{};
+      g.P = h->eb[i].P.p; g.ldP = h->eb[i].P.ld; g.prow_div = i == 0 ? k : 1; g.d = h->enc[i].d;
+      g.H = h->h[i].p; g.ldH = h->h[i].ld;
+      g.out = log_q + r0; g.accumulate = i > 0; g.M = M;
+      HIPCHK(launch_gauss_fwd(h->stream, 1, g));
+    }
+    if (log_ph) CHK(prior_fwd(h, M, log_ph + r0));
+    if (want_out) {
+      CHK(gemm_fwd(h, EPI_TANH, h->h[0], M, h->dense[h->o1], h->ob.y1));
+      CHK(gemm_fwd(h, EPI_TANH, h->ob.y1, M, h->dense[h->o2], h->ob.y2));
+    }
+    if (log_px) {
+      GemmArgs ex{};
+      ex.aux = h->x_in.p; ex.ldaux = h->x_in.ld; ex.x_row_div = k;
+      ex.part = h->part; ex.part2 = h->part2; ex.ldpart = h->ldpart;
+      ex.wa = 1.f; ex.wb = 0.f;
+      Mat none;
+      CHK(gemm_fwd(h, EPI_BERN, h->ob.y2, M, h->dense[h->o3], none, ex));
+      HIPCHK(launch_score_rowsum(h->stream, h->part, h->ldpart, h->npart, M, log_px + r0));
+    }
+    if (probs) {
+      // the output Dense's logits into the caller's rows, turned into probabilities in place
+      Mat pm;
+      pm.p = probs + r0 * ld_probs; pm.ld = ld_probs;
+      CHK(gemm_fwd(h, EPI_STORE, h->ob.y2, M, h->dense[h->o3], pm));
+      HIPCHK(launch_bern_probs(h->stream, pm.p, M, h->xdim, ld_probs));
+    }
+  }
+  return IWAE_OK;
+}
+
+// Encoder.call (F:56-F:75): k samples of q(h|x) per image on the layer-wise
+// kernels (the rows have to reach memory), relayouted into the reference's
+// sample-major buffers.
+int iwae_encode(iwae_handle* h, const float* x, int N, int k, int chunk, const float* const* eps, int n_eps,
+                float* const* lat_out, int n_lat, float* log_q, float* loc_top, float* scale_top) {
+  if (!h) return IWAE_EINVAL;
+  CHK(kernel_status(h));
+  const int L = h->L;
+  if (!x) return fail(h, IWAE_EINVAL, "x is NULL");
+  auto ptrs_ok = [&](const float* const* a, int n, const char* what) {
+    if (n == 0) return IWAE_OK;
+    if (n != L || !a)
+      return fail(h, IWAE_EINVAL, std::string("expected ") + std::to_string(L) + " " + what + " buffers (one per "
+                                  "stochastic layer), got " + std::to_string(n));
+    for (int i = 0; i < L; ++i)
+      if (!a[i]) return fail(h, IWAE_EINVAL, std::string("NULL ") + what + " buffer");
+    return IWAE_OK;
+  };
+  CHK(ptrs_ok(eps, n_eps, "eps"));
+  CHK(ptrs_ok(lat_out, n_lat, "latent"));
+  if (n_lat == 0 && !log_q && !loc_top && !scale_top) return fail(h, IWAE_EINVAL, "every output is NULL");
+  const int imgs = score_chunk(h, N, k, chunk);
+  if (!imgs) return IWAE_EINVAL;
+  const bool injected = n_eps > 0;
+  const int rows = imgs * k;
+  CHK(ensure_capacity(h, imgs, rows, false));
+  if (h->x3) CHK(ensure_wsplit(h));
+  // a chunk's [k][n][d] noise, contiguous, in iwae_posterior's workspace
+  const bool gather = injected && imgs < N;
+  size_t off = 0, o_eps[IWAE_MAX_LAYERS] = {};
+  for (int i = 0; i < L; ++i) {
+    o_eps[i] = off;
+    off += gather ? ((size_t)rows * h->enc[i].d + 63) & ~size_t(63) : 0;
+  }
+  if (off * sizeof(float) > h->post_ws_bytes) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (h->post_ws) (void)hipFree(h->post_ws);
+    h->post_ws = nullptr;
+    h->post_ws_bytes = 0;
+    HIPCHK(hipMalloc(&h->post_ws, off * sizeof(float)));
+    h->post_ws_bytes = off * sizeof(float);
+  }
+  float* ws = reinterpret_cast<float*>(h->post_ws);
+  const size_t wbytes = (size_t)h->xdim * sizeof(float);
+  for (int i0 = 0; i0 < N; i0 += imgs) {
+    const int n = std::min(imgs, N - i0);
+    HIPCHK(hipMemcpy2DAsync(h->x_in.p, (size_t)h->x_in.ld * sizeof(float), x + (size_t)i0 * h->xdim, wbytes, wbytes, n,
+                            hipMemcpyDeviceToDevice, h->stream));
+    Plan P;
+    P.B = n; P.Bimg = n; P.Bsplit = n; P.kS = k;
+    EpsSet E;
+    std::memset(&E, 0, sizeof(E));
+    for (int i = 0; injected && i < L; ++i) {
+      E.a[i] = eps[i];
+      if (gather) {                              // sample s of the chunk's images: n * d floats at (s * N + i0) * d
+        const size_t rb = (size_t)n * h->enc[i].d * sizeof(float);
+        HIPCHK(hipMemcpy2DAsync(ws + o_eps[i], rb, eps[i] + (size_t)i0 * h->enc[i].d,
+                                (size_t)N * h->enc[i].d * sizeof(float), rb, k, hipMemcpyDeviceToDevice, h->stream));
+        E.a[i] = ws + o_eps[i];
+      }
+    }
+    CHK(encoder_fwd(h, P, E, false));
+    ScRelayout G{};
+    G.n = n; G.k = k; G.N = N; G.i0 = i0; G.gather = 0;
+    for (int i = 0; n_lat > 0 && i < L; ++i)
+      G.seg[G.nseg++] = ScSeg{h->h[i].p, h->h[i].ld, 0, h->enc[i].d, lat_out[i], 0, 0};
+    const Mat& PT = h->eb[L - 1].P;              // (mu | zs) of distributions[-1] (F:75): image rows when L = 1
+    const int dT = h->enc[L - 1].d;
+    if (loc_top) G.seg[G.nseg++] = ScSeg{PT.p, PT.ld, 0, dT, loc_top, 0, L == 1};
+    if (scale_top) G.seg[G.nseg++] = ScSeg{PT.p, PT.ld, dT, dT, scale_top, 1, L == 1};
+    HIPCHK(launch_score_relayout(h->stream, G));
+    if (log_q)
+      HIPCHK(hipMemcpyAsync(log_q + (size_t)i0 * k, h->logq, (size_t)n * k * sizeof(float), hipMemcpyDeviceToDevice,
+                            h->stream));
+    if (!injected) HIPCHK(launch_rng_advance(h->stream, &h->ds->rng[0]));
+  }
+  return IWAE_OK;
+}
+
 // get_NLL_without_inactive_units (F:466-F:494): k-sample log p(x) with every
 // sampled h_i multiplied by its 0/1 active-unit mask masks[i] ([dev], d_i).
 int iwae_nll_masked(iwae_handle* h, const float* x, int N, int k, const float* const* eps, int n_eps,
@@ -4882,6 +5103,8 @@ long long iwae_debug_count(const iwae_handle* h, int what) {
     case 20: return h->count.imp_lw;
     case 21: return h->count.bern_mask;
     case 22: return h->count.binarize;
+    case 23: return h->count.score;
+    case 24: return h->count.score_lw;
     default: return -1;
   }
 }

@@ -171,6 +171,56 @@ class _Decoder:
     def generate_x(self, h, eps=None):
         return self._model().generate_x(h, eps=eps)
 
+    def __call__(self, h):
+        """Decoder.call (F:100-F:105): (probs, pxIh) of the given latents, probs
+        [n, B, x_dim]; pxIh carries ``.probs`` (the Bernoulli's parameter)."""
+        probs = self._model().score(None, h, want=("probs",))["probs"]
+        return probs, _Bernoulli(probs)
+
+    def get_log_pxIh(self, x, h):
+        """F:123-F:129: log p(x | h_1), [n, B]."""
+        return self._model().score(x, h, want=("log_px",))["log_px"]
+
+    def get_log_ph(self, h):
+        """F:131-F:142: log p(h), [n, B]."""
+        return self._model().score(None, h, want=("log_ph",))["log_ph"]
+
+    def get_log_pxh(self, x, h):
+        """F:144-F:145: log p(x, h) = log p(x | h_1) + log p(h), [n, B]."""
+        out = self._model().score(x, h, want=("log_ph", "log_px"))
+        return out["log_px"] + out["log_ph"]
+
+
+class _Bernoulli:
+    """The thin stand-in for the reference's ``pxIh`` (F:104): its ``probs``."""
+
+    def __init__(self, probs):
+        self.probs = probs
+
+
+class _Normal:
+    """The thin stand-in for the reference's ``q_top`` (F:75): ``loc`` and ``scale``."""
+
+    def __init__(self, loc, scale):
+        self.loc, self.scale = loc, scale
+
+
+class _Encoder:
+    """``model.encoder``: the reference's ``mdl.encoder(x, n_samples)`` (F:56-F:75)
+    forwarded to the model (held weakly: no reference cycle)."""
+
+    def __init__(self, model):
+        import weakref
+        self._model = weakref.ref(model)
+        self.n_stochastic = len(model.n_hidden_encoder)
+
+    def __call__(self, x, n_samples, eps=None, chunk=0):
+        """(h, log_qhIx, q_top): h a list of [n_samples, B, d_i] device tensors,
+        log_qhIx [n_samples, B], q_top with ``.loc`` / ``.scale`` ([B, d_1] when
+        L = 1, [n_samples, B, d_L] otherwise).  ``eps``: L arrays [n_samples, B,
+        d_i] (default: device noise, which advances the noise position)."""
+        return self._model()._encode(x, n_samples, eps, chunk)
+
 
 class Flexible_Model:
     """HIP-backed ``Flexible_Model`` (F:177-F:545)."""
@@ -234,7 +284,8 @@ class Flexible_Model:
         self.set_weights(glorot_weights(self.dense, rng, resolve_dataset_bias(dataset_bias, x_dim)))
         self._loss_buf = torch.zeros(1, device=self.device)
         self._scratch = torch.zeros(1, device=self.device)
-        self.decoder = _Decoder(self)                         # mdl.decoder.generate_x(h), F:107-F:119
+        self.decoder = _Decoder(self)                         # mdl.decoder(h), .generate_x(h), .get_log_*; F:100-F:145
+        self.encoder = _Encoder(self)                         # mdl.encoder(x, n_samples), F:56-F:75
 
     # ------------------------------------------------------------- plumbing
     def set_seed(self, seed):
@@ -882,6 +933,89 @@ class Flexible_Model:
         out = {"h_mean": hm, "h_sir": hs, "probs": probs[:, :self.x_dim] if probs is not None else None,
                "weights": wts, "ess": ess, "log_px": lpx}
         return {name: out[name] for name in want}
+
+    # ------------------------------------------------ scoring given latents
+    SCORE_OUTPUTS = ("log_q", "log_ph", "log_px", "probs")
+
+    def _latents(self, h):
+        """L latent arrays [n, B, d_i] as contiguous device tensors; (tensors, n, B)."""
+        h = list(h)
+        dims = self.n_latent_encoder
+        if len(h) != len(dims):
+            raise ValueError(f"expected {len(dims)} latent arrays (one per stochastic layer), got {len(h)}")
+        ts = []
+        with torch.cuda.stream(self._stream):
+            for i, v in enumerate(h):
+                t = torch.as_tensor(v).to(device=self.device, dtype=torch.float32, non_blocking=True).contiguous()
+                if t.dim() != 3 or t.shape[2] != dims[i] or (ts and tuple(t.shape[:2]) != tuple(ts[0].shape[:2])):
+                    raise ValueError(f"h[{i}] must be [n_samples, B, d={dims[i]}] like the others, got {tuple(t.shape)}")
+                ts.append(t)
+        return ts, int(ts[0].shape[0]), int(ts[0].shape[1])
+
+    def score(self, x, h, want=("log_q", "log_ph", "log_px"), chunk=0):
+        """Densities of caller-supplied latents (iwae_score).  ``h``: L arrays or
+        tensors [n_samples, B, d_i] (the reference's layout of h_i).  Returns a
+        dict of device tensors with the entries named in ``want``, each
+        [n_samples, B] like the reference's: ``"log_q"`` = log q(h|x) (F:60 /
+        F:70), ``"log_ph"`` = log p(h) (F:134-F:142), ``"log_px"`` = log p(x|h_1)
+        (F:123-F:129); ``"log_w"`` = log_ph + log_px - log_q is added when all
+        three are asked for; ``"probs"`` [n_samples, B, x_dim]: p(h_1), the first
+        item of the decoder's call.  ``x`` may be None when neither log_q nor
+        log_px is asked for.  Nothing is drawn; ``chunk``: images per chunk (0:
+        automatic)."""
+        want = (want,) if isinstance(want, str) else tuple(want)
+        bad = [w for w in want if w not in self.SCORE_OUTPUTS]
+        if bad or not want:
+            raise ValueError(f"want must name some of {self.SCORE_OUTPUTS}, got {want}")
+        ts, k, B = self._latents(h)
+        if B <= 0 or k <= 0:
+            raise ValueError("n_samples and B must be positive")
+        xd = None
+        if x is not None:
+            xd = self._x(x)
+            if xd.shape[0] != B:
+                raise ValueError(f"x has {xd.shape[0]} images, the latents {B}")
+        elif "log_q" in want or "log_px" in want:
+            raise ValueError("log_q and log_px need x")
+        with torch.cuda.stream(self._stream):
+            ld = (self.x_dim + 3) // 4 * 4
+            terms = {n: torch.empty(B, k, device=self.device) for n in ("log_q", "log_ph", "log_px") if n in want}
+            probs = torch.empty(B * k, ld, device=self.device) if "probs" in want else None
+        arr, n = _lib.fptr_array(ts)
+        self._call(self._lib.iwae_score(self._h, _lib.fptr(xd), B, k, int(chunk), arr, n,
+                                        _lib.fptr(terms.get("log_q")), _lib.fptr(terms.get("log_ph")),
+                                        _lib.fptr(terms.get("log_px")), _lib.fptr(probs), ld if probs is not None else 0))
+        with torch.cuda.stream(self._stream):
+            out = {n: t.t().contiguous() for n, t in terms.items()}
+            if len(terms) == 3:
+                out["log_w"] = (out["log_ph"] + out["log_px"]) - out["log_q"]
+            if probs is not None:
+                out["probs"] = probs[:, :self.x_dim].reshape(B, k, self.x_dim).transpose(0, 1).contiguous()
+        self._stream.synchronize()
+        return out
+
+    def _encode(self, x, n_samples, eps=None, chunk=0):
+        """iwae_encode behind ``model.encoder(x, n_samples)``."""
+        xd = self._x(x)
+        B, k = xd.shape[0], int(n_samples)
+        if B <= 0 or k <= 0:
+            raise ValueError("B and n_samples must be positive")
+        arr, n, keep = self._eps(eps, B, k)
+        dims = self.n_latent_encoder
+        L = len(dims)
+        with torch.cuda.stream(self._stream):
+            hs = [torch.empty(k, B, d, device=self.device) for d in dims]
+            lq = torch.empty(B, k, device=self.device)
+            top = (B, dims[0]) if L == 1 else (k, B, dims[-1])
+            loc = torch.empty(*top, device=self.device)
+            scale = torch.empty(*top, device=self.device)
+        harr, nh = _lib.fptr_array(hs)
+        self._call(self._lib.iwae_encode(self._h, _lib.fptr(xd), B, k, int(chunk), arr, n, harr, nh, _lib.fptr(lq),
+                                         _lib.fptr(loc), _lib.fptr(scale)))
+        with torch.cuda.stream(self._stream):
+            lq = lq.t().contiguous()
+        self._stream.synchronize()
+        return hs, lq, _Normal(loc, scale)
 
     def reconstructed_x_probs_iw(self, x, k, eps=None):
         """Importance-weighted reconstruction [N, x_dim]: sum_s w~_s p(x | h_{1,s})

@@ -1,0 +1,361 @@
+"""Scoring caller-supplied latents (iwae_score / iwae_encode; Flexible_Model.score,
+model.encoder, model.decoder) against the float64 reference of tests/score_ref.py,
+on the fused score_kernel and on the layer-wise path.
+
+Bars.  Each of log_q, log_ph, log_px: max|err| <= 1e-4 max|ref| (test_gpu_parity's
+log-weight bar) and, per row, |err_r| <= 1e-4 S_r with S_r the sum of the
+absolute values of the term's addends; probs: test_gpu_generate's PROBS_TOL.
+tests/test_score_ref.py shows the float32 and the emulated-bf16x3 reference
+within a quarter of both bars on every case but SH.
+
+SH (scales of about e^-3): both bars under precision="f32"; under bf16x3 the
+max|ref| bar only.  CPU emulation of bf16x3 for its log_q on the encoder's own
+latents (of max|ref| / of S_r): densities at the f32 latents 1.6e-5 / 2.0e-5, at
+the split latents 1.5e-5 / 1.9e-5 (over seeds 988-991 up to 2.4e-5 / 2.5e-5 and
+2.6e-5 / 3.1e-5).  Measured on an MI355X (printed by test_parity; fused /
+layer-wise, worst over the three latent sets): log_q 1.7e-5 / 2.1e-5 and 1.6e-5
+/ 2.0e-5, log_ph 5.4e-5 / 3.0e-5 and 5.6e-5 / 3.1e-5 (prior samples: a small sum
+of terms whose means carry the products' rounding times e^3; score_ref.py says
+how the case's seed was chosen), log_px 8.5e-7 / 8.8e-7; under f32 at most
+1.1e-6.  The other seven cases: at most 1.1e-5 / 1.6e-5 (DESIGN.md s9 has the table).
+
+test_rows_are_independent: a row of 1e30 latents gives hugely negative log_q and
+log_ph, but its log_px is finite (the first tanh saturates), so that one value is
+held to the float64 reference of the row instead of to "non-finite or hugely
+negative"."""
+import ctypes
+import functools
+import itertools
+
+import numpy as np
+import pytest
+
+import score_ref as R
+from test_gpu_generate import PROBS_TOL
+from test_gpu_parity import make_model, weights_from_flat
+
+pytestmark = pytest.mark.gpu
+
+BAR = 1e-4
+PATHS = ("auto", "layerwise")
+TERMS = (("log_q", "logq", "Sq"), ("log_ph", "logp", "Sp"), ("log_px", "logpx", "Spx"))
+ALL = ("log_q", "log_ph", "log_px", "probs")
+
+
+@functools.lru_cache(maxsize=None)
+def _model(name, path, precision="bf16x3", seed=0):
+    from oracle import iwae_oracle as O
+    spec, params, _, _ = R.case(name)
+    he, hd, le, ld = R.CASES[name][0]
+    m = make_model(he, hd, le, ld, x_dim=spec.x_dim, kernel_path=path, precision=precision, seed=seed)
+    m.set_weights(weights_from_flat(m, O.flatten_params(spec, params)))
+    return m
+
+
+def _f32(a):
+    return [np.asarray(v, np.float32) for v in a] if isinstance(a, (list, tuple)) else np.asarray(a, np.float32)
+
+
+def _counts(m, ids=(23, 24, 3, 0)):
+    return [int(m._lib.iwae_debug_count(m._h, i)) for i in ids]
+
+
+def _ratios(got, ref, sref):
+    err = np.abs(np.asarray(got, np.float64) - ref)
+    return float(err.max() / np.abs(ref).max()), float((err / sref).max())
+
+
+def _check_terms(out, ref, label, row_bar=True):
+    for name, key, sk in TERMS:
+        if name not in out:
+            continue
+        got = out[name].cpu().numpy()
+        assert got.shape == ref[key].shape
+        of_max, of_row = _ratios(got, ref[key], ref[sk])
+        print(f"{label} {name}: {of_max:.2e} of max|ref|, {of_row:.2e} of S_r")
+        assert of_max <= BAR, (label, name, of_max)
+        if row_bar:
+            assert of_row <= BAR, (label, name, of_row)
+
+
+# ------------------------------------------------------------------ 1. parity
+@pytest.mark.parametrize("path", PATHS)
+@pytest.mark.parametrize("which", R.LATENTS)
+@pytest.mark.parametrize("name", list(R.CASES))
+def test_parity(name, which, path):
+    _, _, x, _ = R.case(name)
+    h, ref = R.latents(name, which), R.reference(name, which)
+    precisions = ("bf16x3", "f32") if name == "SH" else ("bf16x3",)
+    for precision in precisions:
+        m = _model(name, path, precision)
+        out = m.score(_f32(x), _f32(h), want=ALL)
+        label = f"[{name} {which} {path} {precision}]"
+        _check_terms(out, ref, label, row_bar=not (name == "SH" and precision == "bf16x3"))
+        lw = out["log_w"].cpu().numpy()
+        np.testing.assert_array_equal(lw, ((out["log_ph"] + out["log_px"]) - out["log_q"]).cpu().numpy())
+        probs = out["probs"].cpu().numpy()
+        assert probs.shape == ref["probs"].shape
+        np.testing.assert_allclose(probs, ref["probs"], **PROBS_TOL)
+        m.check_kernel_status()
+
+
+# -------------------------------------------------------------- 2. path taken
+@pytest.mark.parametrize("name", list(R.CASES))
+def test_path_taken(name):
+    _, _, x, eps = R.case(name)
+    k = R.CASES[name][2]
+    h = _f32(R.latents(name, "off"))
+    m = _model(name, "auto")
+    c0 = _counts(m)
+    m.score(_f32(x), h)
+    c1 = _counts(m)
+    m.log_px(_f32(x), k, eps=_f32(eps))
+    c2 = _counts(m)
+    d = [b - a for a, b in zip(c0, c1)]
+    assert sorted(d[:2]) == [0, 1], d                     # exactly one of 23 / 24, one chunk
+    assert (d[0] == 1) == (c2[3] > c1[3]), (d, c1, c2)    # fused exactly when the NLL on injected noise is
+    assert d[2] == 0                                      # never the ring, K130 included
+    lw = _model(name, "layerwise")
+    c0 = _counts(lw)
+    lw.score(_f32(x), h)
+    d = [b - a for a, b in zip(c0, _counts(lw))]
+    assert d[:3] == [0, 1, 0], d
+
+
+# ----------------------------------------------------------- 3. decomposition
+@pytest.mark.parametrize("path", PATHS)
+@pytest.mark.parametrize("name", ["S1", "S2", "S3", "K130"])
+def test_decomposition_of_the_log_weights(name, path):
+    _, _, x, eps = R.case(name)
+    k = R.CASES[name][2]
+    m = _model(name, path)
+    h, lq, _ = m.encoder(_f32(x), k, eps=_f32(eps))
+    out = m.score(_f32(x), h)
+    lw = m.get_log_weights(_f32(x), k, eps=_f32(eps)).cpu().numpy().astype(np.float64)
+    got = out["log_w"].cpu().numpy().astype(np.float64)
+    assert np.abs(got - lw).max() <= 2 * BAR * np.abs(lw).max()
+    ref = R.reference(name, "on")
+    of_max, of_row = _ratios(out["log_q"].cpu().numpy(), lq.cpu().numpy().astype(np.float64), ref["Sq"])
+    assert of_max <= BAR and of_row <= BAR, (of_max, of_row)
+
+
+# ----------------------------------------------------------- 4. encoder parity
+@pytest.mark.parametrize("path", PATHS)
+@pytest.mark.parametrize("name", ["S1", "S2", "S3", "S4", "C784"])
+def test_encoder_matches_the_oracle(name, path):
+    from oracle import iwae_oracle as O
+    spec, params, x, eps = R.case(name)
+    _, B, k = R.CASES[name][:3]
+    c = O.forward(params, spec, x, eps)
+    m = _model(name, path)
+    g0 = _counts(m)
+    h, lq, top = m.encoder(_f32(x), k, eps=_f32(eps))
+    assert _counts(m)[:2] == g0[:2]                       # no scoring pass: the layer-wise sampling kernels
+    assert len(h) == spec.L and m.encoder.n_stochastic == spec.L
+    for i, (a, r) in enumerate(zip(h, c["h"])):
+        assert tuple(a.shape) == r.shape
+        assert np.abs(a.cpu().numpy() - r).max() <= BAR * np.abs(r).max(), i
+    sq = R.score(params, spec, x, c["h"])["Sq"]
+    of_max, of_row = _ratios(lq.cpu().numpy(), c["logq"], sq)
+    assert tuple(lq.shape) == (k, B) and of_max <= BAR and of_row <= BAR, (of_max, of_row)
+    q = c["enc"][-1]
+    for got, r in ((top.loc, q["mu"]), (top.scale, q["scale"])):
+        assert tuple(got.shape) == r.shape == ((B, spec.n_latent_encoder[0]) if spec.L == 1 else
+                                               (k, B, spec.n_latent_encoder[-1]))
+        assert np.abs(got.cpu().numpy() - r).max() <= BAR * np.abs(r).max()
+    # chunked: the same samples and densities
+    h2, lq2, top2 = m.encoder(_f32(x), k, eps=_f32(eps), chunk=2)
+    for a, b in zip(h + [lq, top.loc, top.scale], h2 + [lq2, top2.loc, top2.scale]):
+        np.testing.assert_array_equal(a.cpu().numpy(), b.cpu().numpy())
+
+
+@pytest.mark.parametrize("name", ["S1", "S3"])
+def test_encoder_device_noise_is_the_layerwise_forwards(name):
+    _, _, x, _ = R.case(name)
+    k = R.CASES[name][2]
+    a, b = (_model(name, "layerwise", seed=31 + i) for i in range(2))
+    for m in (a, b):
+        m.set_seed(77)
+    h, lq, _ = a.encoder(_f32(x), k)
+    got = a.score(_f32(x), h)["log_w"].cpu().numpy().astype(np.float64)
+    lw = b.get_log_weights(_f32(x), k).cpu().numpy().astype(np.float64)
+    assert np.abs(got - lw).max() <= 2 * BAR * np.abs(lw).max()
+    h2, _, _ = a.encoder(_f32(x), k)                      # the noise position advanced: fresh samples
+    assert np.abs((h2[0] - h[0]).cpu().numpy()).max() > 1e-3
+
+
+# ------------------------------------------------------------ 5. output subsets
+@pytest.mark.parametrize("path", PATHS)
+@pytest.mark.parametrize("name", ["S1", "S2", "S3"])
+def test_output_subsets_are_bitwise_the_full_calls(name, path):
+    _, _, x, _ = R.case(name)
+    h = _f32(R.latents(name, "off"))
+    m = _model(name, path)
+    full = {n: v.cpu().numpy() for n, v in m.score(_f32(x), h, want=ALL).items()}
+    subsets = [s for r in (1, 2, 3) for s in itertools.combinations(ALL[:3], r)] + [("probs",)]
+    for want in subsets:
+        need_x = "log_q" in want or "log_px" in want
+        out = m.score(_f32(x) if need_x else None, h, want=want)
+        assert set(out) == set(want) | ({"log_w"} if len(want) == 3 else set())
+        for n in want:
+            np.testing.assert_array_equal(out[n].cpu().numpy(), full[n], err_msg=f"{want} {n}")
+    np.testing.assert_array_equal(m.decoder.get_log_ph(h).cpu().numpy(), full["log_ph"])     # no x
+
+
+# ------------------------------------------------------------------- 6. chunks
+@pytest.mark.parametrize("path", PATHS)
+def test_chunks_do_not_change_a_bit(path):
+    _, _, x, _ = R.case("S2")
+    h = _f32(R.latents("S2", "off"))
+    m = _model("S2", path)
+    c0 = _counts(m)
+    whole = m.score(_f32(x), h, want=ALL, chunk=0)
+    assert sum(_counts(m)[:2]) == sum(c0[:2]) + 1
+    for chunk, launches in ((1, 5), (2, 3)):
+        c0 = _counts(m)
+        out = m.score(_f32(x), h, want=ALL, chunk=chunk)
+        assert sum(_counts(m)[:2]) == sum(c0[:2]) + launches
+        for n in whole:
+            np.testing.assert_array_equal(out[n].cpu().numpy(), whole[n].cpu().numpy(), err_msg=f"chunk {chunk} {n}")
+
+
+# --------------------------------------------------------- 7. row independence
+@pytest.mark.parametrize("bad", [1e30, float("nan")])
+@pytest.mark.parametrize("path", PATHS)
+def test_rows_are_independent(path, bad):
+    _, _, x, _ = R.case("S2")
+    _, B, k = R.CASES["S2"][:3]
+    h = _f32(R.latents("S2", "off"))
+    m = _model("S2", path)
+    base = m.score(_f32(x), h, want=ALL)
+    b, s = 1, 3                                           # row 10: a tile shared with images 0 and 2
+    hb = [v.copy() for v in h]
+    for v in hb:
+        v[s, b, :] = bad
+    out = m.score(_f32(x), hb, want=ALL)
+    keep = np.ones((k, B), bool)
+    keep[s, b] = False
+    for n in ALL:
+        g, r = out[n].cpu().numpy(), base[n].cpu().numpy()
+        np.testing.assert_array_equal(g[keep], r[keep], err_msg=n)
+    for n in ALL[:3]:
+        v = float(out[n].cpu().numpy()[s, b])
+        if n == "log_px" and np.isfinite(bad):
+            # log p(x | h_1 = 1e30) is finite: the first tanh saturates at +-1.  Held to the float64
+            # reference of that row instead (a Gaussian density at 1e30 is hugely negative, this is not)
+            spec, params, _, _ = R.case("S2")
+            with np.errstate(all="ignore"):
+                ref = R.score(params, spec, x[b:b + 1], [np.asarray(u[s:s + 1, b:b + 1], np.float64) for u in hb])
+            assert abs(v - float(ref["logpx"][0, 0])) <= BAR * float(ref["Spx"][0, 0]), (v, ref["logpx"])
+            continue
+        assert not np.isfinite(v) or v < -1e20, (n, v)
+    m.check_kernel_status()
+
+
+# -------------------------------------------------------------------- 8. state
+def test_score_and_encode_leave_the_training_state_alone():
+    from iwae_replication_project_amd import Adam
+    he, hd, le, ld = R.CASES["C784"][0]
+    rng = np.random.default_rng(5)
+    x = (rng.random((40, 784)) < 0.3).astype(np.float32)
+    k = 17
+    eps = [rng.standard_normal((k, 5, d)).astype(np.float32) for d in le]
+    models = []
+    for _ in range(2):
+        m = make_model(he, hd, le, ld, seed=11)
+        m.compile(optimizer=Adam(learning_rate=1e-3, epsilon=1e-4))
+        models.append(m)
+    a, b = models
+    b.set_weights(a.get_weights())
+    la, lb = a.train_steps(x, 20), b.train_steps(x, 20)
+    np.testing.assert_array_equal(np.asarray(la), np.asarray(lb))
+    w0, (m0, v0, t0), g0 = a.get_weights(), a.get_optimizer_state(), a.graph_captures()
+    h, lq, _ = a.encoder(x[:5], k, eps=eps)
+    out = a.score(x[:5], h, want=ALL)
+    assert all(np.isfinite(v.cpu().numpy()).all() for v in out.values())
+    w1, (m1, v1, t1) = a.get_weights(), a.get_optimizer_state()
+    for p, q in zip(w0, w1):
+        np.testing.assert_array_equal(p, q)
+    np.testing.assert_array_equal(m0, m1)
+    np.testing.assert_array_equal(v0, v1)
+    assert t0 == t1 and a.graph_captures() == g0
+    # the noise position stayed: the next device-noise log weights and train steps are the other model's
+    np.testing.assert_array_equal(a.get_log_weights(x[:5], k).cpu().numpy(), b.get_log_weights(x[:5], k).cpu().numpy())
+    la, lb = a.train_steps(x, 20), b.train_steps(x, 20)
+    assert a.graph_captures() == g0                        # replayed, not re-captured
+    np.testing.assert_array_equal(np.asarray(la), np.asarray(lb))
+    for p, q in zip(a.get_weights(), b.get_weights()):
+        np.testing.assert_array_equal(p, q)
+    a.check_kernel_status()
+
+
+# ------------------------------------------------------ 9. reference call forms
+@pytest.mark.parametrize("path", PATHS)
+def test_reference_call_forms(path):
+    for name in ("S2", "C784"):
+        _, _, x, _ = R.case(name)
+        _, B, k = R.CASES[name][:3]
+        h = _f32(R.latents(name, "prior"))
+        m = _model(name, path)
+        out = m.score(_f32(x), h, want=ALL)
+        d = m.decoder
+        for got, want in ((d.get_log_pxIh(_f32(x), h), out["log_px"]), (d.get_log_ph(h), out["log_ph"]),
+                          (d.get_log_pxh(_f32(x), h), out["log_px"] + out["log_ph"])):
+            assert tuple(got.shape) == (k, B)
+            np.testing.assert_array_equal(got.cpu().numpy(), want.cpu().numpy())
+        probs, pxIh = d(h)
+        assert tuple(probs.shape) == (k, B, m.x_dim) and pxIh.probs is probs
+        np.testing.assert_array_equal(probs.cpu().numpy(), out["probs"].cpu().numpy())
+        if name == "C784":                                # one layer: generate_x(h_1) is the same quantity
+            np.testing.assert_allclose(probs.cpu().numpy(), d.generate_x(h[0]).cpu().numpy(), **PROBS_TOL)
+
+
+# ------------------------------------------------------------------ 10. errors
+@pytest.mark.parametrize("path", PATHS)
+def test_invalid_arguments_return_einval_and_leave_the_handle_usable(path):
+    import torch
+    from iwae_replication_project_amd import _lib
+    name = "S2"
+    _, _, x, _ = R.case(name)
+    _, B, k = R.CASES[name][:3]
+    m = _model(name, path)
+    L, xd = 2, m.x_dim
+    dev = m.device
+    xt = torch.as_tensor(_f32(x), device=dev)
+    hs = [torch.as_tensor(v, device=dev).contiguous() for v in _f32(R.latents(name, "off"))]
+    o = [torch.empty(B, k, device=dev) for _ in range(3)]
+    pr = torch.empty(B * k * xd + 8, device=dev)
+    lat, n = _lib.fptr_array(hs)
+    one = (_lib.FP * 2)(_lib.fptr(hs[0]), None)
+    P, N0 = _lib.fptr, None
+    off = ctypes.cast(ctypes.c_void_p(pr.data_ptr() + 4), _lib.FP)
+
+    def call(x=P(xt), N=B, k=k, chunk=0, lat=lat, n=n, q=P(o[0]), ph=P(o[1]), px=P(o[2]), probs=N0, ld=0):
+        return m._lib.iwae_score(m._h, x, N, k, chunk, lat, n, q, ph, px, probs, ld)
+    bad = dict(
+        every_output_null=dict(q=N0, ph=N0, px=N0),
+        x_null_with_log_q=dict(x=N0, px=N0),
+        x_null_with_log_px=dict(x=N0, q=N0),
+        n_lat_not_L=dict(n=1),
+        lat_null=dict(lat=N0),
+        a_null_latent=dict(lat=one),
+        N_zero=dict(N=0), N_negative=dict(N=-3), k_zero=dict(k=0), k_negative=dict(k=-1),
+        k_above_limit=dict(k=(1 << 20) + 1),
+        chunk_above_limit=dict(N=4096, k=1 << 20, chunk=2048),
+        ld_below_x_dim=dict(probs=P(pr), ld=xd - 4),
+        ld_not_multiple_of_4=dict(probs=P(pr), ld=xd + 2),
+        ld_above_limit=dict(probs=P(pr), ld=(1 << 22) + 4),
+        probs_misaligned=dict(probs=off, ld=xd),
+    )
+    for what, kw in bad.items():
+        assert call(**kw) == -1, what
+        assert m._lib.iwae_last_error(m._h), what
+    # iwae_encode's own conditions
+    E = lambda **kw: m._lib.iwae_encode(m._h, kw.get("x", P(xt)), kw.get("N", B), kw.get("k", k), 0, None, 0,
+                                        kw.get("lat", lat), kw.get("n", n), P(o[0]), None, None)
+    assert E(x=N0) == -1 and E(n=1) == -1 and E(N=0) == -1 and E(k=(1 << 20) + 1) == -1
+    assert m._lib.iwae_encode(m._h, P(xt), B, k, 0, None, 0, None, 0, None, None, None) == -1
+    assert call() == 0
+    m.check_kernel_status()
+    out = m.score(_f32(x), _f32(R.latents(name, "off")))
+    _check_terms(out, R.reference(name, "off"), f"[after errors {path}]")
