@@ -220,8 +220,17 @@ int iwae_set_adam_state(iwae_handle* h, const float* m_host, const float* v_host
 
 /* --- training (device pointers, stream-ordered) --------------------------- */
 /* Flexible_Model.train_step (F:221-F:247): forward, loss, backward, Adam.
- * x [dev] is [B][x_dim] in {0,1}.  loss_dev [dev, may be NULL] receives the
- * scalar loss (= -bound, the value train_step returns in {loss: ...}). */
+ * x [dev] is [B][x_dim], every pixel in [0,1] (here and in every entry that
+ * takes images).  log p(x|h) is TFP's Bernoulli log_prob (F:126-F:128): pixels
+ * that are exactly 0 or 1 take its one-log form log(x ? p : 1 - p), any other
+ * value the two-log form x log p + (1 - x) log(1 - p), the same function.  The
+ * kernels decide between the two per group of pixels, not per pixel -- a
+ * wave's column tile of 16, 32 or 64 sample rows, or a workgroup's 128 rows --
+ * so a binarised image takes either form depending on its neighbours in the
+ * batch; results agree to float32 rounding, not bit for bit.  Pixels outside
+ * [0,1] and NaN are not supported (a missing pixel goes through the masked
+ * entries).  loss_dev [dev, may be NULL] receives the scalar loss (= -bound,
+ * the value train_step returns in {loss: ...}). */
 int iwae_train_step(iwae_handle* h, const iwae_loss_config* lc, const float* x, int B,
                     const float* const* eps, int n_eps, float* loss_dev);
 /* fit's batch loop (E:82 -> F:221-F:247 per batch): nsteps consecutive train

@@ -216,16 +216,19 @@ __device__ __forceinline__ void mg_bern(const MgLaunch& L, const MgStage& S, int
     }
   } else {
     // fractional pixels: x log p + (1 - x) log(1 - p), both probabilities
-    // formed without cancellation (sigmoid(-l) = e * sigmoid(l), e = exp(-l))
+    // formed without cancellation and without overflow: a = exp(-|l|) <= 1,
+    // r = 1 / (1 + a); sigmoid(|l|) = r, sigmoid(-|l|) = a r (exp(-l) itself
+    // is inf below l = -88.7, and inf * 0 a NaN)
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const float x = f4_at(xv[rt], i);
-        const float e = fexp(-acc[rt][i]);
-        const float sp = frcp(1.f + e);
-        const float p1 = __builtin_fmaf(sp, kProbScale, kProbShift);
-        const float p0 = __builtin_fmaf(e * sp, kProbScale, kBernOff0);
+        const float l = acc[rt][i];
+        const float a = fexp(-__builtin_fabsf(l));
+        const float r = frcp(1.f + a), ar = a * r;
+        const float p1 = __builtin_fmaf(l >= 0.f ? r : ar, kProbScale, kProbShift);
+        const float p0 = __builtin_fmaf(l >= 0.f ? ar : r, kProbScale, kBernOff0);
         const float v = x * __builtin_amdgcn_logf(p1) + (1.f - x) * __builtin_amdgcn_logf(p0);
         R.l2[rt] += (f0 + i < S.N && !(MASK && x < 0.f)) ? v : 0.f;
       }

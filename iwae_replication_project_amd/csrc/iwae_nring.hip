@@ -657,13 +657,17 @@ __device__ __forceinline__ void nr_bern_frac(const NrStage& S, int t, const nr_f
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const float x = f4_at(xv, i);
-    const float e = fexp(-acc[i]);
-    const float sp = frcp(1.f + e);
+    // a = exp(-|l|) <= 1 (exp(-l) is inf below l = -88.7, and inf * 0 a NaN):
+    // sigmoid(|l|) = r, sigmoid(-|l|) = a r
+    const float l = acc[i];
+    const float a = fexp(-__builtin_fabsf(l));
+    const float r = frcp(1.f + a), ar = a * r;
+    const float sp = l >= 0.f ? r : ar, sm = l >= 0.f ? ar : r;
     const float p1 = __builtin_fmaf(sp, kProbScale, kProbShift);
-    const float p0 = __builtin_fmaf(e * sp, kProbScale, kNrBernOff0);
+    const float p0 = __builtin_fmaf(sm, kProbScale, kNrBernOff0);
     const float v = x * __builtin_amdgcn_logf(p1) + (1.f - x) * __builtin_amdgcn_logf(p0);
     R.l2 += (f0 + i < S.N) ? v : 0.f;
-    if (TR) gv[i] = (wa * (x * frcp(p1) - (1.f - x) * frcp(p0))) * (kProbScale * (sp * (1.f - sp)));
+    if (TR) gv[i] = (wa * (x * frcp(p1) - (1.f - x) * frcp(p0))) * (kProbScale * (sp * sm));
   }
   if (TR) {
     nr_st4(S.out, (R.valid && f0 < S.N) ? (unsigned)(R.grow * S.ld_out + f0) * 4u : kOOB, gv);

@@ -484,13 +484,17 @@ __device__ __forceinline__ void tc_bern(const TcArgs& A, COp& S, int t, const tc
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const float x = f4_at(xv[rt], i);
-        const float e = fexp(-acc[rt][i]);
-        const float sp = frcp(1.f + e);
+        // a = exp(-|l|) <= 1: no overflow at any logit (exp(-l) is inf below
+        // l = -88.7 and inf * 0 a NaN); sigmoid(+-l) are r and a r
+        const float l = acc[rt][i];
+        const float a = fexp(-__builtin_fabsf(l));
+        const float r = frcp(1.f + a), ar = a * r;
+        const float sp = l >= 0.f ? r : ar, sm = l >= 0.f ? ar : r;
         const float p1 = __builtin_fmaf(sp, kProbScale, kProbShift);
-        const float p0 = __builtin_fmaf(e * sp, kProbScale, kBernOff0T);
+        const float p0 = __builtin_fmaf(sm, kProbScale, kBernOff0T);
         const float v = x * __builtin_amdgcn_logf(p1) + (1.f - x) * __builtin_amdgcn_logf(p0);
         R.l2[rt] += (f0 + i < S.N) ? v : 0.f;
-        const float dsg = kProbScale * (sp * (1.f - sp));
+        const float dsg = kProbScale * (sp * sm);
         float f = A.wa * (x * frcp(p1) - (1.f - x) * frcp(p0));
         if (bce) {
           const float b1 = p1 + kKerasEps, b0 = p0 + kKerasEps;

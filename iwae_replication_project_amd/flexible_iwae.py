@@ -432,6 +432,12 @@ class Flexible_Model:
 
     def train_step(self, x, eps=None, sync=True, mask=None):
         """F:221-F:247: one optimisation step; returns {loss_function: loss}.
+        ``x`` [B, x_dim]: pixels in [0, 1].  Images of 0s and 1s take the
+        one-log form of the Bernoulli log-probability, grey levels the two-log
+        form x log p + (1 - x) log(1 - p) (F:127-F:128) -- the same function,
+        decided per tile of sample rows or per workgroup, so a binarised image
+        may take either form depending on its neighbours in the batch (equal
+        to float32 rounding, not bit for bit).
         ``mask`` [B, x_dim] (non-zero = observed): the step on incomplete images
         (iwae_train_step_masked; Mattei & Frellsen 2019): the encoder sees
         x * mask, the likelihood sums the observed pixels, whatever ``x`` holds
@@ -719,7 +725,11 @@ class Flexible_Model:
         return -1 * (self.get_L(x, k) + self.get_NLL(x))
 
     def log_px(self, x, k=5000, eps=None, chunk=0):
-        """Per-image k-sample log p(x) estimate (device tensor [N])."""
+        """Per-image k-sample log p(x) estimate (device tensor [N]).  ``x``:
+        pixels in [0, 1]; 0/1 images take the one-log form of the Bernoulli
+        log-probability, grey levels the two-log form (see train_step: decided
+        per tile or workgroup, so a binarised image may take either form
+        depending on its neighbours)."""
         xd = self._x(x)
         N = xd.shape[0]
         with torch.cuda.stream(self._stream):
