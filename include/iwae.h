@@ -547,6 +547,69 @@ int iwae_score(iwae_handle* h, const float* x, int N, int k, int chunk,
                const float* const* lat, int n_lat,
                float* log_q, float* log_ph, float* log_px,
                float* probs, int ld_probs);
+/* Gradients of the scored densities with respect to the latents (what HMC, AIS
+ * and per-image optimisation of latents move by).  x, N, k, chunk, lat and the
+ * value outputs log_q / log_ph / log_px ([N][k], optional) are iwae_score's,
+ * with its limits (k <= 2^20, a chunk at most 2^30 rows, a chunk holds all k
+ * rows of its images).  coef is a HOST array (c_q, c_ph, c_px); grad is 0 or L
+ * device buffers [k][N][d_i], sample-major like lat.  For row (b, s), layer i:
+ *   grad[i] = c_q dlog q(h|x)/dh_i + c_ph dlog p(h)/dh_i + c_px dlog p(x|h_1)/dh_i
+ * at the caller's float32 latents: (0, 1, 1) the posterior score (HMC), (0, 1,
+ * beta) tempered AIS from the prior, (1 - beta, beta, beta) AIS from q, (-1, 1,
+ * 1) dlog w/dh, a unit vector one term alone.  Terms, with z = (t - mu) / s,
+ * s = exp(zs) + 1e-6 and t a head's target latent: -z / s with respect to the
+ * target; dmu = z / s, dzs = (z^2 - 1)(s - 1e-6) / s into the head's outputs,
+ * carried back through head -> l2 -> l1 (tanh' = 1 - y^2) to the latent the
+ * chain reads.  log q: h_1 gets its target term only (mu_0, s_0 depend on x);
+ * chain i >= 1 gives h_{i+1} its target term and h_i the chain's dX.  log p(h):
+ * -h_L, and each prior chain's target term and dX.  log p(x|h_1): dlogit_j =
+ * (x_j / p_j - (1 - x_j) / (1 - p_j)) (1 - 1e-6) sigma_j (1 - sigma_j) with p =
+ * sigma (1 - 1e-6) + 1e-7, back through the output MLP to h_1; zero for i > 1.
+ * A term whose coefficient is exactly 0 contributes nothing (not even a NaN)
+ * and its chains are left out unless its value output is asked for: then its
+ * forward alone runs.  With n_grad 0 the call is a scoring call.  x may be
+ * NULL when c_q = c_px = 0 (or n_grad is 0) and neither log_q nor log_px is
+ * asked for.  Each grad[i] is written in full, never accumulated into; grad[i]
+ * MUST NOT alias any lat[j] (the latents are read while gradients are stored).
+ * Paths.  Fused: one sg_kernel launch per chunk wherever iwae_score's fused
+ * path applies and the gradient plan fits 160 KiB of LDS at some row tile
+ * (64, 32 or 16 rows per workgroup): score_kernel's prologue and density heads;
+ * the 2L - 1 chains are independent, so each runs forward and straight back with
+ * its y1 / y2 in LDS, the head epilogue turning (mu, zs, target) into the
+ * density, the target gradient and dP, and three backward-data stages on the
+ * fragment-major transposed weight copies (products bf16x3 on
+ * v_mfma_f32_16x16x32_bf16; the heads read the caller's float32 target, the
+ * hi / lo copies of a latent feed products only).  The output chain's dlogit
+ * enters dY2 = dlogit W3^T as slabs of 256 pixels, each dY2 tile accumulated by
+ * one wave in slab order.  Per row, f32 gradient tiles in LDS collect the
+ * addends in the fixed order c_q T^q_1 and -c_ph h_L (prologue), then per
+ * encoder chain i >= 1 c_q T^q_{i+1} and c_q X^q_i, per prior chain c_ph T^p
+ * and c_ph X^p, then c_px X^o (T: target term, X: a chain's dX, the coefficient
+ * applied at the head), and are stored to grad.  Layer-wise (under
+ * iwae_set_precision(h, 0) or iwae_set_path(h, 1), or when the fused plan does
+ * not fit; never an error), one pass per chunk: iwae_score's gather launch and
+ * forward GEMMs, per chain the head gradients (sg_dens_kernel) and three
+ * backward-data GEMMs (no weight gradient), the output Dense's Bernoulli
+ * epilogue with the constant row weight c_px writing c_px dlogit (a chunk's
+ * dlogits: at most 256 MB) and three backward-data GEMMs, then one scatter
+ * launch that forms c_q T^q_i + c_q X^q_i + c_ph T^p_i + c_ph X^p_i + X^o_i -
+ * c_ph h_L left to right (absent addends skipped); its values are iwae_score's
+ * layer-wise launches.  On either path there are no float atomics, the call is
+ * deterministic, and its result does not depend on chunk, bit for bit.  The
+ * value outputs need not be bit-equal to iwae_score's.
+ * Rows are independent: non-finite latents in one row give non-finite outputs
+ * for that row only.  Nothing is drawn and the noise position stays; weights,
+ * Adam state, captured graphs and engine plans are untouched (the backward rows
+ * are a workspace of the call's own); the sticky error (iwae_status) is
+ * returned before any work is enqueued.  IWAE_EINVAL: nothing asked for, coef
+ * NULL or non-finite, n_lat != L, n_grad not 0 or L, a NULL lat[i] or grad[i],
+ * x NULL where it is needed, N <= 0 or k <= 0, k or the chunk above the
+ * limits. */
+int iwae_score_grad(iwae_handle* h, const float* x, int N, int k, int chunk,
+                    const float* const* lat, int n_lat,
+                    const float coef[3],
+                    float* const* grad, int n_grad,
+                    float* log_q, float* log_ph, float* log_px);
 /* Encoder.call (F:56-F:75): k samples of q(h|x) per image, with device noise
  * (eps NULL, n_eps 0) or injected eps[i] [k][N][d_i].  lat_out[i] [k][N][d_i],
  * sample-major (n_lat 0 or L); log_q [N][k]; loc_top / scale_top: the
@@ -613,8 +676,10 @@ double iwae_workspace_bytes(const iwae_handle* h);
  * iwae_train_step_masked / iwae_forward_backward_masked / iwae_bound_masked (a
  * captured step counts once, at capture); 22 binarize_kernel launches issued by
  * iwae_binarize (one per call with n > 0); 23 fused iwae_score launches
- * (score_kernel, one per chunk), 24 its layer-wise passes (one per chunk); -1
- * for an unknown id. */
+ * (score_kernel, one per chunk), 24 its layer-wise passes (one per chunk); 25
+ * fused score-gradient launches of iwae_score_grad (sg_kernel, one per chunk),
+ * 26 its layer-wise score-gradient passes (one per chunk); -1 for an unknown
+ * id. */
 long long iwae_debug_count(const iwae_handle* h, int what);
 /* Live kernel timing: bracket every launch of one kernel class with HIP events
  * on the handle's stream -- a GEMM class (kind: 0 forward, 1 backward-data,

@@ -102,6 +102,7 @@ SIGNATURES = {
     "iwae_impute": (c_int, [H, FP, FP, c_int, c_int, c_int, FPP, c_int, FP, FP, FP, c_int, FP, c_int, FPP, c_int,
                             FPP, c_int, FP, FP, FP]),
     "iwae_score": (c_int, [H, FP, c_int, c_int, c_int, FPP, c_int, FP, FP, FP, FP, c_int]),
+    "iwae_score_grad": (c_int, [H, FP, c_int, c_int, c_int, FPP, c_int, FP, FPP, c_int, FP, FP, FP]),
     "iwae_encode": (c_int, [H, FP, c_int, c_int, c_int, FPP, c_int, FPP, c_int, FP, FP, FP]),
     "iwae_train_step_masked": (c_int, [H, POINTER(IwaeLossConfig), FP, FP, c_int, FPP, c_int, FP]),
     "iwae_forward_backward_masked": (c_int, [H, POINTER(IwaeLossConfig), FP, FP, c_int, FPP, c_int, FP]),

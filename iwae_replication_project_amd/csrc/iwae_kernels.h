@@ -621,6 +621,80 @@ hipError_t launch_score_relayout(hipStream_t st, const ScRelayout& a);
 // out[r] = the row's Bernoulli partial sums in column order (forward_core's row sum), r < rows
 hipError_t launch_score_rowsum(hipStream_t st, const float* part, int ldpart, int npart, int rows, float* out);
 
+// iwae_score_grad's layer-wise path (iwae_scoregrad.hip).  SgDens: a Gaussian
+// head's gradients at the given target H (workspace rows), with z = (t - mu) / s
+// and s = exp(zs) + 1e-6: tg[r][j] = -z / s (with respect to the target) and,
+// when dP is set, dP[r] = (z / s | (z^2 - 1) (s - 1e-6) / s) (into the head's
+// outputs); the head's row of P is r / prow_div.
+struct SgDens {
+  const float* P; int ldP, prow_div, d;
+  const float* H; int ldH;
+  float* tg; int ldtg;
+  float* dP; int lddP;
+  int M;
+};
+hipError_t launch_sg_dens(hipStream_t st, const SgDens& a);
+// SgScatter: layer g's out[((s N) + i0 + b) d + j] = sum_q c[q] src[q][(b k + s) ld[q] + j]
+// - c_top lat[...] (c_top: c_ph on the top layer, the gradient of log N(h_L; 0, 1)),
+// the sources added in their listed order; b < n, s < k, j < d.
+constexpr int kSgMaxSrc = 5;
+struct SgLayer {
+  const float* src[kSgMaxSrc]; int ld[kSgMaxSrc]; float c[kSgMaxSrc]; int nsrc;
+  float c_top; const float* lat;
+  float* out; int d;
+};
+struct SgScatter {
+  SgLayer lay[8]; int nlay;
+  int n, k, N, i0;
+};
+hipError_t launch_sg_scatter(hipStream_t st, const SgScatter& a);
+
+// iwae_score_grad's fused path: sg_kernel (iwae_scoregrad.hip), score_kernel's
+// rows, prologue and density heads with every chain run forward and straight
+// back in LDS.  Buffers (bf16 hi / lo planes): one tile per latent a chain
+// reads, A (a chain's y1, then dY1 in place), B (y2, then dY2 in place) and P
+// (a head's dP in GX's k order, natural (dmu | dzs); the output chain's dlogit
+// slab of 256 pixels).  f32 gradient tiles G_i [rows][g_ld] collect the terms
+// in stage order.  Stage kinds:
+//   SG_TANH   forward Dense + tanh into out_buf (FX copy)
+//   SG_HEADQ / SG_HEADP  density head: the value into log q / log p(h); with
+//             c != 0 the target gradient c (-z / s) into G[layer] and c dP into out_buf
+//   SG_GTANH  backward-data Dense on the GX copy times (1 - y^2), y read from
+//             and the result written to out_buf
+//   SG_GX     backward-data Dense on the GX copy added into G[layer]
+//   SG_OUT    the output Dense (FX) with the Bernoulli value and c dlogit,
+//             fed slab by slab into dY2 = dlogit W3^T (GX, out_gx_*), then
+//             times (1 - y2^2) in place in in_buf
+enum SgKind { SG_TANH = 0, SG_HEADQ = 1, SG_HEADP = 2, SG_GTANH = 3, SG_GX = 4, SG_OUT = 5 };
+constexpr int kSgMaxStages = 48;
+constexpr int kSgOutTiles = 4;       // dY2 column tiles a wave may own in SG_OUT
+constexpr int kSgWaves = 8;          // waves of an sg_kernel workgroup (MG_WAVES)
+struct SgStage {
+  unsigned woff;                     // element offset of the stage's FX / GX copy (hi and lo planes alike)
+  short ldk, N;                      // padded K; output features (heads: 8 ceil(d / 4) permuted)
+  signed char in_buf, out_buf, kind, layer;
+  short d, next_k;                   // heads: latent width; padded K of out_buf's reader
+  float c;                           // coefficient carried by this stage's gradient (0: value only)
+};
+struct SgLaunch {
+  SgStage st[kSgMaxStages]; int nst;
+  const __bf16* fx_hi; const __bf16* fx_lo; long long fx_elems;
+  int buf_off[kMgMaxBufs], buf_ld[kMgMaxBufs];   // bf16 offset of the hi plane / row stride
+  int g_off[8], g_ld[8];             // float offsets / row strides of the gradient tiles
+  int acc_off;                       // floats: logq, logp [rows]
+  int out_gx_woff, out_gx_ldk, out_gx_N;
+  int rows, kS;
+  const float* P0; int ldP0;
+  const float* x; int ldx;
+  const float* lat[8]; float* grad[8]; int lat_N, lat_i0;
+  int n_lat, lat_d[8], lat_buf[8], lat_next_k[8];
+  float cq, cph;                     // prologue: c_q T^q_1 (0: no gradient) and -c_ph h_L
+  int want_q, want_ph;               // prologue values: log N(h_1; P0), log N(h_L; 0, 1)
+  float* log_q; float* log_ph; float* log_px;
+};
+hipError_t launch_sgrad(hipStream_t st, const SgLaunch& L, int rt, size_t lds_bytes);
+hipError_t sgrad_setup_attributes();
+
 // ------------------------------- weight-ring k-sample forward (NLL) ----
 // nring_kernel (iwae_nring.hip): the same per-row work as mega_fwd_kernel for
 // 1- and 2-layer models, activations of 16 rows per wave in registers, the

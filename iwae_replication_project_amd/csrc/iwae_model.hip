@@ -213,6 +213,7 @@ struct Counters {
   long long bern_mask = 0;               // 21: pixel-masked Bernoulli output launches (EPI_BERN_MASK) of train steps and bounds
   long long binarize = 0;                // 22: binarize_kernel launches (iwae_binarize)
   long long score = 0, score_lw = 0;     // 23, 24: iwae_score chunks: score_kernel launches / layer-wise passes
+  long long sgrad = 0, sgrad_lw = 0;     // 25, 26: iwae_score_grad chunks: sg_kernel launches / layer-wise passes
 };
 
 // row-chain train engine plan (device resident, per shape; iwae_train.hip)
@@ -299,6 +300,9 @@ struct iwae_handle {
   char* post_ws = nullptr;           // iwae_posterior's workspace (weights, SIR indices, partial sums, probabilities,
   size_t post_ws_bytes = 0;          // a chunk's injected noise): its own allocation, so the arena and what was
                                      // captured over it stay as they are
+  float* sg_ws = nullptr;            // iwae_score_grad's backward rows (layer-wise path): its own allocation, zeroed
+  size_t sg_ws_floats = 0;           // when it grows, laid out for sg_rows rows (padding columns stay zero)
+  int sg_rows = 0;
   float* loss_slots = nullptr;       // multi-step graphs: step j's loss (kGraphSteps floats), then
                                      // [kGraphSteps, 2 kGraphSteps): where a graph's copy node writes
                                      // when the call wants no losses
@@ -3264,6 +3268,7 @@ iwae_handle* iwae_create(const iwae_config* cfg, int device) {
   e = rb_setup_attributes();
   if (e == hipSuccess) e = mega_setup_attributes();
   if (e == hipSuccess) e = score_setup_attributes();
+  if (e == hipSuccess) e = sgrad_setup_attributes();
   if (e == hipSuccess) e = nring_setup_attributes();
   if (e == hipSuccess) e = smallm_setup_attributes();
   if (e == hipSuccess) e = tc_setup_attributes();
@@ -3297,6 +3302,7 @@ void iwae_destroy(iwae_handle* h) {
   if (h->err_host) (void)hipHostFree(h->err_host);
   if (h->loss_slots) (void)hipFree(h->loss_slots);
   if (h->post_ws) (void)hipFree(h->post_ws);
+  if (h->sg_ws) (void)hipFree(h->sg_ws);
   if (h->nr_units) (void)hipFree(h->nr_units);
   if (h->nrb_units) (void)hipFree(h->nrb_units);
   if (h->nre_units) (void)hipFree(h->nre_units);
@@ -4961,6 +4967,349 @@ int iwae_score(iwae_handle* h, const float* x, int N, int k, int chunk, const fl
   return IWAE_OK;
 }
 
+// sg_kernel's plan (SgLaunch, iwae_kernels.h): the chains of the terms that are needed, each forward
+// and, where its gradient is asked for, straight back.  False when it does not fit 160 KiB of LDS
+// at any row tile, or its stage list or the output chain's column tiles exceed the kernel's limits.
+static bool sgrad_plan(const iwae_handle* h, bool run_q, bool run_ph, bool run_px, float cq, float cph, float cpx,
+                       SgLaunch& S, int& rt, size_t& lds) {
+  const int L = h->L;
+  std::memset(&S, 0, sizeof(S));
+  auto r32 = [](int x) { return (x + 31) & ~31; };
+  const int bA = L, bB = L + 1, bP = L + 2, nb = L + 3;
+  if (nb > kMgMaxBufs || L > 8) return false;
+  std::vector<int> width(nb, 0);
+  std::vector<SgStage> st;
+  auto fwd = [&](int di, int in, int out, int kind, int next_k) {
+    const DenseL& d = h->dense[di];
+    SgStage T{};
+    T.woff = (unsigned)d.fx_off; T.ldk = (short)d.ldF; T.N = (short)d.fout;
+    T.in_buf = (signed char)in; T.out_buf = (signed char)out; T.kind = (signed char)kind; T.next_k = (short)next_k;
+    width[in] = std::max(width[in], d.ldF);
+    if (kind == SG_TANH) width[out] = std::max(width[out], std::max(d.fout, next_k));
+    st.push_back(T);
+    return (int)st.size() - 1;
+  };
+  auto bwd = [&](int di, int in, int out, int kind, int layer) {
+    const DenseL& d = h->dense[di];
+    SgStage T{};
+    T.woff = (unsigned)d.gx_off; T.ldk = (short)(32 * d.gx_steps); T.N = (short)d.fin;
+    T.in_buf = (signed char)in; T.out_buf = (signed char)out; T.kind = (signed char)kind; T.layer = (signed char)layer;
+    width[in] = std::max(width[in], 32 * d.gx_steps);
+    if (out >= 0) width[out] = std::max(width[out], d.fin);
+    st.push_back(T);
+  };
+  for (int i = 0; i < 8; ++i) { S.lat_d[i] = i < L ? h->enc[i].d : 0; S.lat_buf[i] = -1; S.lat_next_k[i] = 0; }
+  auto chain = [&](const StochL& C, int src, int target, int kind, float c) {
+    fwd(C.l1, src, bA, SG_TANH, h->dense[C.l2].ldF);
+    fwd(C.l2, bA, bB, SG_TANH, h->dense[C.head].ldF);
+    const int gk = 32 * h->dense[C.head].gx_steps;
+    const int s = fwd(C.head, bB, bP, kind, gk);
+    st[s].N = (short)(8 * ((C.d + 3) / 4)); st[s].d = (short)C.d; st[s].layer = (signed char)target; st[s].c = c;
+    S.lat_buf[src] = src;
+    S.lat_next_k[src] = std::max(S.lat_next_k[src], h->dense[C.l1].ldF);
+    if (c == 0.f) return;
+    width[bP] = std::max(width[bP], std::max(gk, 2 * C.d));
+    bwd(C.head, bP, bB, SG_GTANH, 0);
+    bwd(C.l2, bB, bA, SG_GTANH, 0);
+    bwd(C.l1, bA, -1, SG_GX, src);
+  };
+  for (int i = 1; run_q && i < L; ++i) chain(h->enc[i], i - 1, i, SG_HEADQ, cq);
+  for (int j = 0; run_ph && j < L - 1; ++j) chain(h->dec[j], L - 1 - j, L - 2 - j, SG_HEADP, cph);
+  if (run_px) {
+    fwd(h->o1, 0, bA, SG_TANH, h->dense[h->o2].ldF);
+    fwd(h->o2, bA, bB, SG_TANH, h->dense[h->o3].ldF);
+    const int s = fwd(h->o3, bB, bP, SG_OUT, 0);
+    st[s].c = cpx;
+    S.lat_buf[0] = 0;
+    S.lat_next_k[0] = std::max(S.lat_next_k[0], h->dense[h->o1].ldF);
+    const DenseL& d3 = h->dense[h->o3];
+    S.out_gx_woff = (int)d3.gx_off; S.out_gx_ldk = 32 * d3.gx_steps; S.out_gx_N = d3.fin;
+    if (cpx != 0.f) {
+      if ((d3.fin + 15) / 16 > kSgOutTiles * kSgWaves) return false;
+      width[bP] = std::max(width[bP], 256);
+      bwd(h->o2, bB, bA, SG_GTANH, 0);
+      bwd(h->o1, bA, -1, SG_GX, 0);
+    }
+  }
+  if ((int)st.size() > kSgMaxStages) return false;
+  for (const SgStage& T : st)
+    if (T.ldk > 32000 || T.N > 32000) return false;
+  for (int i = 0; i < L; ++i)
+    if (S.lat_buf[i] >= 0) width[i] = std::max(width[i], S.lat_next_k[i]);
+  // LDS: the bf16 buffers (mega_plan's strides), the f32 gradient tiles, logq / logp
+  for (int c : {4, 2, 1}) {
+    const int R = 16 * c;
+    for (int pass = 0; pass < 2; ++pass) {
+      int off = 0;                              // bf16 units
+      for (int b = 0; b < nb; ++b) {
+        int sdw = (std::max(width[b], 32) + 1) / 2;
+        if (pass == 0) while (sdw % 16 != 8) ++sdw;
+        else while (sdw % 8 != 4) ++sdw;
+        S.buf_ld[b] = 2 * sdw;
+        S.buf_off[b] = off;
+        off += 2 * R * S.buf_ld[b];
+      }
+      int foff = (off + 3) / 2 & ~1;            // floats
+      foff = std::max(foff, 3 * kSgWaves * R);  // (the value sums' scratch reuses the buffers)
+      for (int i = 0; i < L; ++i) {
+        S.g_ld[i] = h->enc[i].d | 1;            // odd stride: the rows' columns spread over the banks
+        S.g_off[i] = foff;
+        foff += R * S.g_ld[i];
+      }
+      S.acc_off = foff;
+      const size_t bytes = (size_t)(S.acc_off + 2 * R) * sizeof(float);
+      if (bytes <= 160 * 1024) {
+        rt = c;
+        lds = bytes;
+        for (size_t i = 0; i < st.size(); ++i) S.st[i] = st[i];
+        S.nst = (int)st.size();
+        S.n_lat = L;
+        S.fx_hi = h->fx_hi; S.fx_lo = h->fx_lo; S.fx_elems = h->fx_elems;
+        return true;
+      }
+    }
+  }
+  return false;
+}
+
+// Gradients of the scored densities with respect to the latents (include/iwae.h).
+// Fused: one sg_kernel launch per chunk (sgrad_plan).  Layer-wise: iwae_score's
+// gather and forward launches, then per chain the head gradients
+// (sg_dens_kernel) and three backward-data GEMMs, the output MLP's Bernoulli
+// epilogue writing c_px dlogit, and one scatter launch; its backward rows live
+// in a workspace of the call's own (sg_ws), so the arena and what was captured
+// over it stay as they are.
+int iwae_score_grad(iwae_handle* h, const float* x, int N, int k, int chunk, const float* const* lat, int n_lat,
+                    const float coef[3], float* const* grad, int n_grad, float* log_q, float* log_ph, float* log_px) {
+  if (!h) return IWAE_EINVAL;
+  CHK(kernel_status(h));
+  const int L = h->L;
+  if (n_grad == 0 && !log_q && !log_ph && !log_px) return fail(h, IWAE_EINVAL, "every output is absent");
+  if (!coef) return fail(h, IWAE_EINVAL, "coef is NULL");
+  for (int t = 0; t < 3; ++t)
+    if (!std::isfinite(coef[t])) return fail(h, IWAE_EINVAL, "coef must be finite");
+  if (n_lat != L || !lat)
+    return fail(h, IWAE_EINVAL, "expected " + std::to_string(L) + " latent buffers (one per stochastic layer), got " +
+                                   std::to_string(n_lat));
+  if (n_grad != 0 && (n_grad != L || !grad))
+    return fail(h, IWAE_EINVAL, "expected 0 or " + std::to_string(L) + " gradient buffers, got " + std::to_string(n_grad));
+  for (int i = 0; i < L; ++i) {
+    if (!lat[i]) return fail(h, IWAE_EINVAL, "NULL latent buffer");
+    if (n_grad && !grad[i]) return fail(h, IWAE_EINVAL, "NULL gradient buffer");
+  }
+  const bool want_g = n_grad > 0;
+  const float cq = coef[0], cph = coef[1], cpx = coef[2];
+  const bool gq = want_g && cq != 0.f, gph = want_g && cph != 0.f, gpx = want_g && cpx != 0.f;
+  const bool run_q = gq || log_q, run_ph = gph || log_ph, run_px = gpx || log_px;
+  if (!x && (run_q || run_px))
+    return fail(h, IWAE_EINVAL, "x is NULL (log q and log p(x|h), values or gradient terms, need the images)");
+  int imgs = score_chunk(h, N, k, chunk);
+  if (!imgs) return IWAE_EINVAL;
+  // ---- fused: one sg_kernel launch per chunk where iwae_score's fused path applies and the plan fits
+  {
+    MgLaunch MG;
+    SgLaunch SG;
+    int mg_rt = 0, mg_waves = 8, sg_rt = 0;
+    size_t mg_lds = 0, sg_lds = 0;
+    const bool fused = h->x3 && h->nll_fused && h->path != 1 && !h->masked && mega_plan(h, MG, mg_rt, mg_waves, mg_lds) &&
+                       sgrad_plan(h, run_q, run_ph, run_px, gq ? cq : 0.f, gph ? cph : 0.f, gpx ? cpx : 0.f, SG, sg_rt,
+                                  sg_lds);
+    if (fused) {
+      // the first encoder layer runs once per group of images, as iwae_score's; no row buffer is used
+      const int sup = std::min(N, imgs * std::max(1, kNllFirstLayerImages / imgs));
+      CHK(ensure_capacity(h, sup, 1, false));
+      CHK(ensure_wsplit(h));
+      CHK(ensure_fx(h));
+      SG.fx_hi = h->fx_hi; SG.fx_lo = h->fx_lo; SG.fx_elems = h->fx_elems;
+      for (int i = 0; i < 8; ++i) { SG.lat[i] = i < L ? lat[i] : nullptr; SG.grad[i] = i < L && want_g ? grad[i] : nullptr; }
+      SG.lat_N = N;
+      SG.cq = gq ? cq : 0.f; SG.cph = gph ? cph : 0.f;
+      SG.want_q = log_q ? 1 : 0; SG.want_ph = log_ph ? 1 : 0;
+      const size_t xb = (size_t)h->xdim * sizeof(float);
+      int u0 = 0;                                  // first image of the current first-layer group
+      for (int i0 = 0; i0 < N; i0 += imgs) {
+        const int n = std::min(imgs, N - i0);
+        const size_t r0 = (size_t)i0 * k;
+        if (x && (i0 - u0 >= sup || i0 == 0)) {
+          u0 = i0;
+          const int ng = std::min(sup, N - i0);
+          HIPCHK(hipMemcpy2DAsync(h->x_in.p, (size_t)h->x_in.ld * sizeof(float), x + (size_t)i0 * h->xdim, xb, xb, ng,
+                                  hipMemcpyDeviceToDevice, h->stream));
+          if (run_q) CHK(stoch_fwd(h, h->enc[0], h->x_in, ng, h->eb[0]));
+        }
+        const int io = x ? i0 - u0 : 0;            // the chunk's rows in x_in / eb[0]
+        SG.rows = n * k; SG.kS = k; SG.lat_i0 = i0;
+        SG.P0 = h->eb[0].P.p + (size_t)io * h->eb[0].P.ld; SG.ldP0 = h->eb[0].P.ld;
+        SG.x = h->x_in.p + (size_t)io * h->x_in.ld; SG.ldx = h->x_in.ld;
+        SG.log_q = log_q ? log_q + r0 : nullptr;
+        SG.log_ph = log_ph ? log_ph + r0 : nullptr;
+        SG.log_px = log_px ? log_px + r0 : nullptr;
+        HIPCHK(launch_sgrad(h->stream, SG, sg_rt, sg_lds));
+        ++h->count.sgrad;
+      }
+      return IWAE_OK;
+    }
+  }
+  const int ldp = r4(h->xdim), Ho = h->dense[h->o1].fout;
+  // a chunk's dlogits: at most 256 MB of them (iwae_posterior's rule for its rows of probabilities)
+  if (gpx) imgs = (int)std::min<long long>(imgs, std::max<long long>(1, (256LL << 20) / ((long long)k * ldp * 4)));
+  const int rows = imgs * k;
+  CHK(ensure_capacity(h, imgs, rows, false));
+  if (h->x3) CHK(ensure_wsplit(h));
+  // ---- the backward rows (floats; laid out for the largest chunk so far).  One dP per head width and
+  // one dY2 / dY1 pair per hidden width: a buffer's columns past its logical width are never written
+  // and stay zero, as the arena's (the GEMMs read A in quads)
+  Mat dlogit, Xo, Tq[IWAE_MAX_LAYERS], Xq[IWAE_MAX_LAYERS], Tp[IWAE_MAX_LAYERS], Xp[IWAE_MAX_LAYERS];
+  std::map<int, Mat> dPs, dY2s, dY1s;
+  if (want_g) {
+    const int R = std::max(rows, h->sg_rows);
+    size_t off = 0;
+    std::vector<Mat*> all;
+    auto mat = [&](Mat& m, int width) {
+      m.ld = r4(width);
+      m.p = nullptr;
+      all.push_back(&m);
+      const size_t o = off;
+      off += ((size_t)R * m.ld + 63) & ~size_t(63);
+      return o;
+    };
+    std::vector<size_t> offs;
+    auto hid = [&](int H) {
+      if (dY2s.count(H)) return;
+      offs.push_back(mat(dY2s[H], H)); offs.push_back(mat(dY1s[H], H));
+    };
+    auto head = [&](int d) {
+      if (!dPs.count(d)) offs.push_back(mat(dPs[d], 2 * d));
+    };
+    for (int i = 1; i < L; ++i) { hid(h->enc[i].H); head(h->enc[i].d); }
+    for (int i = 0; i < L - 1; ++i) { hid(h->dec[i].H); head(h->dec[i].d); }
+    hid(Ho);
+    offs.push_back(mat(Xo, h->enc[0].d));
+    for (int i = 0; i < L; ++i)
+      for (Mat* m : {&Tq[i], &Xq[i], &Tp[i], &Xp[i]}) offs.push_back(mat(*m, h->enc[i].d));
+    const size_t small = off;
+    offs.push_back(mat(dlogit, h->xdim));                         // last and largest: present once a call needs it
+    const size_t need = gpx ? off : small;
+    if (R > h->sg_rows || need > h->sg_ws_floats) {
+      HIPCHK(hipStreamSynchronize(h->stream));
+      if (h->sg_ws) (void)hipFree(h->sg_ws);
+      h->sg_ws = nullptr; h->sg_ws_floats = 0; h->sg_rows = 0;
+      HIPCHK(hipMalloc(&h->sg_ws, need * sizeof(float)));
+      HIPCHK(hipMemsetAsync(h->sg_ws, 0, need * sizeof(float), h->stream));
+      h->sg_ws_floats = need; h->sg_rows = R;
+    }
+    for (size_t i = 0; i < all.size(); ++i) all[i]->p = h->sg_ws + offs[i];
+    if (!gpx) dlogit = Mat();
+  }
+  // dP (one chain's head gradients) back through head -> l2 -> l1 into dx
+  auto chain_bwd = [&](const StochL& s, int M, LayerBufs& b, Mat& dx) {
+    Mat &dY2 = dY2s[s.H], &dY1 = dY1s[s.H];
+    CHK(gemm_bwd_data(h, dPs[s.d], M, h->dense[s.head], dY2, &b.y2, nullptr));
+    CHK(gemm_bwd_data(h, dY2, M, h->dense[s.l2], dY1, &b.y1, nullptr));
+    CHK(gemm_bwd_data(h, dY1, M, h->dense[s.l1], dx, nullptr, nullptr));
+    return IWAE_OK;
+  };
+  auto dens = [&](const Mat& P, int prow_div, int d, const Mat& H, Mat& tg, bool with_dP, int M) {
+    SgDens a{};
+    a.P = P.p; a.ldP = P.ld; a.prow_div = prow_div; a.d = d;
+    a.H = H.p; a.ldH = H.ld;
+    a.tg = tg.p; a.ldtg = tg.ld;
+    if (with_dP) { a.dP = dPs[d].p; a.lddP = dPs[d].ld; }
+    a.M = M;
+    HIPCHK(launch_sg_dens(h->stream, a));
+    return IWAE_OK;
+  };
+  const size_t wbytes = (size_t)h->xdim * sizeof(float);
+  for (int i0 = 0; i0 < N; i0 += imgs) {
+    const int n = std::min(imgs, N - i0), M = n * k;
+    const size_t r0 = (size_t)i0 * k;            // the chunk's first row of the [N][k] outputs
+    if (x) {
+      HIPCHK(hipMemcpy2DAsync(h->x_in.p, (size_t)h->x_in.ld * sizeof(float), x + (size_t)i0 * h->xdim, wbytes, wbytes,
+                              n, hipMemcpyDeviceToDevice, h->stream));
+      if (run_q) CHK(stoch_fwd(h, h->enc[0], h->x_in, n, h->eb[0]));
+    }
+    ++h->count.sgrad_lw;
+    ScRelayout G{};
+    G.n = n; G.k = k; G.N = N; G.i0 = i0; G.gather = 1;
+    for (int i = 0; i < L; ++i)
+      G.seg[G.nseg++] = ScSeg{h->h[i].p, h->h[i].ld, 0, h->enc[i].d, const_cast<float*>(lat[i]), 0, 0};
+    HIPCHK(launch_score_relayout(h->stream, G));
+    // ---- log q: chain i scores h_{i+1} under enc_i(h_i); its dX is h_i's
+    for (int i = 0; run_q && i < L; ++i) {
+      if (i > 0) CHK(stoch_fwd(h, h->enc[i], h->h[i - 1], M, h->eb[i]));
+      if (log_q) {
+        GaussArgs g{};
+        g.P = h->eb[i].P.p; g.ldP = h->eb[i].P.ld; g.prow_div = i == 0 ? k : 1; g.d = h->enc[i].d;
+        g.H = h->h[i].p; g.ldH = h->h[i].ld;
+        g.out = log_q + r0; g.accumulate = i > 0; g.M = M;
+        HIPCHK(launch_gauss_fwd(h->stream, 1, g));
+      }
+      if (!gq) continue;
+      CHK(dens(h->eb[i].P, i == 0 ? k : 1, h->enc[i].d, h->h[i], Tq[i], i > 0, M));
+      if (i > 0) CHK(chain_bwd(h->enc[i], M, h->eb[i], Xq[i - 1]));
+    }
+    // ---- log p(h): -h_L in the scatter; chain j scores h_{L-1-j} under dec_j(h_{L-j})
+    if (log_ph) {
+      GaussArgs g{};
+      g.d = h->enc[L - 1].d; g.H = h->h[L - 1].p; g.ldH = h->h[L - 1].ld;
+      g.out = log_ph + r0; g.accumulate = 0; g.M = M;
+      HIPCHK(launch_gauss_fwd(h->stream, 2, g));
+    }
+    for (int j = 0; run_ph && j < L - 1; ++j) {
+      const int src = L - 1 - j, t = L - 2 - j;
+      CHK(stoch_fwd(h, h->dec[j], h->h[src], M, h->db[j]));
+      if (log_ph) {
+        GaussArgs g{};
+        g.P = h->db[j].P.p; g.ldP = h->db[j].P.ld; g.prow_div = 1; g.d = h->dec[j].d;
+        g.H = h->h[t].p; g.ldH = h->h[t].ld;
+        g.out = log_ph + r0; g.accumulate = 1; g.M = M;
+        HIPCHK(launch_gauss_fwd(h->stream, 1, g));
+      }
+      if (!gph) continue;
+      CHK(dens(h->db[j].P, 1, h->dec[j].d, h->h[t], Tp[t], true, M));
+      CHK(chain_bwd(h->dec[j], M, h->db[j], Xp[src]));
+    }
+    // ---- log p(x|h_1): the Bernoulli epilogue with the constant row weight c_px writes c_px dlogit
+    if (run_px) {
+      CHK(gemm_fwd(h, EPI_TANH, h->h[0], M, h->dense[h->o1], h->ob.y1));
+      CHK(gemm_fwd(h, EPI_TANH, h->ob.y1, M, h->dense[h->o2], h->ob.y2));
+      GemmArgs ex{};
+      ex.aux = h->x_in.p; ex.ldaux = h->x_in.ld; ex.x_row_div = k;
+      ex.part = h->part; ex.part2 = h->part2; ex.ldpart = h->ldpart;
+      ex.wa = gpx ? cpx : 1.f; ex.wb = 0.f;
+      ex.store_g = gpx ? 1 : 0;
+      Mat gm;
+      if (gpx) gm = dlogit;
+      CHK(gemm_fwd(h, EPI_BERN, h->ob.y2, M, h->dense[h->o3], gm, ex));
+      if (log_px) HIPCHK(launch_score_rowsum(h->stream, h->part, h->ldpart, h->npart, M, log_px + r0));
+      if (gpx) {
+        Mat &dY2 = dY2s[Ho], &dY1 = dY1s[Ho];
+        CHK(gemm_bwd_data(h, dlogit, M, h->dense[h->o3], dY2, &h->ob.y2, nullptr));
+        CHK(gemm_bwd_data(h, dY2, M, h->dense[h->o2], dY1, &h->ob.y1, nullptr));
+        CHK(gemm_bwd_data(h, dY1, M, h->dense[h->o1], Xo, nullptr, nullptr));
+      }
+    }
+    if (!want_g) continue;
+    // ---- grad[i] = c_q (Tq_i + Xq_i) + c_ph (Tp_i + Xp_i) + Xo (i = 0) - c_ph h_L (i = L - 1), left to right
+    SgScatter S{};
+    S.n = n; S.k = k; S.N = N; S.i0 = i0; S.nlay = L;
+    for (int i = 0; i < L; ++i) {
+      SgLayer& y = S.lay[i];
+      auto add = [&](const Mat& m, float c) { y.src[y.nsrc] = m.p; y.ld[y.nsrc] = m.ld; y.c[y.nsrc++] = c; };
+      if (gq) add(Tq[i], cq);
+      if (gq && i < L - 1) add(Xq[i], cq);
+      if (gph && i < L - 1) add(Tp[i], cph);
+      if (gph && i > 0) add(Xp[i], cph);
+      if (gpx && i == 0) add(Xo, 1.f);
+      y.c_top = gph && i == L - 1 ? cph : 0.f;
+      y.lat = lat[i];
+      y.out = grad[i]; y.d = h->enc[i].d;
+    }
+    HIPCHK(launch_sg_scatter(h->stream, S));
+  }
+  return IWAE_OK;
+}
+
 // Encoder.call (F:56-F:75): k samples of q(h|x) per image on the layer-wise
 // kernels (the rows have to reach memory), relayouted into the reference's
 // sample-major buffers.
@@ -5105,6 +5454,8 @@ long long iwae_debug_count(const iwae_handle* h, int what) {
     case 22: return h->count.binarize;
     case 23: return h->count.score;
     case 24: return h->count.score_lw;
+    case 25: return h->count.sgrad;
+    case 26: return h->count.sgrad_lw;
     default: return -1;
   }
 }

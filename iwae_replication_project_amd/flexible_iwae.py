@@ -269,6 +269,7 @@ class Flexible_Model:
         if seed is None:
             seed = int.from_bytes(os.urandom(8), "little")
         self._call(self._lib.iwae_set_seed(h, int(seed) & ((1 << 64) - 1)))
+        self._seed, self._hmc_gen = int(seed) & ((1 << 64) - 1), None
         self._call(self._lib.iwae_set_graphs(h, 1 if use_graphs else 0))
         paths = {"auto": 0, "layerwise": 1, "fused": 2, "engine": 3}
         if kernel_path not in paths:
@@ -292,6 +293,7 @@ class Flexible_Model:
         """Re-key the device Philox stream and restart its counter (reproducible
         draws from here on).  The reference has no seed."""
         self._call(self._lib.iwae_set_seed(self._h, int(seed) & ((1 << 64) - 1)))
+        self._seed, self._hmc_gen = int(seed) & ((1 << 64) - 1), None
 
     def set_noise_stream(self, stream):
         """Select the noise stream (one per rank: Philox key derived from (seed,
@@ -1003,6 +1005,130 @@ class Flexible_Model:
                 out["probs"] = probs[:, :self.x_dim].reshape(B, k, self.x_dim).transpose(0, 1).contiguous()
         self._stream.synchronize()
         return out
+
+    SCORE_GRAD_OUTPUTS = ("grad", "log_q", "log_ph", "log_px")
+
+    def score_grad(self, x, h, coef=(0.0, 1.0, 1.0), want=("grad",), chunk=0):
+        """Gradients of the scored densities with respect to the latents
+        (iwae_score_grad).  ``h`` as in ``score``; ``coef`` = (c_q, c_ph, c_px).
+        Returns a dict with the entries named in ``want``: ``"grad"``: a list of L
+        device tensors shaped like ``h``, grad[i] = c_q dlog q(h|x)/dh_i + c_ph
+        dlog p(h)/dh_i + c_px dlog p(x|h_1)/dh_i per row ((0, 1, 1): the posterior
+        score; (-1, 1, 1): dlog w/dh); ``"log_q"``, ``"log_ph"``, ``"log_px"``
+        [n_samples, B] as ``score`` returns them (``"log_w"`` added when all three
+        are asked for).  A term with coefficient 0 is not computed unless its value
+        is asked for; ``x`` may be None when neither c_q nor c_px nor their values
+        need it.  Nothing is drawn."""
+        want = (want,) if isinstance(want, str) else tuple(want)
+        bad = [w for w in want if w not in self.SCORE_GRAD_OUTPUTS]
+        if bad or not want:
+            raise ValueError(f"want must name some of {self.SCORE_GRAD_OUTPUTS}, got {want}")
+        cf = [float(c) for c in coef]
+        if len(cf) != 3:
+            raise ValueError("coef must be (c_q, c_ph, c_px)")
+        ts, k, B = self._latents(h)
+        if B <= 0 or k <= 0:
+            raise ValueError("n_samples and B must be positive")
+        with_g = "grad" in want
+        xd = None
+        if x is not None:
+            xd = self._x(x)
+            if xd.shape[0] != B:
+                raise ValueError(f"x has {xd.shape[0]} images, the latents {B}")
+        elif "log_q" in want or "log_px" in want or (with_g and (cf[0] != 0.0 or cf[2] != 0.0)):
+            raise ValueError("log q and log p(x|h), values or gradient terms, need x")
+        with torch.cuda.stream(self._stream):
+            terms = {n: torch.empty(B, k, device=self.device) for n in ("log_q", "log_ph", "log_px") if n in want}
+            gs = [torch.empty_like(t) for t in ts] if with_g else []
+        arr, n = _lib.fptr_array(ts)
+        garr, ng = _lib.fptr_array(gs)
+        carr = (ctypes.c_float * 3)(*cf)
+        self._call(self._lib.iwae_score_grad(self._h, _lib.fptr(xd), B, k, int(chunk), arr, n, carr, garr, ng,
+                                             _lib.fptr(terms.get("log_q")), _lib.fptr(terms.get("log_ph")),
+                                             _lib.fptr(terms.get("log_px"))))
+        with torch.cuda.stream(self._stream):
+            out = {n: t.t().contiguous() for n, t in terms.items()}
+            if len(terms) == 3:
+                out["log_w"] = (out["log_ph"] + out["log_px"]) - out["log_q"]
+            if with_g:
+                out["grad"] = gs
+        self._stream.synchronize()
+        return out
+
+    def hmc(self, x, h, step_size, n_leapfrog, n_iter=1, momentum=None, u=None, chunk=0):
+        """Metropolis-adjusted HMC on the latents with target p(h|x) ~ p(x, h)
+        (Hoffman 2017).  Every row (sample s, image b) of ``h`` is a chain of its
+        own, all layers move jointly, the mass matrix is the identity.  One
+        iteration: momenta r ~ N(0, I); ``n_leapfrog`` leapfrog steps (half kick
+        r += eps/2 g, drift h += eps r, half kick) with g = ``score_grad(coef=(0,
+        1, 1))``; accept iff log u < H_old - H_new, H = -(log_ph + log_px) + |r|^2
+        / 2.  ``momentum``: per iteration a list of L arrays [n_samples, B, d_i];
+        ``u``: [n_iter, n_samples, B] uniforms in (0, 1); when absent they are
+        drawn from a ``torch.Generator`` on the device seeded with the model's seed
+        (the constructor's, or the last ``set_seed``'s) that persists across calls,
+        momenta first, then u, per iteration.  The gradient and the densities run
+        in the library; the elementwise steps are torch ops on device tensors.
+        Returns (h_new: list of L device tensors, accept: bool [n_samples, B] of
+        the last iteration, mean acceptance rate over chains and iterations,
+        log p(x, h_new) [n_samples, B]); ``self.hmc_info`` keeps the last
+        iteration's proposal and its H_old / H_new per chain (diagnostics)."""
+        n_leapfrog, n_iter = int(n_leapfrog), int(n_iter)
+        if n_leapfrog <= 0 or n_iter <= 0:
+            raise ValueError("n_leapfrog and n_iter must be positive")
+        eps = float(step_size)
+        ts, k, B = self._latents(h)
+        xd = self._x(x)
+        if momentum is not None and len(momentum) != n_iter:
+            raise ValueError(f"momentum must hold {n_iter} lists (one per iteration)")
+        if self._hmc_gen is None and (momentum is None or u is None):
+            self._hmc_gen = torch.Generator(device=self.device)
+            self._hmc_gen.manual_seed(self._seed & ((1 << 63) - 1))
+        VALS = ("grad", "log_ph", "log_px")
+
+        def joint(hs):
+            o = self.score_grad(xd, hs, coef=(0.0, 1.0, 1.0), want=VALS, chunk=chunk)
+            return o["grad"], o["log_ph"] + o["log_px"]
+
+        with torch.cuda.stream(self._stream):
+            cur = [t.clone() for t in ts]
+            if u is not None:
+                ut = torch.as_tensor(u).to(device=self.device, dtype=torch.float32).reshape(n_iter, k, B)
+        g_cur, lp_cur = joint(cur)
+        acc_sum = 0.0
+        acc = None
+        for it in range(n_iter):
+            with torch.cuda.stream(self._stream):
+                if momentum is not None:
+                    r = [t.clone() for t in self._latents(momentum[it])[0]]
+                    if tuple(r[0].shape[:2]) != (k, B):
+                        raise ValueError("momentum must be shaped like h")
+                else:
+                    r = [torch.randn(t.shape, device=self.device, generator=self._hmc_gen) for t in cur]
+                lu = torch.log(ut[it] if u is not None
+                               else torch.rand(k, B, device=self.device, generator=self._hmc_gen))
+                h_old = -lp_cur + 0.5 * sum((v * v).sum(-1) for v in r)
+                q = [t.clone() for t in cur]
+                g = g_cur
+            for step in range(n_leapfrog):
+                with torch.cuda.stream(self._stream):
+                    for i in range(len(q)):
+                        r[i] += (0.5 * eps) * g[i]
+                        q[i] += eps * r[i]
+                g, lp = joint(q)
+                with torch.cuda.stream(self._stream):
+                    for i in range(len(q)):
+                        r[i] += (0.5 * eps) * g[i]
+            with torch.cuda.stream(self._stream):
+                h_new = -lp + 0.5 * sum((v * v).sum(-1) for v in r)
+                acc = lu < (h_old - h_new)                        # a NaN proposal is rejected
+                sel = acc.unsqueeze(-1)
+                cur = [torch.where(sel, a, b) for a, b in zip(q, cur)]
+                g_cur = [torch.where(sel, a, b) for a, b in zip(g, g_cur)]
+                lp_cur = torch.where(acc, lp, lp_cur)
+                acc_sum += float(acc.float().mean())
+            self.hmc_info = {"proposal": q, "h_old": h_old, "h_new": h_new}
+        self._stream.synchronize()
+        return cur, acc, acc_sum / n_iter, lp_cur
 
     def _encode(self, x, n_samples, eps=None, chunk=0):
         """iwae_encode behind ``model.encoder(x, n_samples)``."""
