@@ -947,18 +947,14 @@ hipError_t launch_transpose_lw(hipStream_t st, const float* lw_img, int Bimg, in
 // ------------------------------------- generation from the prior (fused) ----
 // gen_kernel (iwae_generate.hip): Decoder.generate_x (F:107-F:119) on 16*RT
 // generated rows per workgroup, activations resident in LDS as split bf16
-// planes (mega_fwd_kernel's storage, weight streaming and head layout): top
+// planes, on the chain machinery it shares with mega_fwd_kernel
+// (iwae_mega_dev.h: storage, weight streaming, MFMA loop, tile loop): top
 // latent h_L (given, injected or Philox) -> per prior layer tanh, tanh, head:
 // sample h -> output MLP tanh, tanh, Dense(x_dim) -> probabilities (F:101-F:102)
-// and / or Bernoulli pixel draws.
-enum GnAct { GN_TANH = 1, GN_OUT = 2, GN_HEAD = 3 };
-struct GnStage {
-  const __bf16* Whi; const __bf16* Wlo; unsigned W_bytes;
-  int ldk, N;                // FX k extent (input ones column at fin); output features (heads: 8 * ceil(d / 4) permuted)
-  int in_buf, out_buf;       // LDS buffer ids; out_buf: TANH output, HEAD destination latent
-  int act;                   // GnAct
-  int d, layer;              // HEAD: latent width, Philox layer id
-  int next_k;                // TANH / HEAD: padded K of the reader of out_buf (ones column + zero pad)
+// and / or Bernoulli pixel draws.  Stage fields: MgStage's (act: GnAct; head
+// stages: layer = the Philox layer id; K and stdnormal unused), and:
+enum GnAct { GN_TANH = MG_TANH, GN_OUT = 2, GN_HEAD = 3 };
+struct GnStage : MgStage {
   const float* eps;          // HEAD: injected noise [n][d], or null (Philox)
   float* h_out;              // HEAD: f32 copy of the sampled latent [n][d], or null
 };
@@ -1006,21 +1002,18 @@ hipError_t launch_post_weights(hipStream_t st, const PostWArgs& a);
 // post_kernel: the weighted second pass over a chunk's rows, fused.  A
 // workgroup owns up to 16*RT samples of ONE image (workgroup = image * tiles +
 // tile) and runs the encoder chain after the first layer and the output MLP
-// on them as gen_kernel / mega_fwd_kernel do (split bf16 planes in LDS, bf16x3
-// MFMA, FX weights as the A operand); the sampling and output epilogues
-// multiply by the row's w~ (tail rows: 0), reduce over the rows and write one
-// partial vector [h_1 | .. | h_L | probs] per workgroup; the row whose sample
-// index is the image's SIR index stores its latents.  post_merge_kernel sums an
-// image's partials in tile order.
-enum PoAct { PO_TANH = 1, PO_OUT = 2, PO_SAMPLE = 3 };
-struct PoStage {
-  const __bf16* Whi; const __bf16* Wlo; unsigned W_bytes;
-  int ldk, N;                // FX k extent; output features (heads: 8 * ceil(d / 4) permuted)
-  int in_buf, out_buf;       // LDS buffer ids; out_buf: TANH output, SAMPLE destination latent (-1: the top
-                             // latent, which no stage reads: summed and stored by the epilogue only)
-  int act;                   // PoAct
-  int d, layer;              // SAMPLE: latent width, Philox layer id (= encoder layer)
-  int next_k;                // TANH / SAMPLE: padded K of the reader of out_buf
+// on them with the chain machinery shared with gen_kernel / mega_fwd_kernel
+// (iwae_mega_dev.h: split bf16 planes in LDS, bf16x3 MFMA, FX weights as the A
+// operand); the sampling and output epilogues multiply by the row's w~ (tail
+// rows: 0), reduce over the rows and write one partial vector [h_1 | .. | h_L
+// | probs] per workgroup; the row whose sample index is the image's SIR index
+// stores its latents.  post_merge_kernel sums an image's partials in tile
+// order.  Stage fields: MgStage's (act: PoAct;
+// out_buf of a SAMPLE stage -1: the top latent, which no stage reads: summed
+// and stored by the epilogue only; layer: Philox layer id = encoder layer; K
+// and stdnormal unused), and:
+enum PoAct { PO_TANH = MG_TANH, PO_OUT = 2, PO_SAMPLE = 3 };
+struct PoStage : MgStage {
   int part_off;              // SAMPLE / OUT: float offset of this stage's sums in the partial vector
 };
 struct PoLaunch {

@@ -1,9 +1,17 @@
-// Device code shared by the fused k-sample forward (mega_fwd_kernel,
-// iwae_mega.hip, whose head comment describes the pipeline) and the scoring
-// kernel built on its stages (score_kernel, iwae_score.hip): LDS buffers,
-// weight-fragment fetch, the bf16x3 MFMA loop, the epilogues and one Dense
-// stage.  The two kernels live in separate translation units so that the NLL
-// kernel's code does not depend on the other's presence.
+// Device code shared by every fused kernel that runs a chain of Dense stages
+// in LDS: the fused k-sample forward (mega_fwd_kernel, iwae_mega.hip, whose
+// head comment describes the pipeline), the scoring kernel built on its stages
+// (score_kernel, iwae_score.hip), generation from the prior (gen_kernel,
+// iwae_generate.hip) and the posterior's weighted second pass (post_kernel,
+// iwae_posterior.hip); sg_kernel (iwae_scoregrad.hip) takes the basic pieces
+// (MgBuf, the vector types, mg_pad, the barrier) and has its own tile code.
+// Here: LDS buffers, weight-fragment fetch, the bf16x3 MFMA loop, the tanh
+// epilogue, the barrier, and the loop over a wave's column tiles (mg_tiles),
+// which gen_kernel and post_kernel call with epilogues of their own.
+// mega_fwd_kernel and score_kernel keep their Dense stage (mg_tile / mg_dense,
+// with their operand requests and epilogues) as a second, written-out copy of
+// that loop (see the comment there).  Every kernel lives in its own
+// translation unit, so no kernel's code depends on another's presence.
 #pragma once
 #include "iwae_kernels.h"
 
@@ -50,8 +58,8 @@ __device__ __forceinline__ mg_bf16x8 mg_as_bf16x8(mg_u32x4 v) { return __builtin
 struct MgBuf {
   __bf16* hi; __bf16* lo; int ld;
 };
-template <int RT>
-__device__ __forceinline__ MgBuf mg_buf(const MgLaunch& L, int b) {
+template <int RT, class LT>
+__device__ __forceinline__ MgBuf mg_buf(const LT& L, int b) {
   __bf16* base = reinterpret_cast<__bf16*>(mgs);
   MgBuf B;
   B.ld = L.buf_ld[b];
@@ -355,6 +363,61 @@ __device__ __forceinline__ void mg_lds_barrier() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
+// One Dense stage of gen_kernel / post_kernel: the loop over the column tiles
+// of a wave (wave w owns the tiles w, w + NW, ...) from buffer S.in_buf.  Per
+// tile the MFMAs run over the whole K, then EPI::run(L, S, OUT, t, acc, a...)
+// consumes the accumulators (EPI: a tag type, so the epilogue is a plain
+// forceinline function taking its context by reference; OUT: buffer out_buf).
+// When the whole K fits one fetch (ldk <= 256) the first MG_PF steps of the
+// wave's next tile are requested during the current tile's MFMAs (mg_mma).
+// Call it from the kernel's stage switch directly and keep the wide-K fetch
+// written in place (not mg_fetch): the register allocation of the two
+// kernels depends on both.
+template <int RT, int NW, class EPI, class LT, class ST, class... A>
+__device__ __forceinline__ void mg_tiles(const LT& L, const ST& S, int out_buf, A&&... a) {
+  const int wave = threadIdx.x >> 6;
+  const int ntile = (S.N + 15) >> 4;
+  const MgBuf IN = mg_buf<RT>(L, S.in_buf);
+  const MgBuf OUT = mg_buf<RT>(L, out_buf);
+  const __amdgpu_buffer_rsrc_t rh = buf_rsrc(S.Whi, S.W_bytes), rl = buf_rsrc(S.Wlo, S.W_bytes);
+  if (S.ldk <= 32 * MG_KS) {
+    MgFrag f;
+    const int ns = S.ldk >> 5;
+    if (wave < ntile) {
+      const unsigned vb = mg_frag_base(S, wave, 0);
+#pragma unroll
+      for (int u = 0; u < MG_PF; ++u) mg_fetch_step(rh, rl, vb, u, ns, f);
+    }
+    for (int t = wave; t < ntile; t += NW) {
+      const int tn = t + NW;
+      const unsigned vb = mg_frag_base(S, t, 0);
+#pragma unroll
+      for (int u = MG_PF; u < MG_KS; ++u) mg_fetch_step(rh, rl, vb, u, ns, f);
+      mg_f32x4 acc[RT];
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt) acc[rt] = (mg_f32x4){0.f, 0.f, 0.f, 0.f};
+      mg_mma<RT>(IN, 0, min(MG_KS, ns), f, acc, rh, rl, tn < ntile, mg_frag_base(S, tn, 0), ns);
+      EPI::run(L, S, OUT, t, acc, a...);
+    }
+  } else {
+    // wide K: 256-deep fetches, no prefetch across tiles
+    for (int t = wave; t < ntile; t += NW) {
+      mg_f32x4 acc[RT];
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt) acc[rt] = (mg_f32x4){0.f, 0.f, 0.f, 0.f};
+      for (int k0 = 0; k0 < S.ldk; k0 += 32 * MG_KS) {
+        MgFrag f;
+        const unsigned vb = mg_frag_base(S, t, k0);
+        const int ns = (S.ldk - k0) >> 5;
+#pragma unroll
+        for (int u = 0; u < MG_KS; ++u) mg_fetch_step(rh, rl, vb, u, ns, f);
+        mg_mma<RT>(IN, k0, min(MG_KS, ns), f, acc, rh, rl, false, kOOB, 0);
+      }
+      EPI::run(L, S, OUT, t, acc, a...);
+    }
+  }
+}
+
 // ---- score_kernel's stage kinds (ScAct): operand requests and epilogues
 // defined in iwae_score.hip, compiled into its instantiations only (the
 // branches below that name them are discarded for MgAct stage kinds).
@@ -378,6 +441,14 @@ template <int RT, int ACT>
 __device__ __forceinline__ void sc_epilogue(const ScLaunch& L, const MgStage& S, int t, const mg_f32x4 (&acc)[RT],
                                             const float4 (&xv)[RT], const ScTargets<RT, true>& T, ScRows<RT>& R);
 
+// ---- mega_fwd_kernel's and score_kernel's own tile loop.  mg_tile / mg_dense
+// are mg_tiles' two branches written out with these kernels' operand requests
+// (pixels, density targets) ahead of the MFMAs and their epilogues in place.
+// They have not moved onto a shared loop: an attempt through one with an
+// operand hook changed the device assembly of both kernels throughout, and
+// the NLL kernel's tuned code is not traded for these 40 lines.  A change to
+// the loop's structure is made here and in mg_tiles.
+//
 // One column tile: x operands (Bernoulli stage) requested first, MFMAs over
 // the whole K, epilogue.
 template <int RT, int ACT, bool MASK, class LT, class RW>

@@ -3799,6 +3799,69 @@ int iwae_e_log_px(iwae_handle* h, const float* x, int B, int k, const float* con
   return IWAE_OK;
 }
 
+// ------------------------------------------------ fused-chain plans
+// What the plans of the kernels built on iwae_mega_dev.h (mega_fwd_kernel,
+// gen_kernel, post_kernel) and sg_kernel's share: the buffer widths the stages
+// need, the stage record's weight fields, and the LDS layout of the buffers.
+static int r32(int x) { return (x + 31) & ~31; }
+
+// Widths (bf16 columns) of a plan's LDS buffers.
+struct ChainBufs {
+  std::vector<int> width;
+  explicit ChainBufs(int nb) : width(nb, 0) {}
+  void widen(int b, int w) { width[b] = std::max(width[b], w); }
+  // a Dense stage of padded K ldk read from `in`; out >= 0: its N outputs are
+  // stored there as activations, padded to the reader's K (next_k)
+  void dense(int ldk, int N, int in, int out, int next_k) {
+    widen(in, ldk);
+    if (out >= 0) widen(out, std::max(N, next_k));
+  }
+  // Each buffer = hi and lo bf16 planes [R][ld].  Row stride s dwords (ld = 2 s):
+  // s = 8 mod 16 makes the fragment reads (ds_read_b128) conflict-free; s = 4
+  // mod 8 (2-way) is the fallback of the plans that try one.  Fills buf_ld /
+  // buf_off (bf16 units) and returns the bf16 units used.  The plans call it
+  // per candidate, so a plan that returns false leaves its last candidate's
+  // strides, offsets and LDS size behind and does not touch rt (the callers
+  // start it at 0): a plan, rt and lds are read only on true.
+  int layout(int R, bool fallback, int* buf_ld, int* buf_off) const {
+    int off = 0;
+    for (size_t b = 0; b < width.size(); ++b) {
+      int sdw = (std::max(width[b], 32) + 1) / 2;
+      while (fallback ? sdw % 8 != 4 : sdw % 16 != 8) ++sdw;
+      buf_ld[b] = 2 * sdw;
+      buf_off[b] = off;
+      off += 2 * R * buf_ld[b];
+    }
+    return off;
+  }
+};
+
+// Dense layer di as a stage of kind act (TANH is MG_TANH in every kernel's
+// enum) reading in and writing out: the buffers widened, and, unless S is null
+// (a stage the call does not run), its record filled.  Weights: the
+// fragment-major split copies (FX, the train engine's): one 16-byte load per
+// lane reads 1 KiB contiguous per wave.
+static void chain_stage(const iwae_handle* h, ChainBufs& W, MgStage* S, int di, int in, int out, int act, int next_k) {
+  const DenseL& d = h->dense[di];
+  W.dense(d.ldF, d.fout, in, act == MG_TANH ? out : -1, next_k);
+  if (!S) return;
+  S->Whi = h->fx_hi + d.fx_off; S->Wlo = h->fx_lo + d.fx_off;
+  S->W_bytes = (unsigned)((h->fx_elems - d.fx_off) * (long long)sizeof(__bf16));
+  S->ldk = d.ldF; S->K = d.fin + 1; S->N = d.fout;
+  S->in_buf = in; S->out_buf = out; S->act = act; S->next_k = next_k;
+}
+// A stochastic layer's head (rows permuted into [mu | zs] groups of 8) of
+// latent width dd, sampled into / scored against buffer out (-1: post_plan's
+// top latent, which has no buffer to widen; every other head has one)
+static void chain_head(const iwae_handle* h, ChainBufs& W, MgStage* S, int di, int in, int out, int act, int dd,
+                       int layer) {
+  chain_stage(h, W, S, di, in, out, act, r32(dd + 1));
+  if (out >= 0) W.widen(out, r32(dd + 1));
+  if (!S) return;
+  S->N = 8 * ((dd + 3) / 4);
+  S->d = dd; S->layer = layer;
+}
+
 // ------------------------------------------------ fused k-sample forward
 // Plan of mega_fwd_kernel for this model (iwae_mega.hip).  LDS buffers: h_0 ..
 // h_{L-2} kept (ids 0 .. L-2), scratch P (id L-1, also holds h_{L-1}) and Q
@@ -3810,32 +3873,20 @@ int iwae_e_log_px(iwae_handle* h, const float* x, int B, int k, const float* con
 static bool mega_plan(iwae_handle* h, MgLaunch& M, int& rt, int& waves, size_t& lds) {
   const int L = h->L;
   std::memset(&M, 0, sizeof(M));
-  auto r32 = [](int x) { return (x + 31) & ~31; };
   const int bP = L - 1, bQ = L;
   auto hbuf = [&](int i) { return i == L - 1 ? bP : i; };
   const int nb = L + 1;
   if (nb > kMgMaxBufs) return false;
-  std::vector<int> width(nb, 0);
+  ChainBufs W(nb);
   std::vector<MgStage> st;
   auto stage = [&](int di, int in, int out, int act, int next_k) {
-    const DenseL& d = h->dense[di];
-    MgStage S{};
-    // fragment-major split copies (FX, the train engine's): one 16-byte load
-    // per lane reads 1 KiB contiguous per wave
-    S.Whi = h->fx_hi + d.fx_off; S.Wlo = h->fx_lo + d.fx_off;
-    S.W_bytes = (unsigned)((h->fx_elems - d.fx_off) * (long long)sizeof(__bf16));
-    S.ldk = d.ldF; S.K = d.fin + 1; S.N = d.fout;
-    S.in_buf = in; S.out_buf = out; S.act = act; S.next_k = next_k;
-    width[in] = std::max(width[in], S.ldk);
-    if (act == MG_TANH) width[out] = std::max(width[out], std::max(S.N, next_k));
-    st.push_back(S);
-    return (int)st.size() - 1;
+    st.emplace_back();
+    chain_stage(h, W, &st.back(), di, in, out, act, next_k);
   };
   auto head = [&](int di, int in, int out, int act, int dd, int layer, int stdnormal) {
-    const int s = stage(di, in, out, act, r32(dd + 1));
-    st[s].N = 8 * ((dd + 3) / 4);
-    st[s].d = dd; st[s].layer = layer; st[s].stdnormal = stdnormal;
-    width[out] = std::max(width[out], r32(dd + 1));
+    st.emplace_back();
+    chain_head(h, W, &st.back(), di, in, out, act, dd, layer);
+    st.back().stdnormal = stdnormal;
   };
   for (int i = 1; i < L; ++i) {
     const StochL& E = h->enc[i];
@@ -3854,11 +3905,9 @@ static bool mega_plan(iwae_handle* h, MgLaunch& M, int& rt, int& waves, size_t& 
   stage(h->o2, bQ, bP, MG_TANH, h->dense[h->o3].ldF);
   stage(h->o3, bP, -1, MG_BERN, 0);
   if ((int)st.size() > kMgMaxStages) return false;
-  width[h0] = std::max(width[h0], r32(h->enc[0].d + 1));
-  // LDS layout: each buffer = hi and lo bf16 planes [R][ld], then logq, logp [R]
-  // and the [8][R] reduction scratch as floats.  Row stride s dwords (ld = 2s):
-  // s = 8 mod 16 makes the fragment reads (ds_read_b128) conflict-free; s = 4
-  // mod 8 (2-way) is the fallback when that does not fit.
+  W.widen(h0, r32(h->enc[0].d + 1));
+  // LDS layout: the buffers (ChainBufs::layout, conflict-free strides first),
+  // then logq, logp [R] and the [8][R] reduction scratch as floats.
   // 8-wave workgroups of 64 / 32 / 16 rows, or (h->tune.mg_waves == 4) 4-wave
   // workgroups of 32 rows, two per CU
   waves = h->tune.mg_waves == 4 ? 4 : 8;
@@ -3866,15 +3915,7 @@ static bool mega_plan(iwae_handle* h, MgLaunch& M, int& rt, int& waves, size_t& 
     if (waves == 4 && c != 2) continue;
     const int R = 16 * c;
     for (int pass = 0; pass < 2; ++pass) {
-      int off = 0;                              // bf16 units
-      for (int b = 0; b < nb; ++b) {
-        int sdw = (std::max(width[b], 32) + 1) / 2;
-        if (pass == 0) while (sdw % 16 != 8) ++sdw;
-        else while (sdw % 8 != 4) ++sdw;
-        M.buf_ld[b] = 2 * sdw;
-        M.buf_off[b] = off;
-        off += 2 * R * M.buf_ld[b];
-      }
+      const int off = W.layout(R, pass == 1, M.buf_ld, M.buf_off);
       M.acc_off = (off + 3) / 2 & ~1;           // floats
       const size_t bytes = (size_t)(M.acc_off + 2 * R + 8 * R) * sizeof(float);
       if (bytes <= (waves == 4 ? 80 : 160) * 1024) {
@@ -3909,7 +3950,6 @@ static bool nring_plan(iwae_handle* h, NrLaunch& R) {
       units.push_back(NrUnit{(unsigned)((d.fx_off + (long long)t * S.ns * 512) * (long long)sizeof(__bf16)), S.ns});
     return S.ns <= 8 && d.ldF % 32 == 0;
   };
-  auto r32 = [](int x) { return (x + 31) & ~31; };
   bool ok = true;
   if (L == 2) {
     const StochL& E = h->enc[1];
@@ -4255,6 +4295,33 @@ int iwae_encoder_means(iwae_handle* h, const float* x, int N, int n, const float
   return IWAE_OK;
 }
 
+// Decoder.generate_x's prior chain (F:106-F:119), layer-wise, over `rows` rows:
+// h_{L-2-j} drawn from dec[j](h_{L-1-j}) for j = 0 .. L-2, h_{L-1} in place.
+// eps: prior layer j's injected noise eps[j] [rows][d], or null: Philox, in a
+// stream of its own (layer ids IWAE_MAX_LAYERS + j).  h_out: tight f32 copies
+// h_out[i] [rows][d_i] of the drawn h_i, or null.
+static int prior_chain_fwd(iwae_handle* h, int rows, const float* const* eps, float* const* h_out) {
+  const int L = h->L;
+  for (int j = 0; j < L - 1; ++j) {
+    CHK(stoch_fwd(h, h->dec[j], h->h[L - 1 - j], rows, h->db[j]));
+    GaussArgs g{};
+    g.P = h->db[j].P.p; g.ldP = h->db[j].P.ld; g.prow_div = 1; g.d = h->dec[j].d;
+    g.H = h->h[L - 2 - j].p; g.ldH = h->h[L - 2 - j].ld;
+    g.eps_a = eps ? eps[j] : nullptr;
+    if (eps && !g.eps_a) return fail(h, IWAE_EINVAL, "NULL eps buffer");
+    g.kS = 1; g.Bsplit = rows; g.Bimg = rows;
+    g.seed = h->seed; g.rng_base = &h->ds->rng[0]; g.layer = IWAE_MAX_LAYERS + j;
+    g.out = h->logp; g.accumulate = 0; g.M = rows;
+    HIPCHK(launch_gauss_fwd(h->stream, 0, g));
+    if (h_out) {
+      const size_t wb = (size_t)g.d * sizeof(float);
+      HIPCHK(hipMemcpy2DAsync(h_out[L - 2 - j], wb, g.H, (size_t)g.ldH * sizeof(float), wb, rows,
+                              hipMemcpyDeviceToDevice, h->stream));
+    }
+  }
+  return IWAE_OK;
+}
+
 // reconstructed_x_probs / get_reconstruction_loss (F:249-F:262): one encoder
 // sample, keep h_L, re-draw h_{L-1} .. h_1 from the decoder's prior layers
 // (Decoder.generate_x, F:106-F:119), then the output MLP.
@@ -4278,18 +4345,7 @@ int iwae_reconstruct(iwae_handle* h, const float* x, int B, const float* const* 
   CHK(ensure_capacity(h, B, B, false));
   CHK(copy_x(h, P, x));
   CHK(encoder_fwd(h, P, E, false));
-  for (int j = 0; j < L - 1; ++j) {
-    CHK(stoch_fwd(h, h->dec[j], h->h[L - 1 - j], B, h->db[j]));
-    GaussArgs g{};
-    g.P = h->db[j].P.p; g.ldP = h->db[j].P.ld; g.prow_div = 1; g.d = h->dec[j].d;
-    g.H = h->h[L - 2 - j].p; g.ldH = h->h[L - 2 - j].ld;
-    g.eps_a = injected ? eps[L + j] : nullptr;
-    if (injected && !g.eps_a) return fail(h, IWAE_EINVAL, "NULL eps buffer");
-    g.kS = 1; g.Bsplit = B; g.Bimg = B;
-    g.seed = h->seed; g.rng_base = &h->ds->rng[0]; g.layer = IWAE_MAX_LAYERS + j;   // own Philox stream
-    g.out = h->logp; g.accumulate = 0; g.M = B;
-    HIPCHK(launch_gauss_fwd(h->stream, 0, g));
-  }
+  CHK(prior_chain_fwd(h, B, injected ? eps + L : nullptr, nullptr));
   CHK(gemm_fwd(h, EPI_TANH, h->h[0], B, h->dense[h->o1], h->ob.y1));
   CHK(gemm_fwd(h, EPI_TANH, h->ob.y1, B, h->dense[h->o2], h->ob.y2));
   if (probs) {
@@ -4321,54 +4377,29 @@ int iwae_reconstruct(iwae_handle* h, const float* x, int B, const float* const* 
 static bool gen_plan(iwae_handle* h, GnLaunch& G, int& rt, size_t& lds) {
   const int L = h->L;
   std::memset(&G, 0, sizeof(G));
-  auto r32 = [](int x) { return (x + 31) & ~31; };
   const int bP = L, bQ = L + 1, nb = L + 2;
   if (nb > kMgMaxBufs || 3 * L > kMgMaxStages) return false;
-  std::vector<int> width(nb, 0);
-  auto stage = [&](int di, int in, int out, int act, int next_k) -> GnStage& {
-    const DenseL& d = h->dense[di];
-    GnStage& S = G.st[G.nst++];
-    S.Whi = h->fx_hi + d.fx_off; S.Wlo = h->fx_lo + d.fx_off;
-    S.W_bytes = (unsigned)((h->fx_elems - d.fx_off) * (long long)sizeof(__bf16));
-    S.ldk = d.ldF; S.N = d.fout;
-    S.in_buf = in; S.out_buf = out; S.act = act; S.next_k = next_k;
-    width[in] = std::max(width[in], S.ldk);
-    if (act == GN_TANH) width[out] = std::max(width[out], std::max(S.N, next_k));
-    return S;
+  ChainBufs W(nb);
+  auto stage = [&](int di, int in, int out, int act, int next_k) {
+    chain_stage(h, W, &G.st[G.nst++], di, in, out, act, next_k);
   };
   for (int j = 0; j < L - 1; ++j) {
     const StochL& D = h->dec[j];
     stage(D.l1, L - 1 - j, bQ, GN_TANH, h->dense[D.l2].ldF);
     stage(D.l2, bQ, bP, GN_TANH, h->dense[D.head].ldF);
-    GnStage& S = stage(D.head, bP, L - 2 - j, GN_HEAD, r32(D.d + 1));
-    S.N = 8 * ((D.d + 3) / 4);
-    S.d = D.d; S.layer = IWAE_MAX_LAYERS + j;
-    width[L - 2 - j] = std::max(width[L - 2 - j], r32(D.d + 1));
+    chain_head(h, W, &G.st[G.nst++], D.head, bP, L - 2 - j, GN_HEAD, D.d, IWAE_MAX_LAYERS + j);
   }
   stage(h->o1, 0, bQ, GN_TANH, h->dense[h->o2].ldF);
   stage(h->o2, bQ, bP, GN_TANH, h->dense[h->o3].ldF);
   stage(h->o3, bP, -1, GN_OUT, 0);
   G.d_top = h->enc[L - 1].d; G.top_buf = L - 1; G.top_next_k = r32(G.d_top + 1);
   G.top_layer = IWAE_MAX_LAYERS + L - 1; G.pix_layer = 2 * IWAE_MAX_LAYERS;
-  width[L - 1] = std::max(width[L - 1], G.top_next_k);
-  int per_row = 0;                               // bf16 units per row: both planes of every buffer
-  for (int b = 0; b < nb; ++b) {
-    int sdw = (std::max(width[b], 32) + 1) / 2;
-    while (sdw % 16 != 8) ++sdw;
-    G.buf_ld[b] = 2 * sdw;
-    per_row += 2 * G.buf_ld[b];
+  W.widen(L - 1, G.top_next_k);
+  for (int c : {4, 2, 1}) {
+    lds = (size_t)W.layout(16 * c, false, G.buf_ld, G.buf_off) * sizeof(__bf16);
+    if (lds <= 160 * 1024) { rt = c; return true; }
   }
-  rt = 0;
-  for (int c : {4, 2, 1})
-    if ((size_t)16 * c * per_row * sizeof(__bf16) <= 160 * 1024) { rt = c; break; }
-  if (!rt) return false;
-  int off = 0;
-  for (int b = 0; b < nb; ++b) {
-    G.buf_off[b] = off;
-    off += 2 * 16 * rt * G.buf_ld[b];
-  }
-  lds = (size_t)off * sizeof(__bf16);
-  return true;
+  return false;
 }
 
 int iwae_generate(iwae_handle* h, int n, const float* h_top, const float* const* eps, int n_eps, const float* u,
@@ -4426,22 +4457,7 @@ int iwae_generate(iwae_handle* h, int n, const float* h_top, const float* const*
   const int dL = h->enc[L - 1].d;
   HIPCHK(launch_gen_top(h->stream, h_top ? h_top : eps_top, n, dL, h->h[L - 1].p, h->h[L - 1].ld,
                         keep ? h_out[L - 1] : nullptr, h->seed, &h->ds->rng[0], IWAE_MAX_LAYERS + L - 1));
-  for (int j = 0; j < L - 1; ++j) {
-    CHK(stoch_fwd(h, h->dec[j], h->h[L - 1 - j], n, h->db[j]));
-    GaussArgs g{};
-    g.P = h->db[j].P.p; g.ldP = h->db[j].P.ld; g.prow_div = 1; g.d = h->dec[j].d;
-    g.H = h->h[L - 2 - j].p; g.ldH = h->h[L - 2 - j].ld;
-    g.eps_a = eps_pri ? eps_pri[j] : nullptr;
-    g.kS = 1; g.Bsplit = n; g.Bimg = n;
-    g.seed = h->seed; g.rng_base = &h->ds->rng[0]; g.layer = IWAE_MAX_LAYERS + j;
-    g.out = h->logp; g.accumulate = 0; g.M = n;
-    HIPCHK(launch_gauss_fwd(h->stream, 0, g));
-    if (keep) {
-      const size_t wb = (size_t)g.d * sizeof(float);
-      HIPCHK(hipMemcpy2DAsync(h_out[L - 2 - j], wb, g.H, (size_t)g.ldH * sizeof(float), wb, n,
-                              hipMemcpyDeviceToDevice, h->stream));
-    }
-  }
+  CHK(prior_chain_fwd(h, n, eps_pri, keep ? h_out : nullptr));
   CHK(gemm_fwd(h, EPI_TANH, h->h[0], n, h->dense[h->o1], h->ob.y1));
   CHK(gemm_fwd(h, EPI_TANH, h->ob.y1, n, h->dense[h->o2], h->ob.y2));
   Mat pm;                                        // the logits, then the probabilities, in the caller's buffer
@@ -4493,64 +4509,43 @@ int iwae_binarize(iwae_handle* h, const float* x, long long n_src, const long lo
 static bool post_plan(iwae_handle* h, bool enc, bool out, PoLaunch& G, int& rt, size_t& lds) {
   const int L = h->L;
   std::memset(&G, 0, sizeof(G));
-  auto r32 = [](int x) { return (x + 31) & ~31; };
   const int nl = std::max(1, L - 1), bP = nl, bQ = nl + 1, nb = nl + 2;
   if (nb > kMgMaxBufs || 3 * L > kMgMaxStages) return false;
-  std::vector<int> width(nb, 0);
-  auto stage = [&](int di, int in, int ob, int act, int next_k, bool emit) -> PoStage* {
-    const DenseL& d = h->dense[di];
-    width[in] = std::max(width[in], d.ldF);
-    if (act == PO_TANH) width[ob] = std::max(width[ob], std::max(d.fout, next_k));
-    if (!emit) return nullptr;
-    PoStage& S = G.st[G.nst++];
-    S.Whi = h->fx_hi + d.fx_off; S.Wlo = h->fx_lo + d.fx_off;
-    S.W_bytes = (unsigned)((h->fx_elems - d.fx_off) * (long long)sizeof(__bf16));
-    S.ldk = d.ldF; S.N = d.fout;
-    S.in_buf = in; S.out_buf = ob; S.act = act; S.next_k = next_k;
-    return &S;
-  };
+  ChainBufs W(nb);
+  auto next = [&](bool emit) -> PoStage* { return emit ? &G.st[G.nst++] : nullptr; };
   const int d0 = h->enc[0].d;
   int off = d0;                                  // h_1's sums come first (the prologue's)
   for (int i = 1; i < L; ++i) {
     const StochL& E = h->enc[i];
-    stage(E.l1, i - 1, bP, PO_TANH, h->dense[E.l2].ldF, enc);
-    stage(E.l2, bP, bQ, PO_TANH, h->dense[E.head].ldF, enc);
-    if (PoStage* S = stage(E.head, bQ, i < nl ? i : -1, PO_SAMPLE, r32(E.d + 1), enc)) {
-      S->N = 8 * ((E.d + 3) / 4);
-      S->d = E.d; S->layer = i; S->part_off = off;
-    }
-    if (i < nl) width[i] = std::max(width[i], r32(E.d + 1));
+    chain_stage(h, W, next(enc), E.l1, i - 1, bP, PO_TANH, h->dense[E.l2].ldF);
+    chain_stage(h, W, next(enc), E.l2, bP, bQ, PO_TANH, h->dense[E.head].ldF);
+    PoStage* S = next(enc);
+    chain_head(h, W, S, E.head, bQ, i < nl ? i : -1, PO_SAMPLE, E.d, i);
+    if (S) S->part_off = off;
     off += E.d;
   }
-  stage(h->o1, 0, bQ, PO_TANH, h->dense[h->o2].ldF, out);
-  stage(h->o2, bQ, bP, PO_TANH, h->dense[h->o3].ldF, out);
-  if (PoStage* S = stage(h->o3, bP, -1, PO_OUT, 0, out)) S->part_off = off;
+  chain_stage(h, W, next(out), h->o1, 0, bQ, PO_TANH, h->dense[h->o2].ldF);
+  chain_stage(h, W, next(out), h->o2, bQ, bP, PO_TANH, h->dense[h->o3].ldF);
+  PoStage* S3 = next(out);
+  chain_stage(h, W, S3, h->o3, bP, -1, PO_OUT, 0);
+  if (S3) S3->part_off = off;
   G.ld_part = r4(off + h->xdim);
   G.d0 = d0; G.h0_buf = 0; G.h0_next_k = r32(d0 + 1);
-  width[0] = std::max(width[0], G.h0_next_k);
+  W.widen(0, G.h0_next_k);
   // h_1 as f32 [rows][d0] in the scratch buffer the first stage does not write
-  width[bP] = std::max(width[bP], d0);
-  width[bQ] = std::max(width[bQ], d0);
+  W.widen(bP, d0);
+  W.widen(bQ, d0);
   G.stage_buf = (G.nst > 0 && G.st[0].out_buf == bQ) ? bP : bQ;
-  int per_row = 0;                               // bf16 units per row: both planes of every buffer
-  for (int b = 0; b < nb; ++b) {
-    int sdw = (std::max(width[b], 32) + 1) / 2;
-    while (sdw % 16 != 8) ++sdw;
-    G.buf_ld[b] = 2 * sdw;
-    per_row += 2 * G.buf_ld[b];
+  for (int c : {4, 2, 1}) {
+    const int R = 16 * c;
+    const int o = W.layout(R, false, G.buf_ld, G.buf_off);
+    lds = (size_t)o * sizeof(__bf16) + (size_t)R * sizeof(float);
+    if (lds > 160 * 1024) continue;
+    rt = c;
+    G.w_off = o / 2;                             // the rows' weights, as floats, behind the buffers
+    return true;
   }
-  rt = 0;
-  for (int c : {4, 2, 1})
-    if ((size_t)16 * c * (per_row * sizeof(__bf16) + sizeof(float)) <= 160 * 1024) { rt = c; break; }
-  if (!rt) return false;
-  int o = 0;
-  for (int b = 0; b < nb; ++b) {
-    G.buf_off[b] = o;
-    o += 2 * 16 * rt * G.buf_ld[b];
-  }
-  G.w_off = o / 2;                               // the rows' weights, as floats, behind the buffers
-  lds = (size_t)o * sizeof(__bf16) + (size_t)16 * rt * sizeof(float);
-  return true;
+  return false;
 }
 
 // Two passes per chunk of images (all k samples of an image in one chunk):
@@ -4974,18 +4969,16 @@ static bool sgrad_plan(const iwae_handle* h, bool run_q, bool run_ph, bool run_p
                        SgLaunch& S, int& rt, size_t& lds) {
   const int L = h->L;
   std::memset(&S, 0, sizeof(S));
-  auto r32 = [](int x) { return (x + 31) & ~31; };
   const int bA = L, bB = L + 1, bP = L + 2, nb = L + 3;
   if (nb > kMgMaxBufs || L > 8) return false;
-  std::vector<int> width(nb, 0);
+  ChainBufs W(nb);
   std::vector<SgStage> st;
   auto fwd = [&](int di, int in, int out, int kind, int next_k) {
     const DenseL& d = h->dense[di];
     SgStage T{};
     T.woff = (unsigned)d.fx_off; T.ldk = (short)d.ldF; T.N = (short)d.fout;
     T.in_buf = (signed char)in; T.out_buf = (signed char)out; T.kind = (signed char)kind; T.next_k = (short)next_k;
-    width[in] = std::max(width[in], d.ldF);
-    if (kind == SG_TANH) width[out] = std::max(width[out], std::max(d.fout, next_k));
+    W.dense(d.ldF, d.fout, in, kind == SG_TANH ? out : -1, next_k);
     st.push_back(T);
     return (int)st.size() - 1;
   };
@@ -4994,8 +4987,7 @@ static bool sgrad_plan(const iwae_handle* h, bool run_q, bool run_ph, bool run_p
     SgStage T{};
     T.woff = (unsigned)d.gx_off; T.ldk = (short)(32 * d.gx_steps); T.N = (short)d.fin;
     T.in_buf = (signed char)in; T.out_buf = (signed char)out; T.kind = (signed char)kind; T.layer = (signed char)layer;
-    width[in] = std::max(width[in], 32 * d.gx_steps);
-    if (out >= 0) width[out] = std::max(width[out], d.fin);
+    W.dense(32 * d.gx_steps, d.fin, in, out, 0);
     st.push_back(T);
   };
   for (int i = 0; i < 8; ++i) { S.lat_d[i] = i < L ? h->enc[i].d : 0; S.lat_buf[i] = -1; S.lat_next_k[i] = 0; }
@@ -5008,7 +5000,7 @@ static bool sgrad_plan(const iwae_handle* h, bool run_q, bool run_ph, bool run_p
     S.lat_buf[src] = src;
     S.lat_next_k[src] = std::max(S.lat_next_k[src], h->dense[C.l1].ldF);
     if (c == 0.f) return;
-    width[bP] = std::max(width[bP], std::max(gk, 2 * C.d));
+    W.widen(bP, std::max(gk, 2 * C.d));
     bwd(C.head, bP, bB, SG_GTANH, 0);
     bwd(C.l2, bB, bA, SG_GTANH, 0);
     bwd(C.l1, bA, -1, SG_GX, src);
@@ -5026,7 +5018,7 @@ static bool sgrad_plan(const iwae_handle* h, bool run_q, bool run_ph, bool run_p
     S.out_gx_woff = (int)d3.gx_off; S.out_gx_ldk = 32 * d3.gx_steps; S.out_gx_N = d3.fin;
     if (cpx != 0.f) {
       if ((d3.fin + 15) / 16 > kSgOutTiles * kSgWaves) return false;
-      width[bP] = std::max(width[bP], 256);
+      W.widen(bP, 256);
       bwd(h->o2, bB, bA, SG_GTANH, 0);
       bwd(h->o1, bA, -1, SG_GX, 0);
     }
@@ -5035,20 +5027,12 @@ static bool sgrad_plan(const iwae_handle* h, bool run_q, bool run_ph, bool run_p
   for (const SgStage& T : st)
     if (T.ldk > 32000 || T.N > 32000) return false;
   for (int i = 0; i < L; ++i)
-    if (S.lat_buf[i] >= 0) width[i] = std::max(width[i], S.lat_next_k[i]);
+    if (S.lat_buf[i] >= 0) W.widen(i, S.lat_next_k[i]);
   // LDS: the bf16 buffers (mega_plan's strides), the f32 gradient tiles, logq / logp
   for (int c : {4, 2, 1}) {
     const int R = 16 * c;
     for (int pass = 0; pass < 2; ++pass) {
-      int off = 0;                              // bf16 units
-      for (int b = 0; b < nb; ++b) {
-        int sdw = (std::max(width[b], 32) + 1) / 2;
-        if (pass == 0) while (sdw % 16 != 8) ++sdw;
-        else while (sdw % 8 != 4) ++sdw;
-        S.buf_ld[b] = 2 * sdw;
-        S.buf_off[b] = off;
-        off += 2 * R * S.buf_ld[b];
-      }
+      const int off = W.layout(R, pass == 1, S.buf_ld, S.buf_off);
       int foff = (off + 3) / 2 & ~1;            // floats
       foff = std::max(foff, 3 * kSgWaves * R);  // (the value sums' scratch reuses the buffers)
       for (int i = 0; i < L; ++i) {

@@ -13,20 +13,23 @@
 //   post_merge_kernel     an image's per-workgroup partial sums added in tile order
 //   group_wsum_kernel     pass 2 of the layer-wise path: weighted sums over rows in HBM
 //
-// post_kernel's machinery is mega_fwd_kernel's and gen_kernel's (iwae_mega.hip,
-// iwae_generate.hip), copied here so those kernels' code size and register
-// budget stay as tuned: bf16x3 products on v_mfma_f32_16x16x32_bf16, the
-// weights as the A operand streamed from the fragment-major FX copies, the
-// activations as the B operand read from LDS where they are kept as two bf16
-// planes (hi, lo) with row strides of 8 mod 16 dwords, the ones column of the
-// next reader written by po_pad, LDS-only barriers between stages, head rows
-// permuted into [mu 4q..4q+3 | zs 4q..4q+3] groups and exchanged with
-// v_permlane16_swap.  It has no prior stages and no density sums: they only
-// feed log w.  The rows of one workgroup belong to one image, so the weighted
-// sum over rows is a reduction over the 16 lanes that hold one feature (and
-// the RT row tiles of a lane) -- no segmented reduction.  Deterministic: no
-// float atomics, fixed reduction order, each output written by one lane.
+// post_kernel runs on the chain machinery shared with mega_fwd_kernel,
+// score_kernel and gen_kernel (iwae_mega_dev.h): bf16x3 products on the bf16
+// 16x16x32 MFMA, the weights as the A operand streamed from the fragment-major
+// FX copies, the activations as the B operand read from LDS where they are
+// kept as two bf16 planes (hi, lo) with row strides of 8 mod 16 dwords, the
+// ones column of the next reader written by mg_pad, LDS-only barriers between
+// stages, the loop over a wave's column tiles (mg_tiles).  Its own, here: the
+// prologue, the weighted sampling and output epilogues and the kernel body.
+// Head rows are permuted into [mu 4q..4q+3 | zs 4q..4q+3] groups and exchanged
+// with v_permlane16_swap.  It has no prior stages and no density sums: they
+// only feed log w.  The rows of one workgroup belong to one image, so the
+// weighted sum over rows is a reduction over the 16 lanes that hold one
+// feature (and the RT row tiles of a lane) -- no segmented reduction.
+// Deterministic: no float atomics, fixed reduction order, each output written
+// by one lane.
 #include "iwae_bound.h"
+#include "iwae_mega_dev.h"
 
 namespace iwae {
 
@@ -139,113 +142,6 @@ hipError_t launch_group_wsum(hipStream_t st, const float* H, int ldH, int n, int
 }
 
 // ----------------------------------------------------------- pass 2, fused
-typedef float po_f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 po_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 po_bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 po_bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned po_u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int PO_WAVES = 8;          // waves per workgroup
-constexpr int PO_KS = 8;             // k steps of 32 per weight fetch (256 k)
-constexpr int PO_PF = 2;             // steps of the next column tile requested during the current one
-
-extern __shared__ __attribute__((aligned(16))) float pos[];
-
-__device__ __forceinline__ po_bf16x8 po_as_bf16x8(po_u32x4 v) { return __builtin_bit_cast(po_bf16x8, v); }
-
-// LDS buffer b: hi plane at bf16 offset off, lo plane at off + R * ld
-struct PoBuf {
-  __bf16* hi; __bf16* lo; int ld;
-};
-template <int RT>
-__device__ __forceinline__ PoBuf po_buf(const PoLaunch& L, int b) {
-  __bf16* base = reinterpret_cast<__bf16*>(pos);
-  PoBuf B;
-  B.ld = L.buf_ld[b];
-  B.hi = base + L.buf_off[b];
-  B.lo = B.hi + 16 * RT * B.ld;
-  return B;
-}
-
-// 1 - 2 / (exp(2x) + 1): absolute error ~1 ulp of 1 (mega_fwd_kernel's tanh)
-__device__ __forceinline__ float po_tanh(float x) {
-  return __builtin_fmaf(-2.f, frcp(fexp(2.f * x) + 1.f), 1.f);
-}
-
-// ones column (K - 1 of the next reader) and zero padding of columns [width, next_k)
-template <int RT>
-__device__ __forceinline__ void po_pad(const PoBuf& B, int width, int next_k) {
-  constexpr int TPR = (PO_WAVES * 64) / (16 * RT);    // threads per row
-  const int row = threadIdx.x / TPR;
-  for (int col = width + threadIdx.x % TPR; col < next_k; col += TPR) {
-    B.hi[row * B.ld + col] = (__bf16)(col == width ? 1.f : 0.f);
-    B.lo[row * B.ld + col] = (__bf16)0.f;
-  }
-}
-
-struct PoFrag {
-  po_bf16x8 h[PO_KS], l[PO_KS];
-};
-
-// Byte offset (hi and lo planes alike) of this lane's fragment of column tile
-// t at k0 in the fragment-major copy (FX: [tile][k step][64 lanes][8], head
-// rows already permuted, padding rows zero), or kOOB
-__device__ __forceinline__ unsigned po_frag_base(const PoStage& S, int t, int k0) {
-  const int lane = threadIdx.x & 63;
-  const int ntile = (S.N + 15) >> 4;
-  return t < ntile ? (unsigned)(((t * (S.ldk >> 5) + (k0 >> 5)) * 64 + lane) * 16) : kOOB;
-}
-// k step u of the fragment: 1 KiB further
-__device__ __forceinline__ void po_fetch_step(__amdgpu_buffer_rsrc_t rh, __amdgpu_buffer_rsrc_t rl, unsigned vb,
-                                              int u, int ns, PoFrag& f) {
-  if (u >= ns) return;
-  f.h[u] = po_as_bf16x8(__builtin_amdgcn_raw_buffer_load_b128(rh, vb, 1024 * u, 0));
-  f.l[u] = po_as_bf16x8(__builtin_amdgcn_raw_buffer_load_b128(rl, vb, 1024 * u, 0));
-}
-
-// acc[rt] += F-tile . IN[rows of rt][k0 .. k0 + 32 ns) (bf16x3).  With pf
-// (uniform) the fragments of the first PO_PF steps are re-requested for the
-// wave's next column tile right after their last MFMA (one register set).
-template <int RT>
-__device__ __forceinline__ void po_mma(const PoBuf& IN, int k0, int ns, PoFrag& f, po_f32x4 (&acc)[RT],
-                                       __amdgpu_buffer_rsrc_t rh, __amdgpu_buffer_rsrc_t rl, bool pf, unsigned pf_vb,
-                                       int pf_ns) {
-  const int lane = threadIdx.x & 63;
-  const int r = lane & 15, g = lane >> 4;
-  // chunks of (k step u, row-tile pair p); the activation fragments of the next
-  // chunk are read from LDS while this chunk's MFMAs run (two register sets)
-  constexpr int RH = RT < 2 ? RT : 2;
-  constexpr int NP = RT / RH;
-  constexpr int NC = PO_KS * NP;
-  po_bf16x8 ah[2][RH], al[2][RH];
-  auto rd = [&](int c, int b) {
-    const int u = c / NP, p = c % NP;
-#pragma unroll
-    for (int i = 0; i < RH; ++i) {
-      const int ao = ((p * RH + i) * 16 + r) * IN.ld + k0 + 32 * u + 8 * g;
-      ah[b][i] = *reinterpret_cast<const po_bf16x8*>(IN.hi + ao);
-      al[b][i] = *reinterpret_cast<const po_bf16x8*>(IN.lo + ao);
-    }
-  };
-  rd(0, 0);
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const int u = c / NP, p = c % NP, b = c & 1;
-    if (u >= ns) break;
-    if (c + 1 < NC && (c + 1) / NP < ns) rd(c + 1, b ^ 1);
-#pragma unroll
-    for (int i = 0; i < RH; ++i)
-      acc[p * RH + i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.l[u], ah[b][i], acc[p * RH + i], 0, 0, 0);
-#pragma unroll
-    for (int i = 0; i < RH; ++i)
-      acc[p * RH + i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.h[u], al[b][i], acc[p * RH + i], 0, 0, 0);
-#pragma unroll
-    for (int i = 0; i < RH; ++i)
-      acc[p * RH + i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.h[u], ah[b][i], acc[p * RH + i], 0, 0, 0);
-    if (p == NP - 1 && u < PO_PF && pf) po_fetch_step(rh, rl, pf_vb, u, pf_ns, f);
-  }
-}
-
 // What a workgroup's lanes carry through the stages: the image, the chunk row
 // of the workgroup's first sample, its live rows, the row (of the workgroup)
 // that holds the image's resampled sample (or -1), the weights of the lane's
@@ -266,38 +162,6 @@ __device__ __forceinline__ float po_sum16(float v) {
   return v;
 }
 
-// TANH epilogue: features f0..f0+3 of row rt*16 + r
-template <int RT>
-__device__ __forceinline__ void po_store_tanh(const PoBuf& OUT, const PoStage& S, int t, const po_f32x4 (&acc)[RT]) {
-  const int lane = threadIdx.x & 63;
-  const int r = lane & 15, g = lane >> 4;
-  const int f0 = t * 16 + 4 * g;
-  if (f0 >= S.N) return;
-#pragma unroll
-  for (int rt = 0; rt < RT; ++rt) {
-    float v[4];
-    po_bf16x4 vh, vl;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      v[i] = po_tanh(acc[rt][i]);
-      vh[i] = (__bf16)v[i];
-      vl[i] = (__bf16)(v[i] - (float)vh[i]);
-    }
-    const int o = (rt * 16 + r) * OUT.ld + f0;
-    if (f0 + 3 < S.N) {
-      *reinterpret_cast<po_bf16x4*>(OUT.hi + o) = vh;
-      *reinterpret_cast<po_bf16x4*>(OUT.lo + o) = vl;
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (f0 + i < S.N) {
-          OUT.hi[o + i] = vh[i];
-          OUT.lo[o + i] = vl[i];
-        }
-    }
-  }
-}
-
 // Sampling epilogue (F:66-F:70).  Lane groups g hold, for quad q = 2t + (g >> 1),
 // the mu quad (g even) or the zs quad (g odd); after swap(acc.x, acc.z) and
 // swap(acc.y, acc.w) every lane holds (mu, zs) of its own two latent columns
@@ -306,13 +170,13 @@ __device__ __forceinline__ void po_store_tanh(const PoBuf& OUT, const PoStage& S
 // row's h to the caller's buffer.
 template <int RT>
 __device__ __forceinline__ void po_head(const PoLaunch& L, const PoStage& S, int t, uint64_t base,
-                                        const po_f32x4 (&acc)[RT], const PoRows<RT>& R) {
+                                        const mg_f32x4 (&acc)[RT], const PoRows<RT>& R) {
   const int lane = threadIdx.x & 63;
   const int r = lane & 15, g = lane >> 4;
   const int q = 2 * t + (g >> 1);
   const int j0 = 4 * q + 2 * (g & 1);
   const int d = S.d;
-  const PoBuf H = po_buf<RT>(L, max(S.out_buf, 0));
+  const MgBuf H = mg_buf<RT>(L, max(S.out_buf, 0));
   float* sel = L.h_sir[S.layer];
   float sum[2] = {0.f, 0.f};
 #pragma unroll
@@ -345,14 +209,14 @@ __device__ __forceinline__ void po_head(const PoLaunch& L, const PoStage& S, int
       if (sel && row == R.sir_row && j < d) sel[(size_t)R.img * d + j] = h;
     }
     if (S.out_buf >= 0) {                  // (uniform) a later stage reads this latent
-      po_bf16x2 vh, vl;
+      mg_bf16x2 vh, vl;
 #pragma unroll
       for (int c = 0; c < 2; ++c) {
         vh[c] = (__bf16)hv[c];
         vl[c] = (__bf16)(hv[c] - (float)vh[c]);
       }
-      *reinterpret_cast<po_bf16x2*>(H.hi + row * H.ld + j0) = vh;
-      *reinterpret_cast<po_bf16x2*>(H.lo + row * H.ld + j0) = vl;
+      *reinterpret_cast<mg_bf16x2*>(H.hi + row * H.ld + j0) = vh;
+      *reinterpret_cast<mg_bf16x2*>(H.lo + row * H.ld + j0) = vl;
     }
     __builtin_amdgcn_sched_barrier(0);     // one row tile at a time (register pressure)
   }
@@ -369,7 +233,7 @@ __device__ __forceinline__ void po_head(const PoLaunch& L, const PoStage& S, int
 // features f0..f0+3 of the lane's rows, times their weights, summed over the
 // workgroup's rows: one value per feature into the partial vector.
 template <int RT>
-__device__ __forceinline__ void po_out(const PoStage& S, int t, const po_f32x4 (&acc)[RT], const PoRows<RT>& R) {
+__device__ __forceinline__ void po_out(const PoStage& S, int t, const mg_f32x4 (&acc)[RT], const PoRows<RT>& R) {
   const int lane = threadIdx.x & 63;
   const int r = lane & 15, g = lane >> 4;
   const int f0 = t * 16 + 4 * g;
@@ -388,75 +252,21 @@ __device__ __forceinline__ void po_out(const PoStage& S, int t, const po_f32x4 (
   }
 }
 
-// Barrier between stages: the stages exchange data through LDS only, so the
-// release / acquire cover LDS alone and requested weight fragments stay in
-// flight across it.
-__device__ __forceinline__ void po_lds_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
+// The stage kind's epilogue, for the shared tile loop (mg_tiles)
 template <int RT, int ACT>
-__device__ __forceinline__ void po_epilogue(const PoLaunch& L, const PoStage& S, const PoBuf& OUT, int t,
-                                            uint64_t base, const po_f32x4 (&acc)[RT], const PoRows<RT>& R) {
-  if (ACT == PO_TANH) po_store_tanh<RT>(OUT, S, t, acc);
-  else if (ACT == PO_OUT) po_out<RT>(S, t, acc, R);
-  else po_head<RT>(L, S, t, base, acc, R);
-}
-
-// One Dense stage.  Wave w owns the column tiles w, w + 8, ...; when the whole
-// K fits one fetch (ldk <= 256) the first PO_PF steps of the wave's next tile
-// are requested during the current tile's MFMAs (po_mma).
-template <int RT, int ACT>
-__device__ __forceinline__ void po_dense(const PoLaunch& L, const PoStage& S, uint64_t base, const PoRows<RT>& R) {
-  const int wave = threadIdx.x >> 6;
-  const int ntile = (S.N + 15) >> 4;
-  const PoBuf IN = po_buf<RT>(L, S.in_buf);
-  const PoBuf OUT = po_buf<RT>(L, ACT == PO_TANH ? S.out_buf : S.in_buf);
-  const __amdgpu_buffer_rsrc_t rh = buf_rsrc(S.Whi, S.W_bytes), rl = buf_rsrc(S.Wlo, S.W_bytes);
-  if (S.ldk <= 32 * PO_KS) {
-    PoFrag f;
-    const int ns = S.ldk >> 5;
-    if (wave < ntile) {
-      const unsigned vb = po_frag_base(S, wave, 0);
-#pragma unroll
-      for (int u = 0; u < PO_PF; ++u) po_fetch_step(rh, rl, vb, u, ns, f);
-    }
-    for (int t = wave; t < ntile; t += PO_WAVES) {
-      const int tn = t + PO_WAVES;
-      const unsigned vb = po_frag_base(S, t, 0);
-#pragma unroll
-      for (int u = PO_PF; u < PO_KS; ++u) po_fetch_step(rh, rl, vb, u, ns, f);
-      po_f32x4 acc[RT];
-#pragma unroll
-      for (int rt = 0; rt < RT; ++rt) acc[rt] = (po_f32x4){0.f, 0.f, 0.f, 0.f};
-      po_mma<RT>(IN, 0, min(PO_KS, ns), f, acc, rh, rl, tn < ntile, po_frag_base(S, tn, 0), ns);
-      po_epilogue<RT, ACT>(L, S, OUT, t, base, acc, R);
-    }
-  } else {
-    // wide K: 256-deep fetches, no prefetch across tiles
-    for (int t = wave; t < ntile; t += PO_WAVES) {
-      po_f32x4 acc[RT];
-#pragma unroll
-      for (int rt = 0; rt < RT; ++rt) acc[rt] = (po_f32x4){0.f, 0.f, 0.f, 0.f};
-      for (int k0 = 0; k0 < S.ldk; k0 += 32 * PO_KS) {
-        PoFrag f;
-        const unsigned vb = po_frag_base(S, t, k0);
-        const int ns = (S.ldk - k0) >> 5;
-#pragma unroll
-        for (int u = 0; u < PO_KS; ++u) po_fetch_step(rh, rl, vb, u, ns, f);
-        po_mma<RT>(IN, k0, min(PO_KS, ns), f, acc, rh, rl, false, kOOB, 0);
-      }
-      po_epilogue<RT, ACT>(L, S, OUT, t, base, acc, R);
-    }
+struct PoEpi {
+  static __device__ __forceinline__ void run(const PoLaunch& L, const PoStage& S, const MgBuf& OUT, int t,
+                                             const mg_f32x4 (&acc)[RT], uint64_t base, const PoRows<RT>& R) {
+    if (ACT == PO_TANH) mg_store_tanh<RT>(OUT, S, t, acc);
+    else if (ACT == PO_OUT) po_out<RT>(S, t, acc, R);
+    else po_head<RT>(L, S, t, base, acc, R);
   }
-}
+};
 
 template <int RT>
-__global__ __launch_bounds__(PO_WAVES * 64) void post_kernel(PoLaunch L) {
+__global__ __launch_bounds__(MG_WAVES * 64) void post_kernel(PoLaunch L) {
   constexpr int R = 16 * RT;
-  constexpr int TPR = (PO_WAVES * 64) / R;       // threads per row in the prologue
+  constexpr int TPR = (MG_WAVES * 64) / R;       // threads per row in the prologue
   const int t = threadIdx.x;
   const uint64_t base = *L.rng_base;
   PoRows<RT> Rw;
@@ -466,16 +276,16 @@ __global__ __launch_bounds__(PO_WAVES * 64) void post_kernel(PoLaunch L) {
   Rw.nrows = min(R, L.kS - Rw.s0);               // >= 1: tiles = ceil(kS / R)
   Rw.sir_row = L.sir ? L.sir[Rw.img] - Rw.s0 : -1;
   Rw.part = L.part + (size_t)blockIdx.x * L.ld_part;
-  float* wl = pos + L.w_off;
+  float* wl = mgs + L.w_off;
   if (t < R) wl[t] = t < Rw.nrows ? L.wt[Rw.row0 + t] : 0.f;
   // ---- prologue: h_1 = eps * s0 + mu0 of the image (F:58-F:60): split into
   // its LDS buffer with the ones column, and as f32 into the staging buffer
   // (a TANH buffer no stage has written yet) for the weighted sum over rows
   const int d0 = L.d0;
-  float* stage = reinterpret_cast<float*>(reinterpret_cast<__bf16*>(pos) + L.buf_off[L.stage_buf]);
+  float* stage = reinterpret_cast<float*>(reinterpret_cast<__bf16*>(mgs) + L.buf_off[L.stage_buf]);
   const int ld_stage = L.buf_ld[L.stage_buf];    // two bf16 planes of ld = ld floats per row
   {
-    const PoBuf H = po_buf<RT>(L, L.h0_buf);
+    const MgBuf H = mg_buf<RT>(L, L.h0_buf);
     const int rr = t / TPR, sub = t - rr * TPR;
     const int rc = min(rr, Rw.nrows - 1);
     const float* Pp = L.P0 + (size_t)Rw.img * L.ldP0;
@@ -491,7 +301,7 @@ __global__ __launch_bounds__(PO_WAVES * 64) void post_kernel(PoLaunch L) {
           e4 = philox_normal4(L.seed, base, (unsigned)(Rw.row0 + rc), 0u, (unsigned)gq);
         }
       }
-      po_bf16x4 vh, vl;
+      mg_bf16x4 vh, vl;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int j = 4 * gq + q;
@@ -507,17 +317,17 @@ __global__ __launch_bounds__(PO_WAVES * 64) void post_kernel(PoLaunch L) {
         vh[q] = (__bf16)hv;
         vl[q] = (__bf16)(hv - (float)vh[q]);
       }
-      *reinterpret_cast<po_bf16x4*>(H.hi + rr * H.ld + 4 * gq) = vh;
-      *reinterpret_cast<po_bf16x4*>(H.lo + rr * H.ld + 4 * gq) = vl;
+      *reinterpret_cast<mg_bf16x4*>(H.hi + rr * H.ld + 4 * gq) = vh;
+      *reinterpret_cast<mg_bf16x4*>(H.lo + rr * H.ld + 4 * gq) = vl;
     }
   }
-  po_lds_barrier();
+  mg_lds_barrier();
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt) Rw.w[rt] = wl[rt * 16 + (t & 15)];
   // sum_s w~_s h_1: one column per thread, the rows in sample order (the first
   // stage does not write the staging buffer, and a barrier follows it)
   if (L.want_mean)
-    for (int j = t; j < d0; j += PO_WAVES * 64) {
+    for (int j = t; j < d0; j += MG_WAVES * 64) {
       float acc = 0.f;
       for (int rr = 0; rr < Rw.nrows; ++rr) acc = __builtin_fmaf(wl[rr], stage[rr * ld_stage + j], acc);
       Rw.part[j] = acc;
@@ -525,20 +335,20 @@ __global__ __launch_bounds__(PO_WAVES * 64) void post_kernel(PoLaunch L) {
 
   for (int s = 0; s < L.nst; ++s) {
     const PoStage& S = L.st[s];
-    if (S.act == PO_TANH) po_pad<RT>(po_buf<RT>(L, S.out_buf), S.N, S.next_k);
-    else if (S.act == PO_SAMPLE && S.out_buf >= 0) po_pad<RT>(po_buf<RT>(L, S.out_buf), S.d, S.next_k);
+    if (S.act == PO_TANH) mg_pad<RT, MG_WAVES>(mg_buf<RT>(L, S.out_buf), S.N, S.next_k);
+    else if (S.act == PO_SAMPLE && S.out_buf >= 0) mg_pad<RT, MG_WAVES>(mg_buf<RT>(L, S.out_buf), S.d, S.next_k);
     switch (S.act) {     // one instantiation per stage kind: one epilogue per tile loop
-      case PO_TANH: po_dense<RT, PO_TANH>(L, S, base, Rw); break;
-      case PO_SAMPLE: po_dense<RT, PO_SAMPLE>(L, S, base, Rw); break;
-      default: po_dense<RT, PO_OUT>(L, S, base, Rw); break;
+      case PO_TANH: mg_tiles<RT, MG_WAVES, PoEpi<RT, PO_TANH>>(L, S, S.out_buf, base, Rw); break;
+      case PO_SAMPLE: mg_tiles<RT, MG_WAVES, PoEpi<RT, PO_SAMPLE>>(L, S, S.in_buf, base, Rw); break;
+      default: mg_tiles<RT, MG_WAVES, PoEpi<RT, PO_OUT>>(L, S, S.in_buf, base, Rw); break;
     }
-    po_lds_barrier();
+    mg_lds_barrier();
   }
 }
 
 hipError_t launch_post(hipStream_t st, const PoLaunch& L, int rt, size_t lds_bytes) {
   if (L.Bimg <= 0 || L.kS <= 0) return hipSuccess;
-  const dim3 grid((unsigned)(L.Bimg * L.tiles)), block(PO_WAVES * 64);
+  const dim3 grid((unsigned)(L.Bimg * L.tiles)), block(MG_WAVES * 64);
   switch (rt) {
     case 1: hipLaunchKernelGGL(post_kernel<1>, grid, block, lds_bytes, st, L); break;
     case 2: hipLaunchKernelGGL(post_kernel<2>, grid, block, lds_bytes, st, L); break;
