@@ -610,6 +610,90 @@ int iwae_score_grad(iwae_handle* h, const float* x, int N, int k, int chunk,
                     const float coef[3],
                     float* const* grad, int n_grad,
                     float* log_q, float* log_ph, float* log_px);
+/* Annealed importance sampling on the latents (Neal 2001; Wu et al. 2017): a
+ * whole annealing schedule of Metropolis-adjusted HMC transitions, enqueued on
+ * the handle's stream with no host synchronization (only a workspace that has
+ * to grow waits).  Every chain is one (image b, sample s) row; all layers move
+ * jointly, the mass matrix is the identity.  lat (required, L device buffers
+ * [k][N][d_i], sample-major) is the chains' state, updated IN PLACE; x
+ * (required), N, k and chunk are iwae_score's, with its limits, and N k <=
+ * 2^30 chains.  betas is a HOST array of n_temps + 1 finite values in [0, 1],
+ * in any order: ascending from 0 to 1 is AIS, descending from 1 the reverse
+ * chain (bidirectional Monte Carlo), constant 1 plain HMC on p(h|x).  The
+ * transition at beta moves under c_q log q(h|x) + c_ph log p(h) + c_px log
+ * p(x|h_1), iwae_score_grad's coefficient forms: init 0 (from the prior) (0,
+ * 1, beta) with Delta = log p(x|h_1); init 1 (from q) (1 - beta, beta, beta)
+ * with Delta = log p(h) + log p(x|h_1) - log q(h|x).  Transition t = 1 ..
+ * n_temps, beta = betas[t], per chain with its own step eps:
+ *   1. one iwae_score_grad pass at the state: g, the values, U_old = -(c_q
+ *      log q + c_ph log p(h) + c_px log p(x|h)) (a term whose coefficient is 0
+ *      is left out) and Delta;
+ *   2. log_w += (betas[t] - betas[t-1]) Delta;
+ *   3. momenta r ~ N(0, I); H_old = U_old + |r|^2 / 2; r += eps/2 g; the
+ *      proposal q = state + eps r;
+ *   4. n_leapfrog passes at q; after each but the last r += eps g, q += eps r
+ *      (two half kicks merged); after the last r += eps/2 g, H_new = U(q) +
+ *      |r|^2 / 2; accept iff log u < H_old - H_new (a NaN rejects);
+ *   5. on accept state <- q and the chain's accept count goes up by one; a
+ *      rejected chain keeps its bits;
+ *   6. eps <- clamp(eps (accept ? adapt_inc : adapt_dec), step_min, step_max)
+ *      in float32 (adapt_inc = adapt_dec = 1: a fixed step).
+ * That is n_leapfrog + 1 gradient passes per transition, each on the path
+ * iwae_score_grad would take (fused or layer-wise, never an error), and
+ * between them one launch of iwae_ais.hip: ais_begin_kernel (steps 2, 3),
+ * ais_step_kernel (the merged kick and drift, float4 where d_i is a multiple
+ * of 4), ais_end_kernel (the last kick, the decision, steps 5 and 6); begin
+ * and end give a chain 16 lanes while every d_i <= 64 and a wave otherwise,
+ * and sum |r|^2 per lane in layer, then column order and over the group by a
+ * fixed butterfly.  After the last transition ais_finish_kernel forms, per
+ * image in a fixed order, logpx = logsumexp_s log_w - log k and ess = (sum
+ * e)^2 / sum e^2 with e = exp(log_w - max).  Per-chain arrays are image-major
+ * [N][k]: step_io (NULL: every chain starts at cfg->step; else read and
+ * written), log_w, accepts (accepted transitions, as float); logpx, ess [N];
+ * each of the four outputs is optional.  accumulate = 0: log_w and accepts
+ * start at 0; 1: they are added to the caller's values (with log_w NULL the
+ * weights behind logpx / ess start at 0 either way), and a call on the
+ * lat, step_io, log_w and accepts a previous call left, over the rest of the
+ * schedule (its first beta the previous call's last), continues that chain:
+ * two such calls give bit for bit what one call over the whole schedule
+ * gives, with injected and with device noise.  Noise: mom is NULL / 0, or
+ * n_temps * L device buffers [k][N][d_i], mom[(t - 1) L + i] transition t's
+ * momenta of layer i; u is NULL, or [n_temps][N][k] uniforms in (0, 1).
+ * Absent, momenta of layer i are philox_normal4 under layer id 2
+ * IWAE_MAX_LAYERS + 4 + i (column quad j / 4, value j % 4) and the accept
+ * uniform is value 0 of quad 0 of philox_uniform4 under layer id 2
+ * IWAE_MAX_LAYERS + 12, both at row b k + s over the whole call and base =
+ * the handle's noise position + t - 1 on the current key.  The noise position
+ * advances once per transition, by n_temps per call, whether or not noise was
+ * injected.  There are no float atomics, every element is written by one
+ * thread, the call is deterministic and its result does not depend on chunk,
+ * bit for bit.  Rows are independent: a chain whose latents are not finite
+ * never accepts, stays put, and its neighbours are unaffected.  Weights, Adam
+ * state, the train arena, captured graphs and engine plans are untouched (the
+ * chains' momenta, proposals, gradients and values are a workspace of the
+ * call's own, which only grows); the sticky error (iwae_status) is returned
+ * before any work is enqueued.  IWAE_EINVAL, with nothing launched: cfg,
+ * betas, lat or x NULL, a NULL lat[i], n_lat != L, n_mom not 0 or n_temps * L
+ * or a NULL buffer among them, init not 0 or 1, n_temps < 1 or above 2^24,
+ * n_leapfrog < 1, a beta that is not finite or outside [0, 1], step not
+ * finite or <= 0, adapt_inc or adapt_dec not finite or <= 0, step_min >
+ * step_max, N <= 0 or k <= 0, k, the chunk or N k above the limits. */
+typedef struct iwae_ais_config {
+  int init;         /* 0: from the prior, 1: from q(h|x) */
+  int n_temps;      /* T >= 1; betas holds T + 1 host floats; T <= 2^24 */
+  int n_leapfrog;   /* >= 1 */
+  int accumulate;   /* 0: log_w and accepts start at 0; 1: added to the caller's values */
+  float step;       /* every chain's initial step where step_io is NULL; > 0 */
+  float adapt_inc, adapt_dec, step_min, step_max;   /* 1, 1: fixed step */
+} iwae_ais_config;
+int iwae_ais(iwae_handle* h, const float* x, int N, int k, int chunk,
+             float* const* lat, int n_lat,
+             const iwae_ais_config* cfg, const float* betas,
+             const float* const* mom, int n_mom,
+             const float* u,
+             float* step_io,
+             float* log_w, float* accepts,
+             float* logpx, float* ess);
 /* Encoder.call (F:56-F:75): k samples of q(h|x) per image, with device noise
  * (eps NULL, n_eps 0) or injected eps[i] [k][N][d_i].  lat_out[i] [k][N][d_i],
  * sample-major (n_lat 0 or L); log_q [N][k]; loc_top / scale_top: the
@@ -678,8 +762,9 @@ double iwae_workspace_bytes(const iwae_handle* h);
  * iwae_binarize (one per call with n > 0); 23 fused iwae_score launches
  * (score_kernel, one per chunk), 24 its layer-wise passes (one per chunk); 25
  * fused score-gradient launches of iwae_score_grad (sg_kernel, one per chunk),
- * 26 its layer-wise score-gradient passes (one per chunk); -1 for an unknown
- * id. */
+ * 26 its layer-wise score-gradient passes (one per chunk); 27 AIS transitions
+ * run by iwae_ais, 28 its begin / step / end launches (n_temps (n_leapfrog +
+ * 1) per call; the finish launch is not counted); -1 for an unknown id. */
 long long iwae_debug_count(const iwae_handle* h, int what);
 /* Live kernel timing: bracket every launch of one kernel class with HIP events
  * on the handle's stream -- a GEMM class (kind: 0 forward, 1 backward-data,

@@ -48,6 +48,13 @@ class IwaeLossConfig(ctypes.Structure):
     ]
 
 
+class IwaeAisConfig(ctypes.Structure):
+    _fields_ = [
+        ("init", c_int), ("n_temps", c_int), ("n_leapfrog", c_int), ("accumulate", c_int),
+        ("step", c_float), ("adapt_inc", c_float), ("adapt_dec", c_float), ("step_min", c_float), ("step_max", c_float),
+    ]
+
+
 FP = POINTER(c_float)
 FPP = POINTER(FP)
 H = c_void_p
@@ -103,6 +110,8 @@ SIGNATURES = {
                             FPP, c_int, FP, FP, FP]),
     "iwae_score": (c_int, [H, FP, c_int, c_int, c_int, FPP, c_int, FP, FP, FP, FP, c_int]),
     "iwae_score_grad": (c_int, [H, FP, c_int, c_int, c_int, FPP, c_int, FP, FPP, c_int, FP, FP, FP]),
+    "iwae_ais": (c_int, [H, FP, c_int, c_int, c_int, FPP, c_int, POINTER(IwaeAisConfig), FP, FPP, c_int, FP, FP, FP, FP,
+                         FP, FP]),
     "iwae_encode": (c_int, [H, FP, c_int, c_int, c_int, FPP, c_int, FPP, c_int, FP, FP, FP]),
     "iwae_train_step_masked": (c_int, [H, POINTER(IwaeLossConfig), FP, FP, c_int, FPP, c_int, FP]),
     "iwae_forward_backward_masked": (c_int, [H, POINTER(IwaeLossConfig), FP, FP, c_int, FPP, c_int, FP]),

@@ -1076,4 +1076,37 @@ hipError_t launch_impute_draw(hipStream_t st, const float* x, const float* mask,
 hipError_t launch_binarize(hipStream_t st, const float* x, long long n_src, const long long* perm, const float* u,
                            int n, int xdim, float* out, int ldo, uint64_t seed, const uint64_t* rng_base, int layer);
 
+// ------------------------- annealed importance sampling (iwae_ais.hip) ----
+// One transition's launches between the gradient passes.  Chain c = b k + s
+// (image b, sample s); cur / r / q / g / mom: per layer [k][N][d_i], sample-major;
+// every per-chain scalar [N][k].  lq / lph / lpx and g are what the last
+// iwae_score_grad pass left for the state it was given; (cq, cph, cpx) its
+// coefficients (a zero coefficient's term is left out of the energy).
+struct AisArgs {
+  int L, N, k, group;                   // group: lanes per chain, 16 or 64
+  long long chains;                     // N k
+  int d[8], vec[8];                     // vec: ais_step_kernel takes the layer in float4 (d % 4 == 0, aligned)
+  float* cur[8]; float* r[8]; float* q[8]; const float* g[8];
+  const float* mom[8];                  // begin: injected momenta, or null (Philox normals, layer id mom_layer + i)
+  const float *lq, *lph, *lpx;
+  float cq, cph, cpx;
+  int init;                             // Delta: 0 log p(x|h), 1 log p(h) + log p(x|h) - log q(h|x)
+  float dbeta;                          // begin: log_w += dbeta Delta
+  int zero;                             // the call's first transition, not accumulating: log_w / accepts start at 0
+  float step0;                          // > 0: every chain's step in this transition (step[] not yet written)
+  float* step; float* H_old;
+  float* log_w; float* accepts;         // either may be null
+  const float* u;                       // end: this transition's uniforms [N][k], or null (Philox, layer u_layer)
+  uint64_t seed; const uint64_t* rng_base; unsigned t_off;   // noise base = *rng_base + t_off
+  int mom_layer, u_layer;
+  float inc, dec, smin, smax;           // end: step = clamp(step (accept ? inc : dec), smin, smax)
+};
+hipError_t launch_ais_begin(hipStream_t st, const AisArgs& a);
+hipError_t launch_ais_step(hipStream_t st, const AisArgs& a);
+hipError_t launch_ais_end(hipStream_t st, const AisArgs& a);
+// logpx[b] = logsumexp_s log_w[b][s] - log k, ess[b] = (sum e)^2 / sum e^2 (either may be null; nothing is
+// reduced when log_w is); the noise position moves on by n_adv when rng_base is given
+hipError_t launch_ais_finish(hipStream_t st, const float* log_w, int N, int k, float* logpx, float* ess,
+                             uint64_t* rng_base, unsigned n_adv);
+
 }  // namespace iwae

@@ -214,6 +214,7 @@ struct Counters {
   long long binarize = 0;                // 22: binarize_kernel launches (iwae_binarize)
   long long score = 0, score_lw = 0;     // 23, 24: iwae_score chunks: score_kernel launches / layer-wise passes
   long long sgrad = 0, sgrad_lw = 0;     // 25, 26: iwae_score_grad chunks: sg_kernel launches / layer-wise passes
+  long long ais = 0, ais_launch = 0;     // 27, 28: iwae_ais transitions / their begin, step and end launches
 };
 
 // row-chain train engine plan (device resident, per shape; iwae_train.hip)
@@ -303,6 +304,8 @@ struct iwae_handle {
   float* sg_ws = nullptr;            // iwae_score_grad's backward rows (layer-wise path): its own allocation, zeroed
   size_t sg_ws_floats = 0;           // when it grows, laid out for sg_rows rows (padding columns stay zero)
   int sg_rows = 0;
+  float* ais_ws = nullptr;           // iwae_ais's chains (momenta, proposals, gradients per layer; H_old, the value
+  size_t ais_ws_floats = 0;          // terms, and the weights / steps the caller did not give): its own allocation
   float* loss_slots = nullptr;       // multi-step graphs: step j's loss (kGraphSteps floats), then
                                      // [kGraphSteps, 2 kGraphSteps): where a graph's copy node writes
                                      // when the call wants no losses
@@ -3303,6 +3306,7 @@ void iwae_destroy(iwae_handle* h) {
   if (h->loss_slots) (void)hipFree(h->loss_slots);
   if (h->post_ws) (void)hipFree(h->post_ws);
   if (h->sg_ws) (void)hipFree(h->sg_ws);
+  if (h->ais_ws) (void)hipFree(h->ais_ws);
   if (h->nr_units) (void)hipFree(h->nr_units);
   if (h->nrb_units) (void)hipFree(h->nrb_units);
   if (h->nre_units) (void)hipFree(h->nre_units);
@@ -5294,6 +5298,118 @@ int iwae_score_grad(iwae_handle* h, const float* x, int N, int k, int chunk, con
   return IWAE_OK;
 }
 
+// Annealed importance sampling (include/iwae.h): per transition one gradient
+// pass at the state (iwae_score_grad, fused or layer-wise as it decides), the
+// begin launch, then n_leapfrog passes at the proposal, each followed by the
+// step launch or, the last, by the end launch (iwae_ais.hip); one finish launch
+// per call.  Everything is enqueued on h->stream: coef is a host array and the
+// chains' buffers (ais_ws) only grow, so the host waits only where a workspace
+// grows.
+int iwae_ais(iwae_handle* h, const float* x, int N, int k, int chunk, float* const* lat, int n_lat,
+             const iwae_ais_config* cfg, const float* betas, const float* const* mom, int n_mom, const float* u,
+             float* step_io, float* log_w, float* accepts, float* logpx, float* ess) {
+  if (!h) return IWAE_EINVAL;
+  CHK(kernel_status(h));
+  const int L = h->L;
+  if (!cfg) return fail(h, IWAE_EINVAL, "cfg is NULL");
+  if (!betas) return fail(h, IWAE_EINVAL, "betas is NULL");
+  if (!x) return fail(h, IWAE_EINVAL, "x is NULL");
+  if (n_lat != L || !lat)
+    return fail(h, IWAE_EINVAL, "expected " + std::to_string(L) + " latent buffers (one per stochastic layer), got " +
+                                   std::to_string(n_lat));
+  for (int i = 0; i < L; ++i)
+    if (!lat[i]) return fail(h, IWAE_EINVAL, "NULL latent buffer");
+  if (cfg->init != 0 && cfg->init != 1) return fail(h, IWAE_EINVAL, "init must be 0 (the prior) or 1 (q)");
+  const int T = cfg->n_temps, nl = cfg->n_leapfrog;
+  if (T < 1 || T > (1 << 24)) return fail(h, IWAE_EINVAL, "n_temps must be in [1, 2^24]");
+  if (nl < 1) return fail(h, IWAE_EINVAL, "n_leapfrog must be at least 1");
+  for (int t = 0; t <= T; ++t)
+    if (!std::isfinite(betas[t]) || betas[t] < 0.f || betas[t] > 1.f)
+      return fail(h, IWAE_EINVAL, "betas must be finite and in [0, 1]");
+  if (!std::isfinite(cfg->step) || cfg->step <= 0.f)
+    return fail(h, IWAE_EINVAL, "step must be positive and finite");
+  if (!std::isfinite(cfg->adapt_inc) || !std::isfinite(cfg->adapt_dec) || cfg->adapt_inc <= 0.f || cfg->adapt_dec <= 0.f)
+    return fail(h, IWAE_EINVAL, "adapt_inc and adapt_dec must be positive and finite");
+  if (!(cfg->step_min <= cfg->step_max)) return fail(h, IWAE_EINVAL, "step_min must not exceed step_max");
+  if (n_mom != 0 && ((long long)n_mom != (long long)T * L || !mom))
+    return fail(h, IWAE_EINVAL, "expected 0 or n_temps * " + std::to_string(L) + " momentum buffers, got " +
+                                   std::to_string(n_mom));
+  for (int i = 0; i < n_mom; ++i)
+    if (!mom[i]) return fail(h, IWAE_EINVAL, "NULL momentum buffer");
+  if (!score_chunk(h, N, k, chunk)) return IWAE_EINVAL;
+  const long long chains = (long long)N * k;
+  if (chains > (1LL << 30)) return fail(h, IWAE_EINVAL, "N * k above 2^30 chains");
+  // ---- the chains' buffers: per layer r, q, g [k][N][d_i]; per chain H_old, log q, log p(h), log p(x|h), and
+  // the weights / steps where the caller gave none.  Each starts on a 64-float boundary.
+  size_t off = 0;
+  auto take = [&](size_t n) { const size_t o = off; off += (n + 63) & ~size_t(63); return o; };
+  size_t o_r[IWAE_MAX_LAYERS], o_q[IWAE_MAX_LAYERS], o_g[IWAE_MAX_LAYERS];
+  int dmax = 0;
+  for (int i = 0; i < L; ++i) {
+    const size_t n = (size_t)chains * h->enc[i].d;
+    o_r[i] = take(n); o_q[i] = take(n); o_g[i] = take(n);
+    dmax = std::max(dmax, h->enc[i].d);
+  }
+  const size_t o_H = take(chains), o_lq = take(chains), o_lph = take(chains), o_lpx = take(chains);
+  const size_t o_w = take(chains), o_step = take(chains);
+  if (off > h->ais_ws_floats) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (h->ais_ws) (void)hipFree(h->ais_ws);
+    h->ais_ws = nullptr; h->ais_ws_floats = 0;
+    HIPCHK(hipMalloc(&h->ais_ws, off * sizeof(float)));
+    h->ais_ws_floats = off;
+  }
+  float* ws = h->ais_ws;
+  AisArgs a{};
+  a.L = L; a.N = N; a.k = k; a.chains = chains;
+  a.group = dmax <= 64 ? 16 : 64;
+  float* gbuf[IWAE_MAX_LAYERS];
+  for (int i = 0; i < L; ++i) {
+    a.d[i] = h->enc[i].d;
+    a.vec[i] = (a.d[i] & 3) == 0;
+    a.cur[i] = lat[i]; a.r[i] = ws + o_r[i]; a.q[i] = ws + o_q[i];
+    a.g[i] = gbuf[i] = ws + o_g[i];
+  }
+  const int init = cfg->init;
+  a.init = init;
+  float* lq = init ? ws + o_lq : nullptr;          // (from the prior, log q enters neither the energy nor Delta)
+  float *lph = ws + o_lph, *lpx = ws + o_lpx;
+  a.lq = lq; a.lph = lph; a.lpx = lpx;
+  a.H_old = ws + o_H;
+  a.step = step_io ? step_io : ws + o_step;
+  // logpx / ess are formed from the weights: in the workspace where the caller has no use for them
+  a.log_w = log_w ? log_w : (logpx || ess) ? ws + o_w : nullptr;
+  a.accepts = accepts;
+  a.seed = h->seed; a.rng_base = &h->ds->rng[0];
+  a.mom_layer = 2 * IWAE_MAX_LAYERS + 4; a.u_layer = 2 * IWAE_MAX_LAYERS + 12;
+  a.inc = cfg->adapt_inc; a.dec = cfg->adapt_dec; a.smin = cfg->step_min; a.smax = cfg->step_max;
+  if (cfg->accumulate && !log_w && a.log_w)        // no weights given, nothing to continue from: the workspace's start at 0
+    HIPCHK(hipMemsetAsync(a.log_w, 0, (size_t)chains * sizeof(float), h->stream));
+  for (int t = 1; t <= T; ++t) {
+    const float beta = betas[t];
+    const float coef[3] = {init ? 1.f - beta : 0.f, init ? beta : 1.f, beta};
+    a.cq = coef[0]; a.cph = coef[1]; a.cpx = coef[2];
+    a.dbeta = betas[t] - betas[t - 1];
+    a.zero = t == 1 && !cfg->accumulate;
+    a.step0 = t == 1 && !step_io ? cfg->step : 0.f;
+    a.t_off = (unsigned)(t - 1);
+    for (int i = 0; i < L; ++i) a.mom[i] = n_mom ? mom[(size_t)(t - 1) * L + i] : nullptr;
+    a.u = u ? u + (size_t)(t - 1) * chains : nullptr;
+    CHK(iwae_score_grad(h, x, N, k, chunk, lat, L, coef, gbuf, L, lq, lph, lpx));
+    HIPCHK(launch_ais_begin(h->stream, a));
+    ++h->count.ais_launch;
+    for (int l = 1; l <= nl; ++l) {
+      CHK(iwae_score_grad(h, x, N, k, chunk, a.q, L, coef, gbuf, L, lq, lph, lpx));
+      if (l < nl) HIPCHK(launch_ais_step(h->stream, a));
+      else HIPCHK(launch_ais_end(h->stream, a));
+      ++h->count.ais_launch;
+    }
+    ++h->count.ais;
+  }
+  HIPCHK(launch_ais_finish(h->stream, a.log_w, N, k, logpx, ess, &h->ds->rng[0], (unsigned)T));
+  return IWAE_OK;
+}
+
 // Encoder.call (F:56-F:75): k samples of q(h|x) per image on the layer-wise
 // kernels (the rows have to reach memory), relayouted into the reference's
 // sample-major buffers.
@@ -5440,6 +5556,8 @@ long long iwae_debug_count(const iwae_handle* h, int what) {
     case 24: return h->count.score_lw;
     case 25: return h->count.sgrad;
     case 26: return h->count.sgrad_lw;
+    case 27: return h->count.ais;
+    case 28: return h->count.ais_launch;
     default: return -1;
   }
 }

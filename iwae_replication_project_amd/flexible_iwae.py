@@ -136,6 +136,27 @@ def loss_config(loss_function, k, p=1.0, alpha=1.0, beta=0.5, k1=None, k2=None):
                                int(k1 or 0), int(k2 or 0))
 
 
+def ais_schedule(n_temps, kind="sigmoid", rad=4.0):
+    """The T + 1 inverse temperatures of an AIS run of T = ``n_temps`` transitions,
+    float32, from exactly 0 to exactly 1 and non-decreasing.  ``"linear"``: t / T;
+    ``"sigmoid"``: (s(rad (2 t / T - 1)) - s(-rad)) / (s(rad) - s(-rad)) with s the
+    logistic function (Wu et al. 2017): small steps where the weights move most."""
+    T = int(n_temps)
+    if T < 1:
+        raise ValueError("n_temps must be at least 1")
+    t = np.linspace(0.0, 1.0, T + 1)
+    if kind == "linear":
+        b = t
+    elif kind == "sigmoid":
+        s = lambda v: 1.0 / (1.0 + np.exp(-v))
+        b = (s(float(rad) * (2.0 * t - 1.0)) - s(-float(rad))) / (s(float(rad)) - s(-float(rad)))
+    else:
+        raise ValueError('kind must be "linear" or "sigmoid"')
+    b = np.maximum.accumulate(np.clip(b, 0.0, 1.0)).astype(np.float32)
+    b[0], b[-1] = 0.0, 1.0
+    return b
+
+
 # --------------------------------------------------------------- optimizer
 class Adam:
     """Keras ``tf.keras.optimizers.Adam`` knobs used by E:36-E:40 (defaults are
@@ -1129,6 +1150,98 @@ class Flexible_Model:
             self.hmc_info = {"proposal": q, "h_old": h_old, "h_new": h_new}
         self._stream.synchronize()
         return cur, acc, acc_sum / n_iter, lp_cur
+
+    def ais(self, x, k, betas=None, n_temps=1000, init="prior", h0=None, step_size=0.1, n_leapfrog=10,
+            adapt=(1.02, 0.98, 1e-4, 1.0), momentum=None, u=None, step=None, chunk=0):
+        """Annealed importance sampling of log p(x) (iwae_ais; Wu et al. 2017): k
+        chains per image, each a row (sample s, image b), run through the
+        schedule ``betas`` (default ``ais_schedule(n_temps)``; any values in
+        [0, 1]: ascending from 0 to 1 is AIS, descending from 1 the reverse chain
+        of bidirectional Monte Carlo, constant 1 plain HMC on p(h|x)) by
+        Metropolis-adjusted HMC transitions of ``n_leapfrog`` leapfrog steps,
+        entirely on the device.  ``init="prior"`` anneals from p(h) to p(x, h),
+        ``init="q"`` from q(h|x).  Initial latents: ``h0`` (L arrays [k, B, d_i],
+        as ``score`` takes; e.g. ``sample(return_latents=True)["h"]`` reshaped,
+        for a reverse chain), else the encoder's samples (``init="q"``) or
+        ancestral samples of the prior (``init="prior"``), both on device noise.
+        Every chain has its own step size, ``step_size`` at first (or ``step``
+        [k, B]), multiplied by ``adapt[0]`` after an accepted and ``adapt[1]``
+        after a rejected transition and kept in [``adapt[2]``, ``adapt[3]``].
+        ``momentum``: per transition a list of L arrays [k, B, d_i]; ``u``:
+        [T, k, B] uniforms in (0, 1); absent, both are device noise (Philox,
+        the stream ``set_seed`` positions).  Returns a dict of device tensors:
+        ``"logpx"`` [B] = logsumexp_s log_w - log k, ``"log_w"`` [k, B],
+        ``"ess"`` [B], ``"h"`` (the L final latents [k, B, d_i]),
+        ``"accept_rate"`` [k, B] and ``"step"`` [k, B] (the final step sizes).
+        The chain itself never waits for the host; the call synchronizes once,
+        at the end (drawing the initial latents is a call of its own)."""
+        if init not in ("prior", "q"):
+            raise ValueError('init must be "prior" or "q"')
+        xd = self._x(x)
+        B, k = xd.shape[0], int(k)
+        if B <= 0 or k <= 0:
+            raise ValueError("B and k must be positive")
+        bt = np.ascontiguousarray(ais_schedule(int(n_temps)) if betas is None else betas, dtype=np.float32).ravel()
+        T = bt.size - 1
+        n_leapfrog = int(n_leapfrog)
+        if T < 1 or n_leapfrog < 1:
+            raise ValueError("betas must hold at least two values and n_leapfrog must be positive")
+        if len(adapt) != 4:
+            raise ValueError("adapt must be (inc, dec, step_min, step_max)")
+        dims = self.n_latent_encoder
+        L = len(dims)
+        if h0 is not None:
+            ts, kk, BB = self._latents(h0)
+            if (kk, BB) != (k, B):
+                raise ValueError(f"h0 must be [k={k}, B={B}, d_i] per layer, got [{kk}, {BB}, d_i]")
+            with torch.cuda.stream(self._stream):
+                hs = [t.clone() for t in ts]
+        elif init == "q":
+            hs = self._encode(xd, k, chunk=chunk)[0]
+        else:
+            # (iwae_generate wants an image output: the probabilities, which draw nothing more)
+            hs = [t.reshape(k, B, d) for t, d in zip(self._generate(k * B, None, None, None, True, False, True)[2], dims)]
+        keep = []
+        marr, nm = None, 0
+        if momentum is not None:
+            if len(momentum) != T:
+                raise ValueError(f"momentum must hold {T} lists (one per transition)")
+            for r in momentum:
+                rs, kk, BB = self._latents(r)
+                if (kk, BB) != (k, B):
+                    raise ValueError("momentum must be shaped like the latents")
+                keep += rs
+            marr, nm = _lib.fptr_array(keep)
+        ut = st = None
+        with torch.cuda.stream(self._stream):
+            if u is not None:
+                ut = torch.as_tensor(u).to(device=self.device, dtype=torch.float32)
+                if tuple(ut.shape) != (T, k, B):
+                    raise ValueError(f"u must be [T={T}, k={k}, B={B}], got {tuple(ut.shape)}")
+                ut = ut.transpose(1, 2).contiguous()
+            if step is not None:
+                st = torch.as_tensor(step).to(device=self.device, dtype=torch.float32)
+                if tuple(st.shape) != (k, B):
+                    raise ValueError(f"step must be [k={k}, B={B}], got {tuple(st.shape)}")
+                st = st.t().contiguous()
+            else:
+                st = torch.full((B, k), float(step_size), device=self.device)
+            lw = torch.empty(B, k, device=self.device)
+            acc = torch.empty(B, k, device=self.device)
+            lpx = torch.empty(B, device=self.device)
+            ess = torch.empty(B, device=self.device)
+        cfg = _lib.IwaeAisConfig(init=0 if init == "prior" else 1, n_temps=T, n_leapfrog=n_leapfrog, accumulate=0,
+                                 step=float(step_size), adapt_inc=float(adapt[0]), adapt_dec=float(adapt[1]),
+                                 step_min=float(adapt[2]), step_max=float(adapt[3]))
+        harr, nh = _lib.fptr_array(hs)
+        self._call(self._lib.iwae_ais(self._h, _lib.fptr(xd), B, k, int(chunk), harr, nh, ctypes.byref(cfg),
+                                      bt.ctypes.data_as(_lib.FP), marr, nm, _lib.fptr(ut), _lib.fptr(st), _lib.fptr(lw),
+                                      _lib.fptr(acc), _lib.fptr(lpx), _lib.fptr(ess)))
+        with torch.cuda.stream(self._stream):
+            out = {"logpx": lpx, "log_w": lw.t().contiguous(), "ess": ess, "h": hs,
+                   "accept_rate": (acc / T).t().contiguous(), "step": st.t().contiguous()}
+        self._stream.synchronize()
+        return out
 
     def _encode(self, x, n_samples, eps=None, chunk=0):
         """iwae_encode behind ``model.encoder(x, n_samples)``."""

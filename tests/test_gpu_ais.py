@@ -1,0 +1,404 @@
+"""Annealed importance sampling on the device (iwae_ais; Flexible_Model.ais)
+against the float64 reference of tests/ais_ref.py, on the automatic path of
+these cases (the fused sg_kernel) and on the layer-wise path.
+
+Bars.  Decisions, accept counts and step sizes follow the reference (steps at
+rtol 1e-6: float32 products of the same factors).  log_w within 1e-4 of
+max|ref log_w|, the final latents within 1e-4 of max|ref| per layer: the
+project's bars, as hmc's test uses them; tests/test_ais_ref.py shows the
+float32 + bf16x3 emulation within a quarter of both.  logpx and ess against
+float64 formulas on the device's own log_w at 1e-5 relative, so the reduction
+is tested apart from the chain.  test_parity prints the worst figures
+(DESIGN.md s9 has the table)."""
+import ctypes
+
+import numpy as np
+import pytest
+
+from oracle import iwae_oracle as O
+import ais_ref as A
+import noise_ref as NR
+import score_ref as R
+import scoregrad_ref as G
+from test_gpu_parity import make_model
+from test_gpu_score import _f32, _model
+
+pytestmark = pytest.mark.gpu
+
+BAR = 1e-4
+PATHS = ("auto", "layerwise")
+T = len(A.BETAS) - 1
+
+
+def _counts(m, ids=(27, 28, 25, 26)):
+    return [int(m._lib.iwae_debug_count(m._h, i)) for i in ids]
+
+
+def _np(ts):
+    return [t.cpu().numpy() for t in ts]
+
+
+def _u(ref):
+    return np.exp(ref["log_u"]).astype(np.float32)
+
+
+def _run(m, name, init, ref, betas=A.BETAS, **kw):
+    _, _, x, _ = R.case(name)
+    _, B, k = R.CASES[name][:3]
+    step, _ = A.AIS_CASES[name, init]
+    n = len(betas) - 1
+    kw.setdefault("momentum", [_f32(r) for r in ref["momenta"][:n]])
+    kw.setdefault("u", _u(ref)[:n])
+    return m.ais(_f32(x), k, betas=betas, init=init, h0=_f32(R.latents(name, A.START[init])), step_size=step,
+                 n_leapfrog=A.N_LEAPFROG, adapt=A.ADAPT, **kw)
+
+
+def _compare(out, ref, h0, n_trans, label):
+    """The device's run against the reference's: decisions, steps, weights, latents, the reduction."""
+    acc = out["accept_rate"].cpu().numpy().astype(np.float64) * n_trans
+    np.testing.assert_array_equal(np.rint(acc), ref["accepts"])
+    assert np.abs(acc - np.rint(acc)).max() < 1e-4
+    np.testing.assert_allclose(out["step"].cpu().numpy(), ref["step"], rtol=1e-6)
+    lw = out["log_w"].cpu().numpy().astype(np.float64)
+    ew = np.abs(lw - ref["log_w"]).max() / np.abs(ref["log_w"]).max()
+    eh = [np.abs(a - b).max() / np.abs(b).max() for a, b in zip(_np(out["h"]), ref["h"])]
+    never = ref["accepts"] == 0
+    for a, src in zip(_np(out["h"]), h0):
+        np.testing.assert_array_equal(a[never], _f32(src)[never])        # rejected chains return their input bits
+    lp, ess = A.finish(lw)
+    ep = np.abs(out["logpx"].cpu().numpy() - lp).max() / np.abs(lp).max()
+    ee = (np.abs(out["ess"].cpu().numpy() - ess) / ess).max()
+    print(f"{label} log_w {ew:.2e} of max|ref|; latents {max(eh):.2e} of max|ref|; logpx {ep:.2e}, ess {ee:.2e} relative")
+    assert ew <= BAR and max(eh) <= BAR, (label, ew, eh)
+    assert ep <= 1e-5 and ee <= 1e-5, (label, ep, ee)
+    return ew, max(eh)
+
+
+# ------------------------------------------------------------------ 1. parity
+@pytest.mark.parametrize("path", PATHS)
+@pytest.mark.parametrize("name,init", list(A.AIS_CASES))
+def test_parity(name, init, path):
+    ref = A.ais_case(name, init)
+    m = _model(name, path)
+    out = _run(m, name, init, ref)
+    _, B, k = R.CASES[name][:3]
+    assert tuple(out["log_w"].shape) == (k, B) and tuple(out["logpx"].shape) == (B,) and tuple(out["ess"].shape) == (B,)
+    _compare(out, ref, R.latents(name, A.START[init]), T, f"[{name} {init} {path}]")
+    assert (ref["accepts"] == 0).any() or (ref["accepts"] < T).any()
+    m.check_kernel_status()
+
+
+# ---------------------------------------------------------------- 2. counters
+@pytest.mark.parametrize("path", PATHS)
+def test_counters(path):
+    name, init = "S2", "q"
+    ref = A.ais_case(name, init)
+    _, B, _ = R.CASES[name][:3]
+    m = _model(name, path)
+    for chunk, chunks in ((0, 1), (2, (B + 1) // 2)):
+        c0 = _counts(m)
+        _run(m, name, init, ref, chunk=chunk)
+        d = [b - a for a, b in zip(c0, _counts(m))]
+        passes = T * (A.N_LEAPFROG + 1)
+        assert d[0] == T and d[1] == passes, d
+        assert d[2] + d[3] == passes * chunks, d
+        assert (d[3] == 0) if path == "auto" else (d[2] == 0), d
+
+
+# ------------------------------------------------- 3. constant betas are HMC
+@pytest.mark.parametrize("path", PATHS)
+@pytest.mark.parametrize("name", list(G.HMC_CASES))
+def test_constant_betas_are_hmc(name, path):
+    _, _, x, _ = R.case(name)
+    _, B, k = R.CASES[name][:3]
+    step, nl, _ = G.HMC_CASES[name]
+    r, q, H0, H1, lu, acc = G.hmc_case(name)
+    h = R.latents(name, "on")
+    m = _model(name, path)
+    out = m.ais(_f32(x), k, betas=(1.0, 1.0), init="prior", h0=_f32(h), step_size=step, n_leapfrog=nl,
+                adapt=(1.0, 1.0, 1e-4, 1.0), momentum=[_f32(r)], u=np.exp(lu)[None])
+    got = out["accept_rate"].cpu().numpy()
+    np.testing.assert_array_equal(got, acc.astype(np.float32))
+    assert acc.any() and (~acc).any()
+    np.testing.assert_array_equal(out["step"].cpu().numpy(), np.full((k, B), step, np.float32))
+    np.testing.assert_array_equal(out["log_w"].cpu().numpy(), np.zeros((k, B), np.float32))
+    for i, (a, p, src) in enumerate(zip(_np(out["h"]), q, h)):
+        want = np.where(acc[..., None], p, src)
+        err = np.abs(a - want).max() / np.abs(want).max()
+        print(f"[{name} {path}] returned h_{i + 1}: {err:.2e} of max|ref|")
+        assert err <= BAR, (i, err)
+        np.testing.assert_array_equal(a[~acc], _f32(src)[~acc])
+    m.check_kernel_status()
+
+
+# ------------------------------------------------------------ 4. bit-exactness
+def _raw(m, x, hs, betas, init, nl, step, adapt, accumulate=0, mom=None, u=None, step_io=None, log_w=None, accepts=None,
+         logpx=None, ess=None, chunk=0, n_lat=None, lat=None, cfg=True, x_null=False, betas_null=False, N=None, k=None,
+         n_mom=None, n_temps=None):
+    """iwae_ais through ctypes on device tensors (hs [k, B, d_i] updated in place); returns the code."""
+    import torch
+    from iwae_replication_project_amd import _lib
+    kk, BB = hs[0].shape[:2]
+    bt = np.ascontiguousarray(betas, np.float32)
+    c = _lib.IwaeAisConfig(init=init, n_temps=bt.size - 1 if n_temps is None else n_temps, n_leapfrog=nl,
+                           accumulate=accumulate, step=step, adapt_inc=adapt[0], adapt_dec=adapt[1], step_min=adapt[2],
+                           step_max=adapt[3])
+    harr, nh = _lib.fptr_array(hs)
+    marr, nm = _lib.fptr_array(mom) if mom is not None else (None, 0)
+    P = _lib.fptr
+    with torch.cuda.stream(m._stream):
+        rc = m._lib.iwae_ais(m._h, None if x_null else P(x), BB if N is None else N, kk if k is None else k, chunk,
+                             harr if lat is None else lat, nh if n_lat is None else n_lat,
+                             ctypes.byref(c) if cfg else None, None if betas_null else bt.ctypes.data_as(_lib.FP),
+                             marr, nm if n_mom is None else n_mom, P(u), P(step_io), P(log_w), P(accepts), P(logpx), P(ess))
+    m._stream.synchronize()
+    return rc
+
+
+def _dev(m, arrays):
+    import torch
+    return [torch.as_tensor(np.ascontiguousarray(a, np.float32), device=m.device) for a in arrays]
+
+
+@pytest.mark.parametrize("path", PATHS)
+@pytest.mark.parametrize("name", ["S2", "C784"])
+def test_bit_exactness(name, path):
+    import torch
+    init = "q"
+    ref = A.ais_case(name, init)
+    _, _, x, _ = R.case(name)
+    _, B, k = R.CASES[name][:3]
+    step, _ = A.AIS_CASES[name, init]
+    m = _model(name, path)
+    keys = ("log_w", "logpx", "ess", "accept_rate", "step")
+
+    def same(a, b, what):
+        for u, v in zip(_np(a["h"]), _np(b["h"])):
+            np.testing.assert_array_equal(u, v, err_msg=what)
+        for n in keys:
+            np.testing.assert_array_equal(a[n].cpu().numpy(), b[n].cpu().numpy(), err_msg=f"{what} {n}")
+    whole = _run(m, name, init, ref)
+    same(whole, _run(m, name, init, ref), "the same call twice")
+    same(whole, _run(m, name, init, ref, chunk=1), "chunk 1")
+    # one call over betas[0..4] against [0..2] then [2..4] continuing on the first call's state
+    xt = _dev(m, [x])[0]
+    mom_all = [_dev(m, r) for r in ref["momenta"]]
+    u_all = torch.as_tensor(np.ascontiguousarray(_u(ref).transpose(0, 2, 1)), device=m.device)      # [T][B][k]
+    for noise in ("injected", "device"):
+        res = []
+        for split in (False, True):
+            m.set_seed(4242)
+            hs = _dev(m, R.latents(name, A.START[init]))
+            st = torch.full((B, k), step, device=m.device)
+            lw, ac = torch.full((B, k), 9.0, device=m.device), torch.full((B, k), 9.0, device=m.device)
+            lp, es = torch.empty(B, device=m.device), torch.empty(B, device=m.device)
+            for j, (t0, t1) in enumerate(((0, 2), (2, T)) if split else ((0, T),)):
+                kw = {}
+                if noise == "injected":
+                    kw = dict(mom=[t for r in mom_all[t0:t1] for t in r], u=u_all[t0:t1].contiguous())
+                assert _raw(m, xt, hs, A.BETAS[t0:t1 + 1], 1, A.N_LEAPFROG, step, A.ADAPT, accumulate=int(j > 0),
+                            step_io=st, log_w=lw, accepts=ac, logpx=lp, ess=es, **kw) == 0
+            res.append(_np(hs) + _np([st, lw, ac, lp, es]))
+        for u, v in zip(*res):
+            np.testing.assert_array_equal(u, v, err_msg=f"two calls against one, {noise} noise")
+        if noise == "injected":                                      # and both are the facade's result
+            for u, v in zip(res[0], _np(whole["h"]) + [whole["step"].t().cpu().numpy(), whole["log_w"].t().cpu().numpy()]):
+                np.testing.assert_array_equal(u, v)
+    m.check_kernel_status()
+
+
+def test_accumulating_without_weights_starts_them_at_zero_and_keeps_the_accept_counts():
+    import torch
+    name, init = "S2", "q"
+    ref = A.ais_case(name, init)
+    _, _, x, _ = R.case(name)
+    _, B, k = R.CASES[name][:3]
+    step, _ = A.AIS_CASES[name, init]
+    m = _model(name, "auto")
+    whole = _run(m, name, init, ref)
+    hs = _dev(m, R.latents(name, A.START[init]))
+    mom = [t for r in ref["momenta"] for t in _dev(m, r)]
+    u = torch.as_tensor(np.ascontiguousarray(_u(ref).transpose(0, 2, 1)), device=m.device)
+    ac, lp = torch.full((B, k), 5.0, device=m.device), torch.empty(B, device=m.device)
+    assert _raw(m, _dev(m, [x])[0], hs, A.BETAS, 1, A.N_LEAPFROG, step, A.ADAPT, accumulate=1, mom=mom, u=u, accepts=ac,
+                logpx=lp) == 0
+    np.testing.assert_array_equal(ac.cpu().numpy(), 5.0 + ref["accepts"].T)
+    np.testing.assert_array_equal(lp.cpu().numpy(), whole["logpx"].cpu().numpy())
+
+
+# ------------------------------------------------------------- 5. device noise
+@pytest.mark.parametrize("path", PATHS)
+@pytest.mark.parametrize("name,init", list(A.NOISE_CASES))
+def test_device_noise(name, init, path):
+    ref = A.noise_case(name, init)
+    spec, params, x, _ = R.case(name)
+    _, B, k = R.CASES[name][:3]
+    step, seed = A.NOISE_CASES[name, init]
+    n = len(A.NOISE_BETAS) - 1
+    h0 = R.latents(name, A.START[init])
+    m = _model(name, path)
+    for injected in (False, True):
+        m.set_seed(seed)
+        kw = dict(momentum=[_f32(r) for r in ref["momenta"]], u=ref["u"]) if injected else {}
+        out = m.ais(_f32(x), k, betas=A.NOISE_BETAS, init=init, h0=_f32(h0), step_size=step, n_leapfrog=A.N_LEAPFROG,
+                    adapt=A.ADAPT, **kw)
+        _compare(out, ref, h0, n, f"[{name} {init} {path} {'injected' if injected else 'device'} noise]")
+        # the position is now n: the encoder's next device draw is noise_ref's at that base
+        eps = NR.eps_forward(NR.key(seed), n, B, k, spec.n_latent_encoder)
+        want = O.forward(params, spec, x, eps)["h"]
+        got, _, _ = m.encoder(_f32(x), k)
+        for a, b in zip(_np(got), want):
+            assert np.abs(a - b).max() <= BAR * np.abs(b).max()
+    m.check_kernel_status()
+
+
+# -------------------------------------------------------------------- 6. state
+def test_ais_leaves_the_training_state_alone():
+    from iwae_replication_project_amd import Adam
+    he, hd, le, ld = R.CASES["C784"][0]
+    rng = np.random.default_rng(5)
+    x = (rng.random((40, 784)) < 0.3).astype(np.float32)
+    k = 17
+    models = []
+    for _ in range(2):
+        m = make_model(he, hd, le, ld, seed=11)
+        m.compile(optimizer=Adam(learning_rate=1e-3, epsilon=1e-4))
+        models.append(m)
+    a, b = models
+    b.set_weights(a.get_weights())
+    la, lb = a.train_steps(x, 20), b.train_steps(x, 20)
+    np.testing.assert_array_equal(np.asarray(la), np.asarray(lb))
+    w0, (m0, v0, t0), g0 = a.get_weights(), a.get_optimizer_state(), a.graph_captures()
+    n = 3
+    h, _, _ = a.encoder(x[:5], k)
+    b.encoder(x[:5], k)
+    out = a.ais(x[:5], k, n_temps=n, init="q", h0=h, step_size=0.05, n_leapfrog=2)      # device-drawn momenta and u
+    assert np.isfinite(out["logpx"].cpu().numpy()).all() and tuple(out["log_w"].shape) == (k, 5)
+    w1, (m1, v1, t1) = a.get_weights(), a.get_optimizer_state()
+    for p, q in zip(w0, w1):
+        np.testing.assert_array_equal(p, q)
+    np.testing.assert_array_equal(m0, m1)
+    np.testing.assert_array_equal(v0, v1)
+    assert t0 == t1 and a.graph_captures() == g0
+    for _ in range(n):                                     # the position moved by n: the other model draws n times
+        b.get_log_weights(x[:5], k)
+    np.testing.assert_array_equal(a.get_log_weights(x[:5], k).cpu().numpy(), b.get_log_weights(x[:5], k).cpu().numpy())
+    la, lb = a.train_steps(x, 20), b.train_steps(x, 20)
+    assert a.graph_captures() == g0                        # replayed, not re-captured
+    np.testing.assert_array_equal(np.asarray(la), np.asarray(lb))
+    for p, q in zip(a.get_weights(), b.get_weights()):
+        np.testing.assert_array_equal(p, q)
+    a.check_kernel_status()
+
+
+# ---------------------------------------------------------------- 7. arguments
+@pytest.mark.parametrize("path", PATHS)
+def test_invalid_arguments_return_einval_and_launch_nothing(path):
+    import torch
+    from iwae_replication_project_amd import _lib
+    name, init = "S2", "q"
+    ref = A.ais_case(name, init)
+    _, _, x, _ = R.case(name)
+    _, B, k = R.CASES[name][:3]
+    L = len(ref["h"])
+    m = _model(name, path)
+    xt = _dev(m, [x])[0]
+    h0 = R.latents(name, "on")
+    hs = _dev(m, h0)
+    mom = [t for r in ref["momenta"] for t in _dev(m, r)]
+    one = (_lib.FP * L)(_lib.fptr(hs[0]), *([None] * (L - 1)))
+    mnull = list(mom)
+    mnull[3] = None
+    nan, inf = float("nan"), float("inf")
+    ok = dict(betas=A.BETAS, init=1, nl=2, step=0.1, adapt=A.ADAPT)
+    bad = dict(
+        cfg_null=dict(cfg=False), betas_null=dict(betas_null=True), x_null=dict(x_null=True),
+        lat_null=dict(lat=ctypes.cast(None, _lib.FPP)), a_null_latent=dict(lat=one), n_lat_not_L=dict(n_lat=L - 1),
+        n_mom_not_0_or_TL=dict(mom=mom[:-1]), n_mom_without_buffers=dict(n_mom=T * L), a_null_momentum=dict(mom=mnull),
+        init_2=dict(init=2), init_negative=dict(init=-1), no_transition=dict(n_temps=0), T_negative=dict(n_temps=-1),
+        T_above_limit=dict(n_temps=(1 << 24) + 1),
+        no_leapfrog=dict(nl=0), beta_nan=dict(betas=(0.0, nan, 1.0)), beta_inf=dict(betas=(0.0, inf)),
+        beta_above_1=dict(betas=(0.0, 1.5)), beta_negative=dict(betas=(-0.1, 1.0)),
+        step_zero=dict(step=0.0), step_negative=dict(step=-0.1), step_nan=dict(step=nan), step_inf=dict(step=inf),
+        inc_zero=dict(adapt=(0.0, 0.5, 0.01, 2.0)), dec_negative=dict(adapt=(1.25, -0.5, 0.01, 2.0)),
+        inc_nan=dict(adapt=(nan, 0.5, 0.01, 2.0)), min_above_max=dict(adapt=(1.25, 0.5, 2.0, 0.01)),
+        N_zero=dict(N=0), N_negative=dict(N=-3), k_zero=dict(k=0), k_negative=dict(k=-1),
+        k_above_limit=dict(k=(1 << 20) + 1), chunk_above_limit=dict(N=4096, k=1 << 20, chunk=2048),
+        chains_above_limit=dict(N=2048, k=1 << 20, chunk=1),
+    )
+    c0 = _counts(m)
+    for what, kw in bad.items():
+        assert _raw(m, xt, hs, **{**ok, **kw}) == -1, what
+        assert m._lib.iwae_last_error(m._h), what
+    assert _counts(m) == c0                                   # nothing was launched
+    for a, b in zip(_np(hs), h0):
+        np.testing.assert_array_equal(a, _f32(b))
+    assert _raw(m, xt, hs, **ok) == 0                          # every output absent: the state alone moves
+    m.check_kernel_status()
+
+
+@pytest.mark.parametrize("path", PATHS)
+def test_a_nan_row_stays_put_and_its_neighbours_are_unaffected(path):
+    name, init = "S2", "q"
+    ref = A.ais_case(name, init)
+    _, B, k = R.CASES[name][:3]
+    m = _model(name, path)
+    base = _run(m, name, init, ref)
+    s, b = 3, 1
+    h0 = [np.array(v) for v in _f32(R.latents(name, "on"))]
+    for v in h0:
+        v[s, b, :] = np.nan
+    _, _, x, _ = R.case(name)
+    step, _ = A.AIS_CASES[name, init]
+    out = m.ais(_f32(x), k, betas=A.BETAS, init=init, h0=h0, step_size=step, n_leapfrog=A.N_LEAPFROG, adapt=A.ADAPT,
+                momentum=[_f32(r) for r in ref["momenta"]], u=_u(ref))
+    keep = np.ones((k, B), bool)
+    keep[s, b] = False
+    for u, v, src in zip(_np(out["h"]), _np(base["h"]), h0):
+        np.testing.assert_array_equal(u[keep], v[keep])
+        assert np.isnan(u[s, b]).all()
+    assert out["accept_rate"].cpu().numpy()[s, b] == 0.0
+    for n in ("log_w", "accept_rate", "step"):
+        np.testing.assert_array_equal(out[n].cpu().numpy()[keep], base[n].cpu().numpy()[keep], err_msg=n)
+    dec, lo = np.float32(A.ADAPT[1]), np.float32(A.ADAPT[2])
+    want = np.float32(step)
+    for _ in range(T):
+        want = max(np.float32(want * dec), lo)
+    assert out["step"].cpu().numpy()[s, b] == want
+    others = [i for i in range(B) if i != b]
+    np.testing.assert_array_equal(out["logpx"].cpu().numpy()[others], base["logpx"].cpu().numpy()[others])
+    m.check_kernel_status()
+
+
+# ------------------------------------------------------------------- 8. facade
+@pytest.mark.parametrize("path", PATHS)
+def test_facade(path):
+    name = "S2"
+    spec, _, x, _ = R.case(name)
+    _, B, k = R.CASES[name][:3]
+    m = _model(name, path)
+    m.set_seed(99)
+    for init in ("q", "prior"):
+        out = m.ais(_f32(x), k, n_temps=6, init=init, step_size=0.05, n_leapfrog=2)
+        assert tuple(out["logpx"].shape) == (B,) and tuple(out["ess"].shape) == (B,)
+        for n in ("log_w", "accept_rate", "step"):
+            assert tuple(out[n].shape) == (k, B), n
+        assert [tuple(t.shape) for t in out["h"]] == [(k, B, d) for d in spec.n_latent_encoder]
+        for v in [out[n] for n in ("logpx", "log_w", "ess", "accept_rate", "step")] + list(out["h"]):
+            assert np.isfinite(v.cpu().numpy()).all()
+        ess, rate = out["ess"].cpu().numpy(), out["accept_rate"].cpu().numpy()
+        assert (ess >= 1 - 1e-5).all() and (ess <= k + 1e-3).all() and (rate >= 0).all() and (rate <= 1).all()
+    # one transition from the encoder's samples weighs them as score does
+    h, _, _ = m.encoder(_f32(x), k)
+    sc = m.score(_f32(x), h)
+    out = m.ais(_f32(x), k, betas=(0.0, 1.0), init="q", h0=h, step_size=0.05, n_leapfrog=1)
+    lw, want = out["log_w"].cpu().numpy(), sc["log_w"].cpu().numpy()
+    # (the same float32 densities summed in another order: the value bar, of the largest term)
+    assert np.abs(lw - want).max() <= BAR * max(np.abs(sc[n].cpu().numpy()).max() for n in ("log_q", "log_ph", "log_px"))
+    with pytest.raises(ValueError):
+        m.ais(_f32(x), k, n_temps=2, init="posterior")
+    with pytest.raises(ValueError):
+        m.ais(_f32(x), k, betas=(0.0, 1.5), h0=h)
+    with pytest.raises(ValueError):
+        m.ais(_f32(x), k + 1, n_temps=2, h0=h)
+    m.check_kernel_status()
