@@ -694,6 +694,85 @@ int iwae_ais(iwae_handle* h, const float* x, int N, int k, int chunk,
              float* step_io,
              float* log_w, float* accepts,
              float* logpx, float* ess);
+/* Per-image variational refinement ("local" optimisation of q; Cremer, Li &
+ * Duvenaud 2018): Adam ascent on the parameters of one diagonal Gaussian per
+ * image over all latent layers jointly, q*(h) = prod_i N(h_i; m_i,
+ * diag(exp(ls_i))^2), enqueued on the handle's stream with no host
+ * synchronization (only a workspace that has to grow waits).  mean[i],
+ * logstd[i] (required, n_par = L device buffers [N][d_i], encoder order h_1 ..
+ * h_L) are updated IN PLACE; x (required), N, k and chunk are iwae_score's,
+ * with its limits, and N k <= 2^30 rows.  With k samples per image, row (b,
+ * s): h_i = fmaf(exp(ls_i), eps_i, m_i) in float32 (the value the gradient
+ * pass sees), log q* = sum_ij (-eps^2 / 2 - ls_ij) - D / 2 log 2 pi with D =
+ * sum d_i, log w = log p(h) + log p(x|h_1) - log q*.  objective 0 (ELBO): the
+ * value is mean_s log w_s and a_s = 1 / k; objective 1 (IWAE_k): logsumexp_s
+ * log w_s - log k and a_s = softmax_s(log w).  With g = d(log p(h) + log
+ * p(x|h_1)) / dh (iwae_score_grad under (0, 1, 1)) the total reparameterised
+ * gradients are G^m_ij = sum_s a_s g_sij and G^ls_ij = (sum_s a_s g_sij
+ * eps_sij) exp(ls_ij) + 1, both summed in one fixed order.  Update n = step0
+ * + 1 .. step0 + n_iters, per parameter p with gradient G, in the train
+ * step's Adam form: m1 += (1 - beta1) (G - m1); m2 += (1 - beta2) (G^2 - m2);
+ * p += lr_n m1 / (sqrt(m2) + epsilon), lr_n = lr sqrt(1 - beta2^n) / (1 -
+ * beta1^n) formed on the host in double; then ls is clamped to [logstd_min,
+ * logstd_max].  After the n_iters updates one optional evaluation pass draws
+ * fresh samples at the final parameters and scores them (no gradient); it
+ * runs when any of lat_out / log_w / logpx / ess is asked for, and n_iters =
+ * 0 only evaluates the q* the caller supplies.  P = n_iters + (1 with an
+ * evaluation pass) passes draw noise: eps is NULL / 0, or P L device buffers
+ * [k][N][d_i], eps[p L + i] pass p's noise of layer i; absent, the noise of
+ * layer i is philox_normal4 under layer id 2 IWAE_MAX_LAYERS + 13 + i (column
+ * quad j / 4, value j % 4) at row b k + s over the whole call and base = the
+ * handle's noise position + p on the current key.  The noise position
+ * advances by P per call, whether or not noise was injected.  adam is NULL /
+ * 0 (the moments live in the call's workspace), or 4 L device buffers [N][d_i]:
+ * adam[4 i], adam[4 i + 1] the first and second moment of mean_i, adam[4 i +
+ * 2], adam[4 i + 3] those of logstd_i.  With step0 = 0 the moments start at
+ * zero and the buffers' contents are ignored; with step0 > 0 they are read,
+ * and a second call on the mean, logstd and adam a first call left, with
+ * step0 = the first call's n_iters, continues that run: its noise is the next
+ * passes of the same device stream (or the next injected buffers) and its
+ * result is bit for bit what one call over all iterations gives, provided
+ * the first call ran no evaluation pass.  Outputs, all optional: bound
+ * [n_iters][N], the objective's value at the parameters before update t on
+ * iteration t's samples; lat_out[i] [k][N][d_i] (n_lat 0 or L), the
+ * evaluation pass's samples; log_w [N][k], image-major; logpx = logsumexp_s
+ * log_w - log k and ess = (sum e)^2 / sum e^2 with e = exp(log_w - max), [N].
+ * Per call n_iters gradient passes and, with an evaluation, one scoring pass,
+ * each on the path iwae_score_grad would take (fused or layer-wise, never an
+ * error), and between them n_iters + 1 launches of iwae_refine.hip:
+ * refine_begin_kernel (pass 0's samples), refine_step_kernel (an iteration's
+ * weights, gradients, Adam update and the next pass's samples in one launch),
+ * refine_end_kernel (the last update and the evaluation's samples);
+ * refine_finish_kernel forms the evaluation's outputs and moves the noise
+ * position.  One workgroup owns an image; there are no float atomics, every
+ * element is written by one thread, the call is deterministic and its result
+ * does not depend on chunk, bit for bit.  Rows are independent: an image whose
+ * parameters are not finite has non-finite outputs and its neighbours are
+ * unaffected.  Weights, the model's Adam state, the train arena, captured
+ * graphs and engine plans are untouched (the samples, their noise, gradients
+ * and values are a workspace of the call's own, which only grows); the sticky
+ * error (iwae_status) is returned before any work is enqueued.  IWAE_EINVAL,
+ * with nothing launched: cfg, x, mean or logstd NULL or a NULL buffer among
+ * them, n_par != L, n_eps not 0 or P L, n_adam not 0 or 4 L, n_lat not 0 or L,
+ * a NULL buffer among eps / adam / lat_out, objective not 0 or 1, n_iters < 0
+ * or above 2^24, step0 < 0 or above 2^30, step0 > 0 without adam, n_iters = 0
+ * with no evaluation output, lr or epsilon not finite or <= 0, beta1 or beta2
+ * outside [0, 1), logstd_min > logstd_max or either not finite, N <= 0 or k <=
+ * 0, k, the chunk or N k above the limits. */
+typedef struct iwae_refine_config {
+  int objective;     /* 0 ELBO, 1 IWAE_k */
+  int n_iters;       /* >= 0, <= 2^24 */
+  int step0;         /* Adam steps already taken (continuation); >= 0 */
+  float lr, beta1, beta2, epsilon;
+  float logstd_min, logstd_max;
+} iwae_refine_config;                       /* 36 bytes */
+int iwae_refine(iwae_handle* h, const float* x, int N, int k, int chunk,
+                float* const* mean, float* const* logstd, int n_par,
+                const iwae_refine_config* cfg,
+                const float* const* eps, int n_eps,
+                float* const* adam, int n_adam,
+                float* bound, float* const* lat_out, int n_lat,
+                float* log_w, float* logpx, float* ess);
 /* Encoder.call (F:56-F:75): k samples of q(h|x) per image, with device noise
  * (eps NULL, n_eps 0) or injected eps[i] [k][N][d_i].  lat_out[i] [k][N][d_i],
  * sample-major (n_lat 0 or L); log_q [N][k]; loc_top / scale_top: the
@@ -764,7 +843,9 @@ double iwae_workspace_bytes(const iwae_handle* h);
  * fused score-gradient launches of iwae_score_grad (sg_kernel, one per chunk),
  * 26 its layer-wise score-gradient passes (one per chunk); 27 AIS transitions
  * run by iwae_ais, 28 its begin / step / end launches (n_temps (n_leapfrog +
- * 1) per call; the finish launch is not counted); -1 for an unknown id. */
+ * 1) per call; the finish launch is not counted); 29 refinement iterations
+ * run by iwae_refine, 30 its begin / step / end launches (n_iters + 1 per
+ * call; the finish launch is not counted); -1 for an unknown id. */
 long long iwae_debug_count(const iwae_handle* h, int what);
 /* Live kernel timing: bracket every launch of one kernel class with HIP events
  * on the handle's stream -- a GEMM class (kind: 0 forward, 1 backward-data,

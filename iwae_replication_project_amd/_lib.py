@@ -55,6 +55,14 @@ class IwaeAisConfig(ctypes.Structure):
     ]
 
 
+class IwaeRefineConfig(ctypes.Structure):
+    _fields_ = [
+        ("objective", c_int), ("n_iters", c_int), ("step0", c_int),
+        ("lr", c_float), ("beta1", c_float), ("beta2", c_float), ("epsilon", c_float),
+        ("logstd_min", c_float), ("logstd_max", c_float),
+    ]
+
+
 FP = POINTER(c_float)
 FPP = POINTER(FP)
 H = c_void_p
@@ -112,6 +120,8 @@ SIGNATURES = {
     "iwae_score_grad": (c_int, [H, FP, c_int, c_int, c_int, FPP, c_int, FP, FPP, c_int, FP, FP, FP]),
     "iwae_ais": (c_int, [H, FP, c_int, c_int, c_int, FPP, c_int, POINTER(IwaeAisConfig), FP, FPP, c_int, FP, FP, FP, FP,
                          FP, FP]),
+    "iwae_refine": (c_int, [H, FP, c_int, c_int, c_int, FPP, FPP, c_int, POINTER(IwaeRefineConfig), FPP, c_int, FPP, c_int,
+                            FP, FPP, c_int, FP, FP, FP]),
     "iwae_encode": (c_int, [H, FP, c_int, c_int, c_int, FPP, c_int, FPP, c_int, FP, FP, FP]),
     "iwae_train_step_masked": (c_int, [H, POINTER(IwaeLossConfig), FP, FP, c_int, FPP, c_int, FP]),
     "iwae_forward_backward_masked": (c_int, [H, POINTER(IwaeLossConfig), FP, FP, c_int, FPP, c_int, FP]),

@@ -1109,4 +1109,36 @@ hipError_t launch_ais_end(hipStream_t st, const AisArgs& a);
 hipError_t launch_ais_finish(hipStream_t st, const float* log_w, int N, int k, float* logpx, float* ess,
                              uint64_t* rng_base, unsigned n_adv);
 
+// -------------------- per-image variational refinement (iwae_refine.hip) ----
+// One call's launches between the gradient passes.  mean / logstd and the Adam
+// moments: per layer [N][d_i]; lat / epsw / g / eps_in / lat_out: per layer
+// [k][N][d_i], sample-major (lat, epsw: the workspace's latents and their
+// noise); every per-sample scalar [N][k].  lph / lpx and g are what the last
+// iwae_score_grad pass left for lat.
+struct RefineArgs {
+  int L, N, k, group, D;                // group: lanes per sample in the log q* sums, 16 or 64; D = sum d_i
+  int d[8], vec[8];                     // vec: the draw stores the layer in float4 (d % 4 == 0)
+  float* mean[8]; float* logstd[8];
+  float* m1m[8]; float* m2m[8]; float* m1s[8]; float* m2s[8];   // Adam moments of mean_i and of logstd_i
+  float* lat[8]; float* epsw[8]; const float* g[8];
+  const float* eps_in[8];               // draw: the pass's injected noise, or null (Philox normals, noise_layer + i)
+  const float *lph, *lpx;
+  float* lw;                            // log w_s, then a_s, of the current iteration
+  float* bound;                         // this iteration's [N], or null
+  int objective;                        // 0 ELBO, 1 IWAE_k
+  int zero;                             // the moments are taken as 0 (first update of a run)
+  int draw;                             // end: draw the evaluation pass
+  float lr_n, omb1, omb2, eps_hat, ls_min, ls_max;
+  uint64_t seed; const uint64_t* rng_base; unsigned pass;       // the draw's noise base = *rng_base + pass
+  int noise_layer;
+  // finish
+  int eval;                             // there was an evaluation pass
+  float* lat_out[8]; float* log_w; float* logpx; float* ess;   // each may be null (log_w: wherever logpx / ess need it)
+  uint64_t* rng_adv; unsigned n_adv;    // the noise position moves on by n_adv
+};
+hipError_t launch_refine_begin(hipStream_t st, const RefineArgs& a);
+hipError_t launch_refine_step(hipStream_t st, const RefineArgs& a);
+hipError_t launch_refine_end(hipStream_t st, const RefineArgs& a);
+hipError_t launch_refine_finish(hipStream_t st, const RefineArgs& a);
+
 }  // namespace iwae

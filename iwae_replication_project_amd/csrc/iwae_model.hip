@@ -215,6 +215,7 @@ struct Counters {
   long long score = 0, score_lw = 0;     // 23, 24: iwae_score chunks: score_kernel launches / layer-wise passes
   long long sgrad = 0, sgrad_lw = 0;     // 25, 26: iwae_score_grad chunks: sg_kernel launches / layer-wise passes
   long long ais = 0, ais_launch = 0;     // 27, 28: iwae_ais transitions / their begin, step and end launches
+  long long refine = 0, refine_launch = 0;   // 29, 30: iwae_refine iterations / its begin, step and end launches
 };
 
 // row-chain train engine plan (device resident, per shape; iwae_train.hip)
@@ -306,6 +307,8 @@ struct iwae_handle {
   int sg_rows = 0;
   float* ais_ws = nullptr;           // iwae_ais's chains (momenta, proposals, gradients per layer; H_old, the value
   size_t ais_ws_floats = 0;          // terms, and the weights / steps the caller did not give): its own allocation
+  float* refine_ws = nullptr;        // iwae_refine's samples (latents, noise, gradients per layer; the value terms,
+  size_t refine_ws_floats = 0;       // the weights, and the Adam moments the caller did not give): its own allocation
   float* loss_slots = nullptr;       // multi-step graphs: step j's loss (kGraphSteps floats), then
                                      // [kGraphSteps, 2 kGraphSteps): where a graph's copy node writes
                                      // when the call wants no losses
@@ -3307,6 +3310,7 @@ void iwae_destroy(iwae_handle* h) {
   if (h->post_ws) (void)hipFree(h->post_ws);
   if (h->sg_ws) (void)hipFree(h->sg_ws);
   if (h->ais_ws) (void)hipFree(h->ais_ws);
+  if (h->refine_ws) (void)hipFree(h->refine_ws);
   if (h->nr_units) (void)hipFree(h->nr_units);
   if (h->nrb_units) (void)hipFree(h->nrb_units);
   if (h->nre_units) (void)hipFree(h->nre_units);
@@ -5410,6 +5414,136 @@ int iwae_ais(iwae_handle* h, const float* x, int N, int k, int chunk, float* con
   return IWAE_OK;
 }
 
+// Per-image variational refinement (include/iwae.h): n_iters gradient passes
+// at the samples of q* (iwae_score_grad under (0, 1, 1), fused or layer-wise as
+// it decides) with one launch of iwae_refine.hip before the first, between each
+// pair and after the last, then one scoring pass and the finish launch where
+// the caller wants the evaluation.  Everything is enqueued on h->stream; the
+// samples' buffers (refine_ws) only grow, so the host waits only where a
+// workspace grows.
+int iwae_refine(iwae_handle* h, const float* x, int N, int k, int chunk, float* const* mean, float* const* logstd,
+                int n_par, const iwae_refine_config* cfg, const float* const* eps, int n_eps, float* const* adam,
+                int n_adam, float* bound, float* const* lat_out, int n_lat, float* log_w, float* logpx, float* ess) {
+  if (!h) return IWAE_EINVAL;
+  CHK(kernel_status(h));
+  const int L = h->L;
+  if (!cfg) return fail(h, IWAE_EINVAL, "cfg is NULL");
+  if (!x) return fail(h, IWAE_EINVAL, "x is NULL");
+  if (n_par != L || !mean || !logstd)
+    return fail(h, IWAE_EINVAL, "expected " + std::to_string(L) + " mean and logstd buffers (one per stochastic layer), got " +
+                                   std::to_string(n_par));
+  for (int i = 0; i < L; ++i)
+    if (!mean[i] || !logstd[i]) return fail(h, IWAE_EINVAL, "NULL mean or logstd buffer");
+  if (cfg->objective != 0 && cfg->objective != 1) return fail(h, IWAE_EINVAL, "objective must be 0 (ELBO) or 1 (IWAE_k)");
+  const int T = cfg->n_iters;
+  if (T < 0 || T > (1 << 24)) return fail(h, IWAE_EINVAL, "n_iters must be in [0, 2^24]");
+  if (cfg->step0 < 0 || cfg->step0 > (1 << 30)) return fail(h, IWAE_EINVAL, "step0 must be in [0, 2^30]");
+  if (!std::isfinite(cfg->lr) || cfg->lr <= 0.f) return fail(h, IWAE_EINVAL, "lr must be positive and finite");
+  if (!std::isfinite(cfg->epsilon) || cfg->epsilon <= 0.f)
+    return fail(h, IWAE_EINVAL, "epsilon must be positive and finite");
+  if (!(cfg->beta1 >= 0.f && cfg->beta1 < 1.f) || !(cfg->beta2 >= 0.f && cfg->beta2 < 1.f))
+    return fail(h, IWAE_EINVAL, "beta1 and beta2 must be in [0, 1)");
+  if (!std::isfinite(cfg->logstd_min) || !std::isfinite(cfg->logstd_max) || cfg->logstd_min > cfg->logstd_max)
+    return fail(h, IWAE_EINVAL, "logstd_min and logstd_max must be finite, logstd_min <= logstd_max");
+  if (n_lat != 0 && (n_lat != L || !lat_out))
+    return fail(h, IWAE_EINVAL, "expected 0 or " + std::to_string(L) + " sample buffers, got " + std::to_string(n_lat));
+  for (int i = 0; i < n_lat; ++i)
+    if (!lat_out[i]) return fail(h, IWAE_EINVAL, "NULL sample buffer");
+  const bool eval = n_lat > 0 || log_w || logpx || ess;
+  if (T == 0 && !eval) return fail(h, IWAE_EINVAL, "n_iters is 0 and no evaluation output is asked for");
+  const long long P = (long long)T + (eval ? 1 : 0);
+  if (n_eps != 0 && ((long long)n_eps != P * L || !eps))
+    return fail(h, IWAE_EINVAL, "expected 0 or (n_iters + evaluation) * " + std::to_string(L) + " noise buffers, got " +
+                                   std::to_string(n_eps));
+  for (int i = 0; i < n_eps; ++i)
+    if (!eps[i]) return fail(h, IWAE_EINVAL, "NULL noise buffer");
+  if (n_adam != 0 && (n_adam != 4 * L || !adam))
+    return fail(h, IWAE_EINVAL, "expected 0 or " + std::to_string(4 * L) + " Adam buffers, got " + std::to_string(n_adam));
+  for (int i = 0; i < n_adam; ++i)
+    if (!adam[i]) return fail(h, IWAE_EINVAL, "NULL Adam buffer");
+  if (cfg->step0 > 0 && n_adam == 0) return fail(h, IWAE_EINVAL, "step0 > 0 continues a run: it needs the Adam buffers");
+  if (!score_chunk(h, N, k, chunk)) return IWAE_EINVAL;
+  const long long rows = (long long)N * k;
+  if (rows > (1LL << 30)) return fail(h, IWAE_EINVAL, "N * k above 2^30 rows");
+  // ---- the samples' buffers: per layer latents, noise, gradients [k][N][d_i]; per row log p(h), log p(x|h), the
+  // weights; the moments [N][d_i] where the caller gave none.  Each starts on a 64-float boundary.
+  size_t off = 0;
+  auto take = [&](size_t n) { const size_t o = off; off += (n + 63) & ~size_t(63); return o; };
+  size_t o_h[IWAE_MAX_LAYERS], o_e[IWAE_MAX_LAYERS], o_g[IWAE_MAX_LAYERS], o_m[IWAE_MAX_LAYERS][4];
+  int dmax = 0, D = 0;
+  for (int i = 0; i < L; ++i) {
+    const int d = h->enc[i].d;
+    const size_t n = (size_t)rows * d;
+    o_h[i] = take(n); o_e[i] = take(n); o_g[i] = take(n);
+    for (int j = 0; j < 4; ++j) o_m[i][j] = n_adam ? 0 : take((size_t)N * d);
+    dmax = std::max(dmax, d);
+    D += d;
+  }
+  const size_t o_lph = take(rows), o_lpx = take(rows), o_w = take(rows);
+  if (off > h->refine_ws_floats) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (h->refine_ws) (void)hipFree(h->refine_ws);
+    h->refine_ws = nullptr; h->refine_ws_floats = 0;
+    HIPCHK(hipMalloc(&h->refine_ws, off * sizeof(float)));
+    h->refine_ws_floats = off;
+  }
+  float* ws = h->refine_ws;
+  RefineArgs a{};
+  a.L = L; a.N = N; a.k = k; a.D = D;
+  a.group = dmax <= 64 ? 16 : 64;
+  float *lat[IWAE_MAX_LAYERS], *gbuf[IWAE_MAX_LAYERS];
+  for (int i = 0; i < L; ++i) {
+    a.d[i] = h->enc[i].d;
+    a.vec[i] = (a.d[i] & 3) == 0;
+    a.mean[i] = mean[i]; a.logstd[i] = logstd[i];
+    a.m1m[i] = n_adam ? adam[4 * i] : ws + o_m[i][0];
+    a.m2m[i] = n_adam ? adam[4 * i + 1] : ws + o_m[i][1];
+    a.m1s[i] = n_adam ? adam[4 * i + 2] : ws + o_m[i][2];
+    a.m2s[i] = n_adam ? adam[4 * i + 3] : ws + o_m[i][3];
+    a.lat[i] = lat[i] = ws + o_h[i];
+    a.epsw[i] = ws + o_e[i];
+    a.g[i] = gbuf[i] = ws + o_g[i];
+    a.lat_out[i] = n_lat ? lat_out[i] : nullptr;
+  }
+  float *lph = ws + o_lph, *lpx = ws + o_lpx;
+  a.lph = lph; a.lpx = lpx; a.lw = ws + o_w;
+  a.objective = cfg->objective;
+  a.omb1 = 1.f - cfg->beta1; a.omb2 = 1.f - cfg->beta2; a.eps_hat = cfg->epsilon;
+  a.ls_min = cfg->logstd_min; a.ls_max = cfg->logstd_max;
+  a.seed = h->seed; a.rng_base = &h->ds->rng[0];
+  a.noise_layer = 2 * IWAE_MAX_LAYERS + 13;
+  a.eval = eval ? 1 : 0;
+  // logpx / ess are formed from the weights: in the workspace where the caller has no use for them
+  a.log_w = log_w ? log_w : (logpx || ess) ? ws + o_w : nullptr;
+  a.logpx = logpx; a.ess = ess;
+  a.rng_adv = &h->ds->rng[0]; a.n_adv = (unsigned)P;
+  const float coef[3] = {0.f, 1.f, 1.f};
+  auto pass_noise = [&](long long p) {             // the next draw is pass p's
+    a.pass = (unsigned)p;
+    for (int i = 0; i < L; ++i) a.eps_in[i] = n_eps ? eps[(size_t)p * L + i] : nullptr;
+  };
+  pass_noise(0);
+  HIPCHK(launch_refine_begin(h->stream, a));
+  ++h->count.refine_launch;
+  const double b1 = cfg->beta1, b2 = cfg->beta2;
+  for (int t = 0; t < T; ++t) {
+    CHK(iwae_score_grad(h, x, N, k, chunk, lat, L, coef, gbuf, L, nullptr, lph, lpx));
+    const double n = (double)cfg->step0 + t + 1;
+    a.lr_n = (float)((double)cfg->lr * std::sqrt(1.0 - std::pow(b2, n)) / (1.0 - std::pow(b1, n)));
+    a.zero = cfg->step0 == 0 && t == 0;
+    a.bound = bound ? bound + (size_t)t * N : nullptr;
+    a.draw = t + 1 < T || eval;
+    if (a.draw) pass_noise(t + 1);
+    if (t + 1 < T) HIPCHK(launch_refine_step(h->stream, a));
+    else HIPCHK(launch_refine_end(h->stream, a));
+    ++h->count.refine_launch;
+    ++h->count.refine;
+  }
+  if (eval) CHK(iwae_score_grad(h, x, N, k, chunk, lat, L, coef, nullptr, 0, nullptr, lph, lpx));
+  HIPCHK(launch_refine_finish(h->stream, a));
+  return IWAE_OK;
+}
+
 // Encoder.call (F:56-F:75): k samples of q(h|x) per image on the layer-wise
 // kernels (the rows have to reach memory), relayouted into the reference's
 // sample-major buffers.
@@ -5558,6 +5692,8 @@ long long iwae_debug_count(const iwae_handle* h, int what) {
     case 26: return h->count.sgrad_lw;
     case 27: return h->count.ais;
     case 28: return h->count.ais_launch;
+    case 29: return h->count.refine;
+    case 30: return h->count.refine_launch;
     default: return -1;
   }
 }

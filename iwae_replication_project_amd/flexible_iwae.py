@@ -1243,6 +1243,131 @@ class Flexible_Model:
         self._stream.synchronize()
         return out
 
+    REFINE_OUTPUTS = ("bound", "log_w", "logpx", "ess", "h")
+
+    def _encoder_gaussian(self, xd):
+        """(means, logstds), L device tensors [B, d_i] each: the encoder's mean chain
+        (h_i at zero noise) and its scales along it, from iwae_encode alone."""
+        B = xd.shape[0]
+        dims = self.n_latent_encoder
+        L = len(dims)
+        if L == 1:
+            _, _, top = self._encode(xd, 1, eps=[np.zeros((1, B, dims[0]), np.float32)])
+            with torch.cuda.stream(self._stream):
+                return [top.loc.clone()], [torch.log(top.scale)]
+        # sample 0: no noise; sample j: unit noise at layer j only, so h_j moves by exactly its scale
+        eps = [np.zeros((L + 1, B, d), np.float32) for d in dims]
+        for j in range(L):
+            eps[j][j + 1] = 1.0
+        hs, _, _ = self._encode(xd, L + 1, eps=eps)
+        with torch.cuda.stream(self._stream):
+            return [h[0].clone() for h in hs], [torch.log(h[j + 1] - h[0]) for j, h in enumerate(hs)]
+
+    def refine(self, x, k, n_iters=100, objective="ELBO", lr=0.01, betas=(0.9, 0.999), epsilon=1e-7,
+               logstd_range=(-12.0, 4.0), init="encoder", state=None, eps=None, chunk=0, want=REFINE_OUTPUTS):
+        """Per-image variational refinement (iwae_refine; Cremer, Li & Duvenaud
+        2018): ``n_iters`` Adam ascent steps on one diagonal Gaussian per image
+        over all latent layers, q*(h) = prod_i N(h_i; m_i, exp(ls_i)^2), with k
+        reparameterised samples per image and step, entirely on the device.
+        ``objective``: ``"ELBO"`` (mean_s log w_s) or ``"IWAE"`` (logsumexp_s log
+        w_s - log k).  ``init``: ``"encoder"`` (the encoder's mean chain and its
+        scales along it, one ``encoder`` call) or a pair ``(means, logstds)`` of L
+        arrays [B, d_i] each (copied).  ``lr``, ``betas``, ``epsilon``: Adam's;
+        the log standard deviations are kept in ``logstd_range``.  After the
+        updates one evaluation pass draws k fresh samples at the final parameters
+        when ``want`` names any of ``"log_w"`` [k, B], ``"logpx"`` [B] =
+        logsumexp_s log_w - log k (at ELBO-optimal q* and large k: the estimate
+        whose distance to ``ais`` is the approximation gap), ``"ess"`` [B] and
+        ``"h"`` (the L sample tensors [k, B, d_i]); ``"bound"`` [n_iters, B] is
+        the objective before each update on that step's samples.  ``n_iters=0``
+        only evaluates the given q*.  ``eps``: per pass (the ``n_iters`` steps,
+        then the evaluation if there is one) a list of L arrays [k, B, d_i];
+        absent: device noise (Philox, the stream ``set_seed`` positions).
+        Returns a dict of device tensors: ``"mean"``, ``"logstd"`` (lists of [B,
+        d_i]), the entries of ``want``, and ``"state"`` (Adam's moments and step
+        count), which ``state=`` takes back, together with ``init=(out["mean"],
+        out["logstd"])``, to continue the run: two such calls give bit for bit
+        what one call over all the steps gives when the first evaluated nothing
+        (``want=("bound",)``).  The call synchronizes once, at the end."""
+        if objective not in ("ELBO", "IWAE"):
+            raise ValueError('objective must be "ELBO" or "IWAE"')
+        want = (want,) if isinstance(want, str) else tuple(want)
+        bad = [w for w in want if w not in self.REFINE_OUTPUTS]
+        if bad:
+            raise ValueError(f"want must name some of {self.REFINE_OUTPUTS}, got {want}")
+        xd = self._x(x)
+        B, k, T = xd.shape[0], int(k), int(n_iters)
+        if B <= 0 or k <= 0 or T < 0:
+            raise ValueError("B and k must be positive, n_iters non-negative")
+        if len(betas) != 2 or len(logstd_range) != 2:
+            raise ValueError("betas must be (beta1, beta2), logstd_range (min, max)")
+        dims = self.n_latent_encoder
+        L = len(dims)
+        if isinstance(init, str):
+            if init != "encoder":
+                raise ValueError('init must be "encoder" or a (means, logstds) pair')
+            mean, logstd = self._encoder_gaussian(xd)
+        else:
+            if len(init) != 2 or len(init[0]) != L or len(init[1]) != L:
+                raise ValueError(f"init must be (means, logstds), {L} arrays [B, d_i] each")
+            with torch.cuda.stream(self._stream):
+                mean, logstd = ([torch.as_tensor(v).to(device=self.device, dtype=torch.float32).clone().contiguous()
+                                 for v in part] for part in init)
+            for t, d in zip(mean + logstd, list(dims) * 2):
+                if tuple(t.shape) != (B, d):
+                    raise ValueError(f"init arrays must be [B={B}, d_i], got {tuple(t.shape)} for d_i = {d}")
+        evaluate = any(w in want for w in ("log_w", "logpx", "ess", "h"))
+        if T == 0 and not evaluate:
+            raise ValueError("n_iters = 0 with no evaluation output has nothing to do")
+        P = T + (1 if evaluate else 0)
+        keep = []
+        if eps is not None:
+            if len(eps) != P:
+                raise ValueError(f"eps must hold {P} lists (one per step, then the evaluation's)")
+            for e in eps:
+                es, kk, BB = self._latents(e)
+                if (kk, BB) != (k, B):
+                    raise ValueError(f"eps arrays must be [k={k}, B={B}, d_i]")
+                keep += es
+        earr, ne = _lib.fptr_array(keep)
+        step0 = 0
+        with torch.cuda.stream(self._stream):
+            if state is not None:
+                step0, adam = int(state["step"]), list(state["adam"])
+                if len(adam) != 4 * L or any(tuple(t.shape) != (B, dims[i // 4]) for i, t in enumerate(adam)):
+                    raise ValueError("state does not belong to a run on these images")
+            else:
+                adam = [torch.empty(B, d, device=self.device) for d in dims for _ in range(4)]
+            bound = torch.empty(T, B, device=self.device) if "bound" in want and T > 0 else None
+            hs = [torch.empty(k, B, d, device=self.device) for d in dims] if "h" in want else []
+            lw = torch.empty(B, k, device=self.device) if "log_w" in want else None
+            lpx = torch.empty(B, device=self.device) if "logpx" in want else None
+            ess = torch.empty(B, device=self.device) if "ess" in want else None
+        cfg = _lib.IwaeRefineConfig(objective=0 if objective == "ELBO" else 1, n_iters=T, step0=step0, lr=float(lr),
+                                    beta1=float(betas[0]), beta2=float(betas[1]), epsilon=float(epsilon),
+                                    logstd_min=float(logstd_range[0]), logstd_max=float(logstd_range[1]))
+        marr, nm = _lib.fptr_array(mean)
+        sarr, _ = _lib.fptr_array(logstd)
+        aarr, na = _lib.fptr_array(adam)
+        harr, nh = _lib.fptr_array(hs)
+        self._call(self._lib.iwae_refine(self._h, _lib.fptr(xd), B, k, int(chunk), marr, sarr, nm, ctypes.byref(cfg),
+                                         earr, ne, aarr, na, _lib.fptr(bound), harr, nh, _lib.fptr(lw), _lib.fptr(lpx),
+                                         _lib.fptr(ess)))
+        out = {"mean": mean, "logstd": logstd, "state": {"adam": adam, "step": step0 + T}}
+        with torch.cuda.stream(self._stream):
+            if "bound" in want:
+                out["bound"] = bound if bound is not None else torch.empty(0, B, device=self.device)
+            if lw is not None:
+                out["log_w"] = lw.t().contiguous()
+            if lpx is not None:
+                out["logpx"] = lpx
+            if ess is not None:
+                out["ess"] = ess
+            if hs:
+                out["h"] = hs
+        self._stream.synchronize()
+        return out
+
     def _encode(self, x, n_samples, eps=None, chunk=0):
         """iwae_encode behind ``model.encoder(x, n_samples)``."""
         xd = self._x(x)
