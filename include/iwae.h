@@ -182,6 +182,19 @@ enum iwae_knob {
      cost-model terms); iwae_set_tuning rejects them with IWAE_EINVAL */
 };
 int iwae_set_tuning(iwae_handle* h, int knob, long long value);
+/* Store policy of what a launch leaves to later launches, a bit mask (default
+ * 5).  A launch's end writes back whatever its stores left dirty in the L2s,
+ * and the next launch waits for it.  Bit 1: the forward, bit 2: the backward
+ * 16-row engine launch store write-through (sc1); bit 4: the fused update's
+ * sample-row tiles, bit 8: its one-iteration tiles too; bit 16: a sample-row
+ * tile's workgroup, bit 32: the forward's job E / O1 workgroups, which end
+ * before the launch does, write their XCD's L2 back as their last act
+ * (agent-scope release).  16-row engine plans and the fused / combined update
+ * routes only; results do not change by a bit.  Measured at B = 20, k = 50:
+ * bits 1 and 4 win, the others lose.  Like a tuning knob (and not
+ * one of the enum only because that list is closed): for A/B measurements and
+ * tests; setting it drops the handle's captured graphs and engine plans. */
+int iwae_set_store_policy(iwae_handle* h, int mask);
 /* Matrix-product precision of the tiled GEMM kernels: 1 (default) bf16x3 --
  * a.b = a_hi b_hi + a_hi b_lo + a_lo b_hi with hi = bf16(x), lo = bf16(x - hi),
  * f32 accumulate on v_mfma_f32_16x16x32_bf16 (the engine, ring, update and

@@ -82,6 +82,7 @@ SIGNATURES = {
     "iwae_set_path": (c_int, [H, c_int]),
     "iwae_set_precision": (c_int, [H, c_int]),
     "iwae_set_tuning": (c_int, [H, c_int, c_longlong]),
+    "iwae_set_store_policy": (c_int, [H, c_int]),
     "iwae_num_params": (c_longlong, [H]),
     "iwae_set_params": (c_int, [H, FP, c_longlong]),
     "iwae_get_params": (c_int, [H, FP, c_longlong]),

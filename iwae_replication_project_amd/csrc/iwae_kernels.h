@@ -426,7 +426,13 @@ struct UpdArgs {
   // back, then Adam and the FX / GX copies as usual
   int apply; const float* scale_dev;
   int waves;                                          // 4, or 8 (64-column tiles: two waves per SIMD)
+  // store policy (iwae_set_store_policy; the fused / combined routes only), kUpdSt* bits:
+  // the grad, m, v, param, FX and GX stores of the sample-row ("heavy": more than
+  // one reduction iteration) or one-iteration ("light") tiles write-through (sc1);
+  // a heavy tile's workgroup writes its XCD's L2 back as its last act
+  int st_wt;
 };
+constexpr int kUpdStHeavy = 1, kUpdStLight = 2, kUpdStRelease = 4;
 hipError_t launch_update(hipStream_t st, const UpdArgs& a);
 constexpr int kUpdRowsPerIter = 128;     // rows per reduction iteration of the update kernel (UP_RI)
 // in-launch wait of the update's first-encoder-layer tiles on the image-row
@@ -899,7 +905,8 @@ constexpr unsigned kTcKindsImgBwd = (1u << TC_TGRAD) | (1u << TC_LIN) | (1u << T
 constexpr unsigned kTcKindsImgFwd = (1u << TC_LOADSLAB) | (1u << TC_TANH) | (1u << TC_HEADP);
 // not an op kind: an engine instantiation whose activation / dZ stores are
 // write-through (sc1) -- job I' inside tcu_kernel, the producer side of the
-// write-through hand-off (UpdWait::wt)
+// write-through hand-off (UpdWait::wt) -- and, under the store policy
+// (TcArgs::st_wt), every global store of a 16-row forward / backward launch
 constexpr unsigned kTcWriteThrough = 1u << 31;
 struct TcArgs {
   const TcPlan* plan;
@@ -929,6 +936,12 @@ struct TcArgs {
   // workgroup bnd_block (the grid's last) runs the whole bound: log weights,
   // loss, global dlw / dpx, the Philox base and the Adam step
   BoundArgs bnd; int bnd_rows, bnd_block, bnd_ld, bnd_lds, bnd_stage;
+  // store policy (iwae_set_store_policy; 16-row plans only).  st_wt: launch_tc runs the
+  // write-through instantiation of the plan's kind set (every global store sc1).
+  // rel_jobs: the workgroups of these jobs (bit per job), which end well before
+  // the launch does, write their XCD's L2 back themselves as their last act
+  // (wg_release_l2), so the write-back at the launch's end finds less to do
+  int st_wt; unsigned rel_jobs;
 };
 hipError_t launch_tc(hipStream_t st, const TcArgs& a, int rt, size_t lds_bytes);
 // job I' (a one-job image-row plan, RT = 1) and the fused update (8 waves) in one launch

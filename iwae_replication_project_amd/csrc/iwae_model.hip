@@ -116,6 +116,8 @@ struct Tune {
   int tcu = 1;                       // job I' and the fused update in one launch (tcu_kernel) where it fits
   int tcu_wt = 1;                    // the combined launch's hand-off write-through (launch_tcu decides)
   int tcu_wait_test = 0;             // fault injection: every combined-launch wait gives up
+  int st_wt = 5;                     // store policy of what a launch leaves to later launches (iwae_set_store_policy bits;
+                                     // 1 + 4: B = 20 step 0.0977 -> 0.0957 ms, profiles/store_policy_ab.txt)
   int dw_wide = 1;                   // the slab pass run by the 208 x 128-block weight-gradient kernel (iwae_dwgrad.hip;
                                      // B = 512: 107 vs 152 us for the update kernel's pass, step 0.513 -> 0.473 ms)
   long long dw_target = 768;         // split-K target workgroups per layer of the grouped weight-gradient GEMMs
@@ -1839,7 +1841,12 @@ static int run_update(iwae_handle* h, const Plan& P, const UpdMode& mode) {
   a.state = &h->ds->adam;
   a.gscale = a.tail_val = 1.f;
   switch (mode.kind) {
-    case UpdMode::FUSED: a.do_adam = mode.adam ? 1 : 0; break;
+    case UpdMode::FUSED:
+      a.do_adam = mode.adam ? 1 : 0;
+      // store policy (bits 4, 8, 16 of the knob: heavy tiles, light tiles, the heavy tiles' release)
+      a.st_wt = ((h->tune.st_wt & 4) ? kUpdStHeavy : 0) | ((h->tune.st_wt & 8) ? kUpdStLight : 0) |
+                ((h->tune.st_wt & 16) ? kUpdStRelease : 0);
+      break;
     case UpdMode::DP_GRADS:
       a.gscale = a.tail_val = (float)P.B;
       a.tail = (mode.bucket & WG_OUT_ONLY) ? h->grad + h->nparam_int : nullptr;
@@ -2526,6 +2533,14 @@ static int tc_run(iwae_handle* h, const Plan& P, const EpsSet& E, TcLaunch which
   a.dlw = dlw ? dlw : h->dlw; a.dpx = dpx ? dpx : h->dpx; a.wa = P.wa;
   a.wb = P.wb; a.need_bce = P.need_bce;
   a.unit_w = unit ? 1 : 0;
+  if (rec.rt == 1) {
+    // store policy (16-row plans): bit 1 the forward launches, 2 the backward
+    // ones write-through; 32: the forward's jobs before its last (E and O1,
+    // which end before O2) write their XCD's L2 back as they end
+    const bool fwd = which == TCL_FWD || which == TCL_IMG_FWD;
+    a.st_wt = (h->tune.st_wt & (fwd ? 1 : 2)) != 0;
+    if (which == TCL_FWD && (h->tune.st_wt & 32) && njobs > 1) a.rel_jobs = (1u << (njobs - 1)) - 1u;
+  }
   a.bnd_block = -1;
   if (bnd) {
     // the bound in this (backward) launch: its rows' dL/dlw per workgroup, the
@@ -3484,6 +3499,17 @@ int iwae_set_tuning(iwae_handle* h, int knob, long long value) {
       break;
     default: return fail(h, IWAE_EINVAL, "unknown tuning knob " + std::to_string(knob));
   }
+  // captured steps and engine plans were built for the previous setting
+  invalidate_graphs(h);
+  invalidate_tc_plans(h);
+  return IWAE_OK;
+}
+
+int iwae_set_store_policy(iwae_handle* h, int mask) {
+  if (!h) return IWAE_EINVAL;
+  if (mask < 0 || mask > 63) return fail(h, IWAE_EINVAL, "store policy: a mask of bits 1 .. 32");
+  HIPCHK(hipStreamSynchronize(h->stream));
+  h->tune.st_wt = mask;
   // captured steps and engine plans were built for the previous setting
   invalidate_graphs(h);
   invalidate_tc_plans(h);

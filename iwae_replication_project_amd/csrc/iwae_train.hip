@@ -151,18 +151,21 @@ __device__ __forceinline__ void tc_put1(const TcBuf& B, int o, float v) {
 // workgroups (RT >= 2, large batches) store with sc1: the lines leave the
 // XCD's L2 instead of displacing the weight fragments every workgroup
 // re-reads from it (hundreds of MB of activations stream out per launch).
-// WT: the producer side of tcu_kernel's write-through hand-off (sc1 too).
+// WT: sc1 too -- the producer side of tcu_kernel's write-through hand-off, and
+// the 16-row launches under the store policy (iwae_set_store_policy): what a launch
+// leaves to later launches goes through to memory as it is stored, not in the
+// L2 write-back at the launch's end.
 // base must be wave-uniform; idx in floats.
 template <int RT, bool WT = false>
 __device__ __forceinline__ void tc_st4(float* base, size_t idx, float4 v) {
   const tc_u32x4 u = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
   __builtin_amdgcn_raw_buffer_store_b128(u, buf_rsrc(base), (unsigned)(idx * 4), 0, (RT >= 2 || WT) ? 16 : 0);
 }
-template <int RT>
+template <int RT, bool WT = false>
 __device__ __forceinline__ void tc_st2(float* base, size_t idx, float a, float b) {
   typedef unsigned tc_u32x2 __attribute__((ext_vector_type(2)));
   const tc_u32x2 u = {__float_as_uint(a), __float_as_uint(b)};
-  __builtin_amdgcn_raw_buffer_store_b64(u, buf_rsrc(base), (unsigned)(idx * 4), 0, RT >= 2 ? 16 : 0);
+  __builtin_amdgcn_raw_buffer_store_b64(u, buf_rsrc(base), (unsigned)(idx * 4), 0, (RT >= 2 || WT) ? 16 : 0);
 }
 template <int RT, bool WT = false>
 __device__ __forceinline__ void tc_st1(float* base, size_t idx, float a) {
@@ -350,7 +353,7 @@ __device__ __forceinline__ void tc_store_act(COp& S, const TcBuf& OUT, int t, co
 // Head epilogue (SAMPLE / PRIOR).  Lane groups g hold, for quad q = 2t + (g >> 1),
 // the mu quad (g even) or the zs quad (g odd); two v_permlane16_swap leave every
 // lane (mu, zs) of its own two latent columns j0, j0 + 1.
-template <int RT, int KIND>
+template <int RT, int KIND, bool WT = false>
 __device__ __forceinline__ void tc_head(const TcArgs& A, COp& S, const TcBuf& H, int t, uint64_t base,
                                         const tc_f32x4 (&acc)[RT], const float2 (&tv)[RT], TcRows<RT>& R, int row0,
                                         int nrows) {
@@ -392,20 +395,20 @@ __device__ __forceinline__ void tc_head(const TcArgs& A, COp& S, const TcBuf& H,
       // every row stride a multiple of 4 floats); a last odd column alone
       const size_t po = (size_t)grow * S.ld_out;
       if (st && j0 + 1 < d) {
-        tc_st2<RT>(S.h, (size_t)grow * S.ld_h + j0, hv[0], hv[1]);
-        tc_st2<RT>(S.eps, (size_t)grow * S.ld_eps + j0, e.x, e.y);
-        tc_st2<RT>(S.out, po + j0, mu[0], mu[1]);
+        tc_st2<RT, WT>(S.h, (size_t)grow * S.ld_h + j0, hv[0], hv[1]);
+        tc_st2<RT, WT>(S.eps, (size_t)grow * S.ld_eps + j0, e.x, e.y);
+        tc_st2<RT, WT>(S.out, po + j0, mu[0], mu[1]);
         if ((d & 1) == 0) {
-          tc_st2<RT>(S.out, po + d + j0, zs[0], zs[1]);
+          tc_st2<RT, WT>(S.out, po + d + j0, zs[0], zs[1]);
         } else {
-          tc_st1<RT>(S.out, po + d + j0, zs[0]);
-          tc_st1<RT>(S.out, po + d + j0 + 1, zs[1]);
+          tc_st1<RT, WT>(S.out, po + d + j0, zs[0]);
+          tc_st1<RT, WT>(S.out, po + d + j0 + 1, zs[1]);
         }
       } else if (st && j0 < d) {
-        tc_st1<RT>(S.h, (size_t)grow * S.ld_h + j0, hv[0]);
-        tc_st1<RT>(S.eps, (size_t)grow * S.ld_eps + j0, e.x);
-        tc_st1<RT>(S.out, po + j0, mu[0]);
-        tc_st1<RT>(S.out, po + d + j0, zs[0]);
+        tc_st1<RT, WT>(S.h, (size_t)grow * S.ld_h + j0, hv[0]);
+        tc_st1<RT, WT>(S.eps, (size_t)grow * S.ld_eps + j0, e.x);
+        tc_st1<RT, WT>(S.out, po + j0, mu[0]);
+        tc_st1<RT, WT>(S.out, po + d + j0, zs[0]);
       }
       tc_put1(H, row * H.ld + j0, hv[0]);
       tc_put1(H, row * H.ld + j0 + 1, hv[1]);
@@ -419,16 +422,16 @@ __device__ __forceinline__ void tc_head(const TcArgs& A, COp& S, const TcBuf& H,
       }
       const size_t po = (size_t)grow * S.ld_out;
       if (st && Pr && j0 + 1 < d) {
-        tc_st2<RT>(S.out, po + j0, mu[0], mu[1]);
+        tc_st2<RT, WT>(S.out, po + j0, mu[0], mu[1]);
         if ((d & 1) == 0) {
-          tc_st2<RT>(S.out, po + d + j0, zs[0], zs[1]);
+          tc_st2<RT, WT>(S.out, po + d + j0, zs[0], zs[1]);
         } else {
-          tc_st1<RT>(S.out, po + d + j0, zs[0]);
-          tc_st1<RT>(S.out, po + d + j0 + 1, zs[1]);
+          tc_st1<RT, WT>(S.out, po + d + j0, zs[0]);
+          tc_st1<RT, WT>(S.out, po + d + j0 + 1, zs[1]);
         }
       } else if (st && Pr && j0 < d) {
-        tc_st1<RT>(S.out, po + j0, mu[0]);
-        tc_st1<RT>(S.out, po + d + j0, zs[0]);
+        tc_st1<RT, WT>(S.out, po + j0, mu[0]);
+        tc_st1<RT, WT>(S.out, po + d + j0, zs[0]);
       }
     }
     __builtin_amdgcn_sched_barrier(0);     // one row tile at a time (register pressure)
@@ -440,7 +443,7 @@ __device__ __forceinline__ void tc_head(const TcArgs& A, COp& S, const TcBuf& H,
 // backward pass.  Binarised pixels: the selected probability is
 // sigmoid(+-l) * c + (x ? 1e-7 : 1 - c - 1e-7) (no f32 cancellation), four of
 // them multiplied before one log2.
-template <int RT>
+template <int RT, bool WT = false>
 __device__ __forceinline__ void tc_bern(const TcArgs& A, COp& S, int t, const tc_f32x4 (&acc)[RT],
                                         const float4 (&xv)[RT], TcRows<RT>& R, int row0, int nrows) {
   const int lane = threadIdx.x & 63;
@@ -513,11 +516,11 @@ __device__ __forceinline__ void tc_bern(const TcArgs& A, COp& S, int t, const tc
 #endif
       const size_t o = (size_t)(row0 + row) * S.ld_out + f0;
       if (f0 + 3 < S.N) {
-        tc_st4<RT>(S.out, o, make_float4(gv[0], gv[1], gv[2], gv[3]));
+        tc_st4<RT, WT>(S.out, o, make_float4(gv[0], gv[1], gv[2], gv[3]));
       } else {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-          if (f0 + i < S.N) tc_st1<RT>(S.out, o + i, gv[i]);
+          if (f0 + i < S.N) tc_st1<RT, WT>(S.out, o + i, gv[i]);
       }
     }
   }
@@ -612,8 +615,8 @@ __device__ __forceinline__ void tc_epilogue(const TcArgs& A, COp& S, const TcBuf
                                             const float2 (&tv)[RT], TcRows<RT>& R, int row0, int nrows) {
   if (KIND == TC_TANH || KIND == TC_TGRAD || KIND == TC_LIN)
     tc_store_act<RT, KIND, WT>(S, OUT, t, acc, ov, row0, nrows);
-  else if (KIND == TC_BERN) tc_bern<RT>(A, S, t, acc, ov, R, row0, nrows);
-  else tc_head<RT, KIND>(A, S, OUT, t, base, acc, tv, R, row0, nrows);
+  else if (KIND == TC_BERN) tc_bern<RT, WT>(A, S, t, acc, ov, R, row0, nrows);
+  else tc_head<RT, KIND, WT>(A, S, OUT, t, base, acc, tv, R, row0, nrows);
 }
 
 // Weight-fragment pipeline.  Four register sets with fixed roles: X holds
@@ -729,13 +732,13 @@ __device__ __forceinline__ int tc_dense(const TcArgs& A, COp& S, const TcHot& H,
     if (x.last) {
 #endif
       switch (kind) {
-        case TC_TANH: if constexpr ((KM >> TC_TANH) & 1u) tc_epilogue<RT, TC_TANH>(A, S, OUT, x.t, base, acc, ov, tv, R, row0, nrows); break;
+        case TC_TANH: if constexpr ((KM >> TC_TANH) & 1u) tc_epilogue<RT, TC_TANH, (KM & kTcWriteThrough) != 0>(A, S, OUT, x.t, base, acc, ov, tv, R, row0, nrows); break;
         case TC_TGRAD: if constexpr ((KM >> TC_TGRAD) & 1u) tc_epilogue<RT, TC_TGRAD, (KM & kTcWriteThrough) != 0>(A, S, OUT, x.t, base, acc, ov, tv, R, row0, nrows); break;
         case TC_LIN: if constexpr ((KM >> TC_LIN) & 1u) tc_epilogue<RT, TC_LIN, (KM & kTcWriteThrough) != 0>(A, S, OUT, x.t, base, acc, ov, tv, R, row0, nrows); break;
-        case TC_BERN: if constexpr ((KM >> TC_BERN) & 1u) tc_epilogue<RT, TC_BERN>(A, S, OUT, x.t, base, acc, ov, tv, R, row0, nrows); break;
-        case TC_SAMPLE: if constexpr ((KM >> TC_SAMPLE) & 1u) tc_epilogue<RT, TC_SAMPLE>(A, S, OUT, x.t, base, acc, ov, tv, R, row0, nrows); break;
-        case TC_HEADP: if constexpr ((KM >> TC_HEADP) & 1u) tc_epilogue<RT, TC_HEADP>(A, S, OUT, x.t, base, acc, ov, tv, R, row0, nrows); break;
-        default: if constexpr ((KM >> TC_PRIOR) & 1u) tc_epilogue<RT, TC_PRIOR>(A, S, OUT, x.t, base, acc, ov, tv, R, row0, nrows); break;
+        case TC_BERN: if constexpr ((KM >> TC_BERN) & 1u) tc_epilogue<RT, TC_BERN, (KM & kTcWriteThrough) != 0>(A, S, OUT, x.t, base, acc, ov, tv, R, row0, nrows); break;
+        case TC_SAMPLE: if constexpr ((KM >> TC_SAMPLE) & 1u) tc_epilogue<RT, TC_SAMPLE, (KM & kTcWriteThrough) != 0>(A, S, OUT, x.t, base, acc, ov, tv, R, row0, nrows); break;
+        case TC_HEADP: if constexpr ((KM >> TC_HEADP) & 1u) tc_epilogue<RT, TC_HEADP, (KM & kTcWriteThrough) != 0>(A, S, OUT, x.t, base, acc, ov, tv, R, row0, nrows); break;
+        default: if constexpr ((KM >> TC_PRIOR) & 1u) tc_epilogue<RT, TC_PRIOR, (KM & kTcWriteThrough) != 0>(A, S, OUT, x.t, base, acc, ov, tv, R, row0, nrows); break;
       }
     }
 #ifdef IWAE_TC_TRACE
@@ -797,13 +800,13 @@ __device__ __forceinline__ void tc_dense2(const TcArgs& A, COp& S, const TcHot& 
     tc_next(ci, q.nch);
     if (x.last) {
       switch (kind) {
-        case TC_TANH: if constexpr ((KM >> TC_TANH) & 1u) tc_epilogue<RT, TC_TANH>(A, S, OUT, x.t, base, acc, ov, tv, R, row0, nrows); break;
+        case TC_TANH: if constexpr ((KM >> TC_TANH) & 1u) tc_epilogue<RT, TC_TANH, (KM & kTcWriteThrough) != 0>(A, S, OUT, x.t, base, acc, ov, tv, R, row0, nrows); break;
         case TC_TGRAD: if constexpr ((KM >> TC_TGRAD) & 1u) tc_epilogue<RT, TC_TGRAD, (KM & kTcWriteThrough) != 0>(A, S, OUT, x.t, base, acc, ov, tv, R, row0, nrows); break;
         case TC_LIN: if constexpr ((KM >> TC_LIN) & 1u) tc_epilogue<RT, TC_LIN, (KM & kTcWriteThrough) != 0>(A, S, OUT, x.t, base, acc, ov, tv, R, row0, nrows); break;
-        case TC_BERN: if constexpr ((KM >> TC_BERN) & 1u) tc_epilogue<RT, TC_BERN>(A, S, OUT, x.t, base, acc, ov, tv, R, row0, nrows); break;
-        case TC_SAMPLE: if constexpr ((KM >> TC_SAMPLE) & 1u) tc_epilogue<RT, TC_SAMPLE>(A, S, OUT, x.t, base, acc, ov, tv, R, row0, nrows); break;
-        case TC_HEADP: if constexpr ((KM >> TC_HEADP) & 1u) tc_epilogue<RT, TC_HEADP>(A, S, OUT, x.t, base, acc, ov, tv, R, row0, nrows); break;
-        default: if constexpr ((KM >> TC_PRIOR) & 1u) tc_epilogue<RT, TC_PRIOR>(A, S, OUT, x.t, base, acc, ov, tv, R, row0, nrows); break;
+        case TC_BERN: if constexpr ((KM >> TC_BERN) & 1u) tc_epilogue<RT, TC_BERN, (KM & kTcWriteThrough) != 0>(A, S, OUT, x.t, base, acc, ov, tv, R, row0, nrows); break;
+        case TC_SAMPLE: if constexpr ((KM >> TC_SAMPLE) & 1u) tc_epilogue<RT, TC_SAMPLE, (KM & kTcWriteThrough) != 0>(A, S, OUT, x.t, base, acc, ov, tv, R, row0, nrows); break;
+        case TC_HEADP: if constexpr ((KM >> TC_HEADP) & 1u) tc_epilogue<RT, TC_HEADP, (KM & kTcWriteThrough) != 0>(A, S, OUT, x.t, base, acc, ov, tv, R, row0, nrows); break;
+        default: if constexpr ((KM >> TC_PRIOR) & 1u) tc_epilogue<RT, TC_PRIOR, (KM & kTcWriteThrough) != 0>(A, S, OUT, x.t, base, acc, ov, tv, R, row0, nrows); break;
       }
     }
   };
@@ -832,7 +835,7 @@ __device__ __forceinline__ void tc_lds_barrier() {
 // h1 = eps * scale + mu of the row's image (Encoder.call F:58-F:60), log q(h1|x)
 // and log N(h1; 0, 1) into the row accumulators, h1 into out_buf (ones column
 // at d, zeros to next_k); h1 / eps stored when S.h is set.
-template <int RT>
+template <int RT, bool WT = false>
 __device__ __forceinline__ void tc_sample0(const TcArgs& A, CJob& J, COp& S, uint64_t base, int row0,
                                            int nrows, float* rq, float* rp) {
   constexpr int R = 16 * RT, TPR = (TC_NW * 64) / R;
@@ -891,14 +894,14 @@ __device__ __forceinline__ void tc_sample0(const TcArgs& A, CJob& J, COp& S, uin
         }
       }
       if (st && 4 * gq + 3 < d) {
-        tc_st4<RT>(S.h, (size_t)rg * S.ld_h + 4 * gq, make_float4(hv[0], hv[1], hv[2], hv[3]));
-        tc_st4<RT>(S.eps, (size_t)rg * S.ld_eps + 4 * gq, e4);
+        tc_st4<RT, WT>(S.h, (size_t)rg * S.ld_h + 4 * gq, make_float4(hv[0], hv[1], hv[2], hv[3]));
+        tc_st4<RT, WT>(S.eps, (size_t)rg * S.ld_eps + 4 * gq, e4);
       } else if (st) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           if (4 * gq + q < d) {
-            tc_st1<RT>(S.h, (size_t)rg * S.ld_h + 4 * gq + q, hv[q]);
-            tc_st1<RT>(S.eps, (size_t)rg * S.ld_eps + 4 * gq + q, ev[q]);
+            tc_st1<RT, WT>(S.h, (size_t)rg * S.ld_h + 4 * gq + q, hv[q]);
+            tc_st1<RT, WT>(S.eps, (size_t)rg * S.ld_eps + 4 * gq + q, ev[q]);
           }
         }
       }
@@ -942,7 +945,7 @@ __device__ __forceinline__ void tc_loadg(const TcArgs& A, CJob& J, COp& S, int r
 //   GBWD_ENC:   sampled h = eps s + mu, dL/dlogq = -dlw, G = sum of the dL/dh
 //               sources (+ dlw * d log N(h; 0, 1)/dh for the top layer):
 //               dmu = G + dlq z / s, dscale = G eps + dlq (z^2 - 1) / s.
-template <int RT, int KIND>
+template <int RT, int KIND, bool WT = false>
 __device__ __forceinline__ void tc_gbwd(const TcArgs& A, CJob& J, COp& S, int row0, int nrows) {
   constexpr int R = 16 * RT, TPR = (TC_NW * 64) / R;
   const int t = threadIdx.x, rr = t / TPR, sub = t - rr * TPR;
@@ -987,7 +990,7 @@ __device__ __forceinline__ void tc_gbwd(const TcArgs& A, CJob& J, COp& S, int ro
       const float z = hv[q] * rs - mu[q] * rs;
       float dmu, dsc;
       if (KIND == TC_GBWD_PRIOR) {
-        if (st) tc_st1<RT>(S.dh, (size_t)rg * S.ld_dh + c, dl * (-z * rs));
+        if (st) tc_st1<RT, WT>(S.dh, (size_t)rg * S.ld_dh + c, dl * (-z * rs));
         dmu = dl * (z * rs);
         dsc = dl * ((z * z - 1.f) * rs);
       } else {
@@ -1002,8 +1005,8 @@ __device__ __forceinline__ void tc_gbwd(const TcArgs& A, CJob& J, COp& S, int ro
       tc_put1(B, rr * B.ld + c, dmu);
       tc_put1(B, rr * B.ld + d + c, dzs);
       if (st && S.out) {
-        tc_st1<RT>(S.out, (size_t)rg * S.ld_out + c, dmu);
-        tc_st1<RT>(S.out, (size_t)rg * S.ld_out + d + c, dzs);
+        tc_st1<RT, WT>(S.out, (size_t)rg * S.ld_out + c, dmu);
+        tc_st1<RT, WT>(S.out, (size_t)rg * S.ld_out + d + c, dzs);
       }
     }
   }
@@ -1012,7 +1015,7 @@ __device__ __forceinline__ void tc_gbwd(const TcArgs& A, CJob& J, COp& S, int ro
 // Image rows (the first encoder layer, after its split-K input Dense):
 // y1 = tanh(sum of the partial slabs) into out_buf (ones column at N, zeros to
 // next_k) and S.out.  Every slab load of a quad is issued before the sum.
-template <int RT>
+template <int RT, bool WT = false>
 __device__ __forceinline__ void tc_loadslab(CJob& J, COp& S, int row0, int nrows) {
   constexpr int R = 16 * RT, TPR = (TC_NW * 64) / R;
   constexpr int kMaxSlab = 4;
@@ -1038,7 +1041,10 @@ __device__ __forceinline__ void tc_loadslab(CJob& J, COp& S, int row0, int nrows
     for (int i = 0; i < 4; ++i) {
       const int c = k + i;
       v[i] = c < S.N ? ftanh(v[i]) : (c == S.N ? 1.f : 0.f);
-      if (st && c < S.N) S.out[(size_t)rg * S.ld_out + c] = v[i];
+      if (st && c < S.N) {
+        if constexpr (WT) tc_st1<1, true>(S.out, (size_t)rg * S.ld_out + c, v[i]);
+        else S.out[(size_t)rg * S.ld_out + c] = v[i];
+      }
     }
     tc_put4(B, rr * B.ld + k, v);
   }
@@ -1173,6 +1179,7 @@ __device__ __forceinline__ void tc_gbwd0(const TcArgs& A, CJob& J, COp& S, int r
 template <int RT, unsigned KM = kTcKindsAll>
 __device__ __forceinline__ void tc_body(const TcArgs& A, const int bid) {
   constexpr int R = 16 * RT;
+  constexpr bool WT = (KM & kTcWriteThrough) != 0;
   CPlan* plan = (CPlan*)A.plan;
   if (bid == A.bnd_block) {
     // the step's bound (bound_kernel's work in this launch's spare workgroup)
@@ -1294,12 +1301,12 @@ __device__ __forceinline__ void tc_body(const TcArgs& A, const int bid) {
 #ifdef IWAE_TC_SKIPELEM    // timing experiment only
       default: break;
 #else
-      case TC_SAMPLE0: if constexpr ((KM >> TC_SAMPLE0) & 1u) tc_sample0<RT>(A, J, S, base, row0, nrows, rq, rp); break;
-      case TC_GBWD_PRIOR: if constexpr ((KM >> TC_GBWD_PRIOR) & 1u) tc_gbwd<RT, TC_GBWD_PRIOR>(A, J, S, row0, nrows); break;
-      case TC_GBWD_ENC: if constexpr ((KM >> TC_GBWD_ENC) & 1u) tc_gbwd<RT, TC_GBWD_ENC>(A, J, S, row0, nrows); break;
+      case TC_SAMPLE0: if constexpr ((KM >> TC_SAMPLE0) & 1u) tc_sample0<RT, WT>(A, J, S, base, row0, nrows, rq, rp); break;
+      case TC_GBWD_PRIOR: if constexpr ((KM >> TC_GBWD_PRIOR) & 1u) tc_gbwd<RT, TC_GBWD_PRIOR, WT>(A, J, S, row0, nrows); break;
+      case TC_GBWD_ENC: if constexpr ((KM >> TC_GBWD_ENC) & 1u) tc_gbwd<RT, TC_GBWD_ENC, WT>(A, J, S, row0, nrows); break;
       case TC_LOADG: if constexpr ((KM >> TC_LOADG) & 1u) tc_loadg<RT>(A, J, S, row0, nrows); break;
-      case TC_LOADSLAB: if constexpr ((KM >> TC_LOADSLAB) & 1u) tc_loadslab<RT>(J, S, r0, nr); break;
-      default: if constexpr ((KM >> TC_GBWD0) & 1u) tc_gbwd0<RT, (KM & kTcWriteThrough) != 0>(A, J, S, row0, nrows); break;
+      case TC_LOADSLAB: if constexpr ((KM >> TC_LOADSLAB) & 1u) tc_loadslab<RT, WT>(J, S, r0, nr); break;
+      default: if constexpr ((KM >> TC_GBWD0) & 1u) tc_gbwd0<RT, WT>(A, J, S, row0, nrows); break;
 #endif
     }
 #ifdef IWAE_TC_TRACE
@@ -1310,7 +1317,11 @@ __device__ __forceinline__ void tc_body(const TcArgs& A, const int bid) {
     else tc_lds_barrier();
     H = Hn;
   }
-  if (!J.logq && !J.logp && !J.bern) return;
+  const bool early = ((A.rel_jobs >> jb) & 1u) != 0;
+  if (!J.logq && !J.logp && !J.bern) {
+    if (early) wg_release_l2();
+    return;
+  }
   // per-row sums: over the 4 lane groups, then over the waves (fixed order)
   {
     const int r = lane & 15, g = lane >> 4;
@@ -1333,18 +1344,31 @@ __device__ __forceinline__ void tc_body(const TcArgs& A, const int bid) {
 #pragma unroll
       for (int w = 0; w < TC_NW; ++w) s4[k] += red[(k * TC_NW + w) * R + t];
     const int rg = row0 + t;
-    if (J.logq) J.logq[rg] = rq[t] + s4[0];
-    if (J.logp) J.logp[rg] = rp[t] + s4[1];
     // the bound sums columns 0-1 of a row: a single-split job clears column 1,
     // which a split launch of another (smaller) shape may have written earlier
-    if (J.bern_ncol == 1) {
-      if (J.bern) *reinterpret_cast<float2*>(J.bern + (size_t)rg * J.ld_bern) = make_float2(kLn2 * s4[2], 0.f);
-      if (J.bce) *reinterpret_cast<float2*>(J.bce + (size_t)rg * J.ld_bern) = make_float2(kLn2 * s4[3], 0.f);
+    if constexpr (WT) {
+      if (J.logq) tc_st1<1, true>(J.logq, (size_t)rg, rq[t] + s4[0]);
+      if (J.logp) tc_st1<1, true>(J.logp, (size_t)rg, rp[t] + s4[1]);
+      if (J.bern_ncol == 1) {
+        if (J.bern) tc_st2<1, true>(J.bern, (size_t)rg * J.ld_bern, kLn2 * s4[2], 0.f);
+        if (J.bce) tc_st2<1, true>(J.bce, (size_t)rg * J.ld_bern, kLn2 * s4[3], 0.f);
+      } else {
+        if (J.bern) tc_st1<1, true>(J.bern, (size_t)rg * J.ld_bern + J.bern_col, kLn2 * s4[2]);
+        if (J.bce) tc_st1<1, true>(J.bce, (size_t)rg * J.ld_bern + J.bern_col, kLn2 * s4[3]);
+      }
     } else {
-      if (J.bern) J.bern[(size_t)rg * J.ld_bern + J.bern_col] = kLn2 * s4[2];
-      if (J.bce) J.bce[(size_t)rg * J.ld_bern + J.bern_col] = kLn2 * s4[3];
+      if (J.logq) J.logq[rg] = rq[t] + s4[0];
+      if (J.logp) J.logp[rg] = rp[t] + s4[1];
+      if (J.bern_ncol == 1) {
+        if (J.bern) *reinterpret_cast<float2*>(J.bern + (size_t)rg * J.ld_bern) = make_float2(kLn2 * s4[2], 0.f);
+        if (J.bce) *reinterpret_cast<float2*>(J.bce + (size_t)rg * J.ld_bern) = make_float2(kLn2 * s4[3], 0.f);
+      } else {
+        if (J.bern) J.bern[(size_t)rg * J.ld_bern + J.bern_col] = kLn2 * s4[2];
+        if (J.bce) J.bce[(size_t)rg * J.ld_bern + J.bern_col] = kLn2 * s4[3];
+      }
     }
   }
+  if (early) wg_release_l2();
 }
 
 template <int RT, unsigned KM>
@@ -1430,6 +1454,21 @@ hipError_t launch_tc(hipStream_t st, const TcArgs& a, int rt, size_t lds_bytes) 
   else if (km == 2) hipLaunchKernelGGL((tc_kernel<R, kTcKindsBwd>), dim3(nb), dim3(TC_NW * 64), lds_bytes, st, a); \
   else hipLaunchKernelGGL((tc_kernel<R, kTcKindsAll>), dim3(nb), dim3(TC_NW * 64), lds_bytes, st, a);
   const bool cov = IWAE_TC_KM && a.kinds;
+  // store policy (TcArgs::st_wt, 16-row plans): the same kind sets with every
+  // global store write-through (the aux value is an immediate: an instantiation bit)
+  if (rt == 1 && a.st_wt && cov) {
+    constexpr unsigned W = kTcWriteThrough;
+    if (IWAE_TC_NARROW && !(a.kinds & ~kTcKindsBwdRows))
+      hipLaunchKernelGGL((tc_kernel<1, kTcKindsBwdRows | W>), dim3(nb), dim3(TC_NW * 64), lds_bytes, st, a);
+    else if (IWAE_TC_NARROW && !(a.kinds & ~kTcKindsImgBwd))
+      hipLaunchKernelGGL((tc_kernel<1, kTcKindsImgBwd | W>), dim3(nb), dim3(TC_NW * 64), lds_bytes, st, a);
+    else if (IWAE_TC_NARROW && !(a.kinds & ~kTcKindsImgFwd))
+      hipLaunchKernelGGL((tc_kernel<1, kTcKindsImgFwd | W>), dim3(nb), dim3(TC_NW * 64), lds_bytes, st, a);
+    else if (km == 1) hipLaunchKernelGGL((tc_kernel<1, kTcKindsFwd | W>), dim3(nb), dim3(TC_NW * 64), lds_bytes, st, a);
+    else if (km == 2) hipLaunchKernelGGL((tc_kernel<1, kTcKindsBwd | W>), dim3(nb), dim3(TC_NW * 64), lds_bytes, st, a);
+    else hipLaunchKernelGGL((tc_kernel<1, kTcKindsAll>), dim3(nb), dim3(TC_NW * 64), lds_bytes, st, a);
+    return hipGetLastError();
+  }
   switch (rt) {
     case 1:
       // (no narrower sample-row forward set: without the folded image-row ops the
@@ -1459,7 +1498,12 @@ hipError_t tc_setup_attributes() {
                        (const void*)tc_kernel<1, kTcKindsBwd>, (const void*)tc_kernel<2, kTcKindsBwd>,
                        (const void*)tc_kernel<4, kTcKindsBwd>, (const void*)tcu_kernel<kTcKindsAll>,
                        (const void*)tcu_kernel<kTcKindsBwd>, (const void*)tc_kernel<1, kTcKindsBwdRows>, (const void*)tc_kernel<1, kTcKindsImgBwd>,
-                       (const void*)tcu_kernel<kTcKindsImgBwd | kTcWriteThrough>, (const void*)tc_kernel<1, kTcKindsImgFwd>};
+                       (const void*)tcu_kernel<kTcKindsImgBwd | kTcWriteThrough>, (const void*)tc_kernel<1, kTcKindsImgFwd>,
+                       (const void*)tc_kernel<1, kTcKindsFwd | kTcWriteThrough>,
+                       (const void*)tc_kernel<1, kTcKindsBwd | kTcWriteThrough>,
+                       (const void*)tc_kernel<1, kTcKindsBwdRows | kTcWriteThrough>,
+                       (const void*)tc_kernel<1, kTcKindsImgBwd | kTcWriteThrough>,
+                       (const void*)tc_kernel<1, kTcKindsImgFwd | kTcWriteThrough>};
   for (const void* f : fns) {
     const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;

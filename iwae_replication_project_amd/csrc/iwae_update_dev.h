@@ -69,6 +69,27 @@ __device__ __forceinline__ up_f32x4 up_ld4(__amdgpu_buffer_rsrc_t r, unsigned of
 __device__ __forceinline__ up_f32x4 up_ld4_sc1(__amdgpu_buffer_rsrc_t r, unsigned off) {
   return __builtin_bit_cast(up_f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 16));
 }
+// 16-byte store at byte offset off of a wave-uniform base; wt: write-through
+// (sc1: the line goes to memory now and leaves the XCD's L2, so the L2
+// write-back at the launch's end has nothing to do for it), else a plain store
+__device__ __forceinline__ void up_st16(void* base, unsigned off, up_u32x4 v, bool wt) {
+  if (wt) __builtin_amdgcn_raw_buffer_store_b128(v, buf_rsrc(base), off, 0, 16);
+  else *reinterpret_cast<up_u32x4*>(reinterpret_cast<char*>(base) + off) = v;
+}
+__device__ __forceinline__ up_u32x4 up_bits(float a, float b, float c, float d) {
+  return up_u32x4{__float_as_uint(a), __float_as_uint(b), __float_as_uint(c), __float_as_uint(d)};
+}
+// Last act of a workgroup that ends well before its launch does: every wave's
+// stores drained, then one agent-scope release, which writes the XCD's dirty L2
+// lines back -- beside the workgroups still running, not in the launch's end.
+__device__ __forceinline__ void wg_release_l2() {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+}
 __device__ __forceinline__ up_f32x2 up_ld2(__amdgpu_buffer_rsrc_t r, unsigned off) {
   return __builtin_bit_cast(up_f32x2, __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, 0));
 }
@@ -302,6 +323,10 @@ __device__ __forceinline__ void upd_tile(const UpdArgs& a, const UpdJob& J, cons
   // the last row are unconditional out-of-range reads of zeros
   // (apply mode: no reduction, the gradient comes from the buffer)
   const int ngrp = ((kUpdAblate & 64) || a.apply) ? 0 : (J.rows + UP_G * UP_RI - 1) / (UP_G * UP_RI);
+  // store policy of this tile's class (uniform over the workgroup)
+  const bool light = ngrp == 1 && J.rows <= UP_RI;
+  const bool wt = (a.st_wt & (light ? kUpdStLight : kUpdStHeavy)) != 0;
+  const bool release = !light && (a.st_wt & kUpdStRelease) != 0;
   float* buf0 = ups;
   float* buf1 = ups + UP_BUF;
   const UpOff O = up_offsets<TN, NW>(J, i0, j0);
@@ -476,10 +501,13 @@ __device__ __forceinline__ void upd_tile(const UpdArgs& a, const UpdJob& J, cons
   for (int q = 0; q < EJ / 4; ++q) {
     const int c = j0 + ej + 4 * q;
     if (erow && c < J.ldw)
-      *reinterpret_cast<float4*>(a.grad + J.off + (long long)(i0 + ei) * J.ldw + c) =
-          make_float4(wsc * g[4 * q], wsc * g[4 * q + 1], wsc * g[4 * q + 2], wsc * g[4 * q + 3]);
+      up_st16(a.grad + J.off, (unsigned)((i0 + ei) * J.ldw + c) * 4u,
+              up_bits(wsc * g[4 * q], wsc * g[4 * q + 1], wsc * g[4 * q + 2], wsc * g[4 * q + 3]), wt);
   }
-  if (!a.do_adam || (kUpdAblate & 32)) return;
+  if (!a.do_adam || (kUpdAblate & 32)) {
+    if (release) wg_release_l2();
+    return;
+  }
 
   // Adam (adam_kernel's arithmetic)
   const float tt = (float)st.t;
@@ -501,14 +529,17 @@ __device__ __forceinline__ void upd_tile(const UpdArgs& a, const UpdJob& J, cons
     }
     const int c = j0 + ej + 4 * q;
     if (erow && c < J.ldw) {
-      const long long o = J.off + (long long)(i0 + ei) * J.ldw + c;
-      *reinterpret_cast<float4*>(a.m + o) = make_float4(mq[0], mq[1], mq[2], mq[3]);
-      *reinterpret_cast<float4*>(a.v + o) = make_float4(vq[0], vq[1], vq[2], vq[3]);
-      *reinterpret_cast<float4*>(a.param + o) = make_float4(pq[0], pq[1], pq[2], pq[3]);
+      const unsigned o = (unsigned)((i0 + ei) * J.ldw + c) * 4u;
+      up_st16(a.m + J.off, o, up_bits(mq[0], mq[1], mq[2], mq[3]), wt);
+      up_st16(a.v + J.off, o, up_bits(vq[0], vq[1], vq[2], vq[3]), wt);
+      up_st16(a.param + J.off, o, up_bits(pq[0], pq[1], pq[2], pq[3]), wt);
     }
     *reinterpret_cast<float4*>(pw + ei * PS + ej + 4 * q) = make_float4(pq[0], pq[1], pq[2], pq[3]);
   }
-  if (J.fx_off < 0 || (kUpdAblate & 16)) return;   // no fragment-major copies (the f32 input layer)
+  if (J.fx_off < 0 || (kUpdAblate & 16)) {         // no fragment-major copies (the f32 input layer)
+    if (release) wg_release_l2();
+    return;
+  }
   __syncthreads();
   // FX chunks: (feature jj, 8 W_aug rows 8 ib ..) -> lane (pos & 15) + 16 ((k % 32) / 8) of step k / 32
 #pragma unroll
@@ -525,10 +556,9 @@ __device__ __forceinline__ void upd_tile(const UpdArgs& a, const UpdJob& J, cons
         vl[q] = (__bf16)(v - (float)h);
       }
       const int n = up_fx_pos(j, J.head_d);
-      const long long o = J.fx_off +
-          ((long long)((n >> 4) * J.fx_steps + (k0 >> 5)) * 64 + (n & 15) + 16 * ((k0 & 31) >> 3)) * 8;
-      *reinterpret_cast<up_bf16x8*>(a.fx_hi + o) = vh;
-      *reinterpret_cast<up_bf16x8*>(a.fx_lo + o) = vl;
+      const unsigned o = (unsigned)((((n >> 4) * J.fx_steps + (k0 >> 5)) * 64 + (n & 15) + 16 * ((k0 & 31) >> 3)) * 8) * 2u;
+      up_st16(a.fx_hi + J.fx_off, o, __builtin_bit_cast(up_u32x4, vh), wt);
+      up_st16(a.fx_lo + J.fx_off, o, __builtin_bit_cast(up_u32x4, vl), wt);
     }
   }
   // GX chunks: (input feature ii < fin, 8 outputs 8 jb ..)
@@ -545,12 +575,12 @@ __device__ __forceinline__ void upd_tile(const UpdArgs& a, const UpdJob& J, cons
         vh[q] = h;
         vl[q] = (__bf16)(v - (float)h);
       }
-      const long long o = J.gx_off +
-          ((long long)((n >> 4) * J.gx_steps + (k0 >> 5)) * 64 + (n & 15) + 16 * ((k0 & 31) >> 3)) * 8;
-      *reinterpret_cast<up_bf16x8*>(a.fx_hi + o) = vh;
-      *reinterpret_cast<up_bf16x8*>(a.fx_lo + o) = vl;
+      const unsigned o = (unsigned)((((n >> 4) * J.gx_steps + (k0 >> 5)) * 64 + (n & 15) + 16 * ((k0 & 31) >> 3)) * 8) * 2u;
+      up_st16(a.fx_hi + J.gx_off, o, __builtin_bit_cast(up_u32x4, vh), wt);
+      up_st16(a.fx_lo + J.gx_off, o, __builtin_bit_cast(up_u32x4, vl), wt);
     }
   }
+  if (release) wg_release_l2();
 }
 
 // Optional in-launch dependency (tcu_kernel, iwae_train.hip): the tiles of the

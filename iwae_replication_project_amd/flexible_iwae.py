@@ -327,6 +327,9 @@ class Flexible_Model:
         """Kernel-variant / tuning knob of the library (include/iwae.h enum
         iwae_knob, e.g. ``set_tuning("upd", 0)``): for A/B measurements and the
         variant-agreement tests; the defaults are the measured-fastest paths."""
+        if name == "st_wt":      # the store-policy mask has its own entry point (iwae_set_store_policy)
+            self._call(self._lib.iwae_set_store_policy(self._h, int(value)))
+            return
         if name not in _lib.KNOBS:
             raise ValueError(f"unknown tuning knob {name!r}; expected one of {tuple(_lib.KNOBS)}")
         self._call(self._lib.iwae_set_tuning(self._h, _lib.KNOBS[name], int(value)))
