@@ -560,6 +560,35 @@ int iwae_score(iwae_handle* h, const float* x, int N, int k, int chunk,
                const float* const* lat, int n_lat,
                float* log_q, float* log_ph, float* log_px,
                float* probs, int ld_probs);
+/* iwae_score for incomplete images: the densities of iwae_impute's and
+ * iwae_train_step_masked's model, p(x_obs, h) and q(h | x_obs).  mask is
+ * [N][x_dim] on the device, non-zero = observed, 0 = missing; every other
+ * argument, limit and output layout is iwae_score's.  The encoder sees x (.)
+ * mask, so log_q is log q(h | x (.) mask); log_px[b][s] = sum over the pixels j
+ * with mask[b][j] != 0 of log Bern(x_bj | p_j(h_1)); log_ph does not change;
+ * probs stay the probabilities of EVERY pixel, observed or not (a caller fills
+ * the missing pixels from them).  Missing entries of x are selected away and
+ * never multiplied: whatever they hold (NaN, Inf) gives the bits a 0 there
+ * gives.  An image with every pixel missing is legal; its log_px is exactly 0.
+ * Staging: where iwae_score copies a chunk's (fused: a first-layer group's)
+ * images into the workspace, this call runs one impute_stage_kernel launch that
+ * writes two copies by select, mask ? x : 0 (the first encoder layer's input)
+ * and mask ? x : -1 (the likelihood's pixels: a negative pixel is a missing
+ * one); the mask rows advance with the chunk.  Kernels: fused, the masked
+ * instantiation of score_kernel (mg_bern's masked form: a missing pixel is the
+ * factor 1 of a binarised product and the term 0 of a fractional sum) on
+ * iwae_score's plan and LDS layout, wherever iwae_score's fused path applies;
+ * layer-wise, iwae_score's launches with the output Dense's masked Bernoulli
+ * epilogue (the tiled GEMM's, as iwae_bound_masked) reading the -1 copy.  The
+ * weight-ring kernel is never used.  There are no float atomics, the call is
+ * deterministic, its result does not depend on chunk, bit for bit, and an
+ * all-observed mask gives iwae_score's bits on either path.  State and error
+ * rules are iwae_score's, and: IWAE_EINVAL for mask NULL and for x NULL (a call
+ * that needs no images has no use for a mask). */
+int iwae_score_masked(iwae_handle* h, const float* x, const float* mask, int N, int k, int chunk,
+                      const float* const* lat, int n_lat,
+                      float* log_q, float* log_ph, float* log_px,
+                      float* probs, int ld_probs);
 /* Gradients of the scored densities with respect to the latents (what HMC, AIS
  * and per-image optimisation of latents move by).  x, N, k, chunk, lat and the
  * value outputs log_q / log_ph / log_px ([N][k], optional) are iwae_score's,
@@ -623,6 +652,32 @@ int iwae_score_grad(iwae_handle* h, const float* x, int N, int k, int chunk,
                     const float coef[3],
                     float* const* grad, int n_grad,
                     float* log_q, float* log_ph, float* log_px);
+/* iwae_score_grad for incomplete images: mask ([N][x_dim], device, non-zero =
+ * observed) and the semantics are iwae_score_masked's; every other argument,
+ * limit and output is iwae_score_grad's.  log q is log q(h | x (.) mask) (its
+ * gradient with respect to the latents follows); log p(x|h_1) sums the observed
+ * pixels only and the dlogit of a missing pixel is 0, so an image with every
+ * pixel missing has log_px exactly 0 and d log p(x|h)/dh exactly 0; log p(h) and
+ * its gradient do not change.  Missing entries of x are selected away, never
+ * multiplied: NaN or Inf there gives the bits a 0 gives.  Staging is
+ * iwae_score_masked's (one impute_stage_kernel launch per chunk or first-layer
+ * group: mask ? x : 0 for the encoder, mask ? x : -1 for the likelihood).
+ * Kernels: fused, the masked instantiation of sg_kernel on iwae_score_grad's
+ * plan and LDS layout -- in the output stage a pixel whose staged value is
+ * negative adds 0 to the row's log p(x|h) and stores a 0 dlogit, by a select on
+ * values computed for every pixel; the 256-pixel slabs, the one-wave-per-dY2-
+ * tile accumulation and the addend order are iwae_score_grad's; layer-wise,
+ * iwae_score_grad's launches with the masked Bernoulli epilogue writing c_px
+ * dlogit (a chunk's dlogits: at most 256 MB).  The weight-ring kernel is never
+ * used.  There are no float atomics, the call is deterministic, its result
+ * does not depend on chunk, bit for bit, and an all-observed mask gives
+ * iwae_score_grad's bits on either path.  State and error rules are
+ * iwae_score_grad's, and: IWAE_EINVAL for mask NULL and for x NULL. */
+int iwae_score_grad_masked(iwae_handle* h, const float* x, const float* mask, int N, int k, int chunk,
+                           const float* const* lat, int n_lat,
+                           const float coef[3],
+                           float* const* grad, int n_grad,
+                           float* log_q, float* log_ph, float* log_px);
 /* Annealed importance sampling on the latents (Neal 2001; Wu et al. 2017): a
  * whole annealing schedule of Metropolis-adjusted HMC transitions, enqueued on
  * the handle's stream with no host synchronization (only a workspace that has
@@ -707,6 +762,34 @@ int iwae_ais(iwae_handle* h, const float* x, int N, int k, int chunk,
              float* step_io,
              float* log_w, float* accepts,
              float* logpx, float* ess);
+/* iwae_ais on incomplete images: annealing towards p(h | x_obs), so logpx
+ * estimates log p(x_obs).  mask ([N][x_dim], device, non-zero = observed) and
+ * the semantics are iwae_score_masked's: log q is log q(h | x (.) mask), log
+ * p(x|h_1) sums the observed pixels, a missing pixel's dlogit is 0, log p(h)
+ * does not change, missing entries of x are selected away (NaN or Inf there
+ * gives the bits a 0 gives), an all-missing image is legal.  Every other
+ * argument, limit, output, noise rule and the transition itself are iwae_ais's;
+ * each of the n_leapfrog + 1 gradient passes of a transition is an
+ * iwae_score_grad_masked pass with the same mask (its two staged copies, mask
+ * ? x : 0 for the encoder and mask ? x : -1 for the likelihood, then the masked
+ * sg_kernel or the masked layer-wise launches), between them iwae_ais's own
+ * begin / step / end launches.  The weight-ring kernel is never used.
+ * There are no float atomics, the call is deterministic, its result does not
+ * depend on chunk, bit for bit, and an all-observed mask gives iwae_ais's bits.
+ * Continuation: with accumulate = 1 a call on the lat, step_io, log_w and
+ * accepts a previous call left, with the same x and mask and over the rest of
+ * the schedule, gives bit for bit what one call over the whole schedule gives,
+ * with injected and with device noise.  State, noise-position and error rules
+ * (nothing launched on an error) are iwae_ais's, and: IWAE_EINVAL for mask
+ * NULL (x NULL is iwae_ais's own error). */
+int iwae_ais_masked(iwae_handle* h, const float* x, const float* mask, int N, int k, int chunk,
+                    float* const* lat, int n_lat,
+                    const iwae_ais_config* cfg, const float* betas,
+                    const float* const* mom, int n_mom,
+                    const float* u,
+                    float* step_io,
+                    float* log_w, float* accepts,
+                    float* logpx, float* ess);
 /* Per-image variational refinement ("local" optimisation of q; Cremer, Li &
  * Duvenaud 2018): Adam ascent on the parameters of one diagonal Gaussian per
  * image over all latent layers jointly, q*(h) = prod_i N(h_i; m_i,
@@ -786,6 +869,33 @@ int iwae_refine(iwae_handle* h, const float* x, int N, int k, int chunk,
                 float* const* adam, int n_adam,
                 float* bound, float* const* lat_out, int n_lat,
                 float* log_w, float* logpx, float* ess);
+/* iwae_refine on incomplete images: q*(h) is fitted to p(h | x_obs), and the
+ * evaluation's logpx is a bound on log p(x_obs).  mask ([N][x_dim], device,
+ * non-zero = observed) and the semantics are iwae_score_masked's: log p(x|h_1)
+ * sums the observed pixels, a missing pixel's dlogit is 0, log p(h) does not
+ * change, missing entries of x are selected away (NaN or Inf there gives the
+ * bits a 0 gives), an all-missing image is legal (its q* moves under the prior
+ * alone).  Every other argument, limit, output, noise rule and the update are
+ * iwae_refine's; each gradient pass and the evaluation's scoring pass is an
+ * iwae_score_grad_masked pass under (0, 1, 1) with the same mask (its two
+ * staged copies, mask ? x : 0 for the encoder and mask ? x : -1 for the
+ * likelihood, then the masked sg_kernel or the masked layer-wise launches),
+ * between them iwae_refine's own launches.  The weight-ring kernel is never
+ * used.  There are no float atomics, the call is deterministic, its result
+ * does not depend on chunk, bit for bit, and an all-observed mask gives
+ * iwae_refine's bits.  Continuation: a second call on the mean, logstd and
+ * adam a first call left, with the same x and mask and step0 = the first
+ * call's n_iters, gives bit for bit what one call over all iterations gives,
+ * provided the first call ran no evaluation pass.  State, noise-position and
+ * error rules (nothing launched on an error) are iwae_refine's, and:
+ * IWAE_EINVAL for mask NULL (x NULL is iwae_refine's own error). */
+int iwae_refine_masked(iwae_handle* h, const float* x, const float* mask, int N, int k, int chunk,
+                       float* const* mean, float* const* logstd, int n_par,
+                       const iwae_refine_config* cfg,
+                       const float* const* eps, int n_eps,
+                       float* const* adam, int n_adam,
+                       float* bound, float* const* lat_out, int n_lat,
+                       float* log_w, float* logpx, float* ess);
 /* Encoder.call (F:56-F:75): k samples of q(h|x) per image, with device noise
  * (eps NULL, n_eps 0) or injected eps[i] [k][N][d_i].  lat_out[i] [k][N][d_i],
  * sample-major (n_lat 0 or L); log_q [N][k]; loc_top / scale_top: the
@@ -858,7 +968,13 @@ double iwae_workspace_bytes(const iwae_handle* h);
  * run by iwae_ais, 28 its begin / step / end launches (n_temps (n_leapfrog +
  * 1) per call; the finish launch is not counted); 29 refinement iterations
  * run by iwae_refine, 30 its begin / step / end launches (n_iters + 1 per
- * call; the finish launch is not counted); -1 for an unknown id. */
+ * call; the finish launch is not counted); pixel-masked calls
+ * (iwae_score_masked, iwae_score_grad_masked and the passes iwae_ais_masked /
+ * iwae_refine_masked run), one per chunk and not counted under 23-26: 31
+ * masked fused score_kernel launches, 32 masked layer-wise score passes, 33
+ * masked fused sg_kernel launches, 34 masked layer-wise score-gradient passes
+ * (iwae_ais_masked and iwae_refine_masked count under 27-30 as their
+ * siblings do); -1 for an unknown id. */
 long long iwae_debug_count(const iwae_handle* h, int what);
 /* Live kernel timing: bracket every launch of one kernel class with HIP events
  * on the handle's stream -- a GEMM class (kind: 0 forward, 1 backward-data,

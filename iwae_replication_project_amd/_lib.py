@@ -118,11 +118,17 @@ SIGNATURES = {
     "iwae_impute": (c_int, [H, FP, FP, c_int, c_int, c_int, FPP, c_int, FP, FP, FP, c_int, FP, c_int, FPP, c_int,
                             FPP, c_int, FP, FP, FP]),
     "iwae_score": (c_int, [H, FP, c_int, c_int, c_int, FPP, c_int, FP, FP, FP, FP, c_int]),
+    "iwae_score_masked": (c_int, [H, FP, FP, c_int, c_int, c_int, FPP, c_int, FP, FP, FP, FP, c_int]),
     "iwae_score_grad": (c_int, [H, FP, c_int, c_int, c_int, FPP, c_int, FP, FPP, c_int, FP, FP, FP]),
+    "iwae_score_grad_masked": (c_int, [H, FP, FP, c_int, c_int, c_int, FPP, c_int, FP, FPP, c_int, FP, FP, FP]),
     "iwae_ais": (c_int, [H, FP, c_int, c_int, c_int, FPP, c_int, POINTER(IwaeAisConfig), FP, FPP, c_int, FP, FP, FP, FP,
                          FP, FP]),
+    "iwae_ais_masked": (c_int, [H, FP, FP, c_int, c_int, c_int, FPP, c_int, POINTER(IwaeAisConfig), FP, FPP, c_int, FP,
+                                FP, FP, FP, FP, FP]),
     "iwae_refine": (c_int, [H, FP, c_int, c_int, c_int, FPP, FPP, c_int, POINTER(IwaeRefineConfig), FPP, c_int, FPP, c_int,
                             FP, FPP, c_int, FP, FP, FP]),
+    "iwae_refine_masked": (c_int, [H, FP, FP, c_int, c_int, c_int, FPP, FPP, c_int, POINTER(IwaeRefineConfig), FPP, c_int,
+                                   FPP, c_int, FP, FPP, c_int, FP, FP, FP]),
     "iwae_encode": (c_int, [H, FP, c_int, c_int, c_int, FPP, c_int, FPP, c_int, FP, FP, FP]),
     "iwae_train_step_masked": (c_int, [H, POINTER(IwaeLossConfig), FP, FP, c_int, FPP, c_int, FP]),
     "iwae_forward_backward_masked": (c_int, [H, POINTER(IwaeLossConfig), FP, FP, c_int, FPP, c_int, FP]),

@@ -610,6 +610,8 @@ struct ScLaunch : MgLaunch {
   float* probs; int ld_probs;        // out: p(h_1) of the rows [rows][ld_probs], or null
 };
 hipError_t launch_score(hipStream_t st, const ScLaunch& L, int rt, int waves, size_t lds_bytes);
+// The pixel-masked variant (iwae_score_masked): L.x is the staged copy with -1 at the missing pixels
+hipError_t launch_score_masked(hipStream_t st, const ScLaunch& L, int rt, int waves, size_t lds_bytes);
 hipError_t score_setup_attributes();
 
 // Relayouts between the callers' sample-major [k][N][d] buffers and the
@@ -699,6 +701,9 @@ struct SgLaunch {
   float* log_q; float* log_ph; float* log_px;
 };
 hipError_t launch_sgrad(hipStream_t st, const SgLaunch& L, int rt, size_t lds_bytes);
+// The pixel-masked variant (iwae_score_grad_masked): L.x is the staged copy with -1 at the missing
+// pixels; their terms of log p(x|h) and their dlogits are 0
+hipError_t launch_sgrad_masked(hipStream_t st, const SgLaunch& L, int rt, size_t lds_bytes);
 hipError_t sgrad_setup_attributes();
 
 // ------------------------------- weight-ring k-sample forward (NLL) ----

@@ -437,7 +437,7 @@ struct ScTargets<RT, true> {
 template <int RT, int ACT>
 __device__ __forceinline__ void sc_operands(const ScLaunch& L, const MgStage& S, int t, const ScRows<RT>& R,
                                             float4 (&xv)[RT], ScTargets<RT, true>& T);
-template <int RT, int ACT>
+template <int RT, int ACT, bool MASK>
 __device__ __forceinline__ void sc_epilogue(const ScLaunch& L, const MgStage& S, int t, const mg_f32x4 (&acc)[RT],
                                             const float4 (&xv)[RT], const ScTargets<RT, true>& T, ScRows<RT>& R);
 
@@ -469,7 +469,7 @@ __device__ __forceinline__ void mg_tile(const LT& L, const MgStage& S, const MgB
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt) acc[rt] = (mg_f32x4){0.f, 0.f, 0.f, 0.f};
   mg_mma<RT>(IN, 0, min(MG_KS, S.ldk >> 5), f, acc, ph, pl, pf, pf_vb, pf_ns);
-  if constexpr (ACT >= MG_DENSQ) sc_epilogue<RT, ACT>(L, S, t, acc, xv, tg, R);
+  if constexpr (ACT >= MG_DENSQ) sc_epilogue<RT, ACT, MASK>(L, S, t, acc, xv, tg, R);
   else if (ACT == MG_TANH) mg_store_tanh<RT>(OUT, S, t, acc);
   else if (ACT == MG_BERN) mg_bern<RT, MASK>(L, S, t, acc, xv, R);
   else mg_head<RT, ACT>(L, S, t, base, acc, R);
@@ -521,7 +521,7 @@ __device__ __forceinline__ void mg_dense(const LT& L, const MgStage& S, uint64_t
         mg_fetch(S, rh, rl, t, k0, f);
         mg_mma<RT>(IN, k0, min(MG_KS, (S.ldk - k0) >> 5), f, acc, rh, rl, false, kOOB, 0);
       }
-      if constexpr (ACT >= MG_DENSQ) sc_epilogue<RT, ACT>(L, S, t, acc, xv, tg, R);
+      if constexpr (ACT >= MG_DENSQ) sc_epilogue<RT, ACT, MASK>(L, S, t, acc, xv, tg, R);
       else if (ACT == MG_TANH) mg_store_tanh<RT>(OUT, S, t, acc);
       else if (ACT == MG_BERN) mg_bern<RT, MASK>(L, S, t, acc, xv, R);
       else mg_head<RT, ACT>(L, S, t, base, acc, R);

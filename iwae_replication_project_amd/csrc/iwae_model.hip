@@ -218,6 +218,8 @@ struct Counters {
   long long sgrad = 0, sgrad_lw = 0;     // 25, 26: iwae_score_grad chunks: sg_kernel launches / layer-wise passes
   long long ais = 0, ais_launch = 0;     // 27, 28: iwae_ais transitions / their begin, step and end launches
   long long refine = 0, refine_launch = 0;   // 29, 30: iwae_refine iterations / its begin, step and end launches
+  long long score_pix = 0, score_pix_lw = 0;   // 31, 32: pixel-masked iwae_score chunks: masked score_kernel launches / layer-wise passes
+  long long sgrad_pix = 0, sgrad_pix_lw = 0;   // 33, 34: pixel-masked iwae_score_grad chunks: masked sg_kernel launches / layer-wise passes
 };
 
 // row-chain train engine plan (device resident, per shape; iwae_train.hip)
@@ -4897,8 +4899,25 @@ static void score_plan(const iwae_handle* h, const MgLaunch& MG, bool q, bool ph
   S.want_ph = ph ? 1 : 0;
 }
 
-int iwae_score(iwae_handle* h, const float* x, int N, int k, int chunk, const float* const* lat, int n_lat,
-               float* log_q, float* log_ph, float* log_px, float* probs, int ld_probs) {
+// The chunk's (or the first-layer group's) ng images from row i0 on into x_in:
+// a copy, or with a pixel mask the two staged copies by select (x_in = mask ?
+// x : 0, x_lik = mask ? x : -1; impute_stage_kernel).
+static int score_stage_x(iwae_handle* h, const float* x, const float* mask, int i0, int ng) {
+  if (mask) {
+    HIPCHK(launch_impute_stage(h->stream, x + (size_t)i0 * h->xdim, mask + (size_t)i0 * h->xdim, ng, h->xdim, h->x_in.p,
+                               h->x_in.ld, h->x_lik.p, h->x_lik.ld));
+    return IWAE_OK;
+  }
+  const size_t wbytes = (size_t)h->xdim * sizeof(float);
+  HIPCHK(hipMemcpy2DAsync(h->x_in.p, (size_t)h->x_in.ld * sizeof(float), x + (size_t)i0 * h->xdim, wbytes, wbytes, ng,
+                          hipMemcpyDeviceToDevice, h->stream));
+  return IWAE_OK;
+}
+
+// iwae_score and iwae_score_masked (mask: [N][x_dim], non-zero = observed; null: none)
+static int score_core(iwae_handle* h, const float* x, const float* mask, int N, int k, int chunk,
+                      const float* const* lat, int n_lat, float* log_q, float* log_ph, float* log_px, float* probs,
+                      int ld_probs) {
   if (!h) return IWAE_EINVAL;
   CHK(kernel_status(h));
   const int L = h->L;
@@ -4931,7 +4950,7 @@ int iwae_score(iwae_handle* h, const float* x, int N, int k, int chunk, const fl
     SC.eps_N = N; SC.eps_s0 = 0;
     SC.rng_base = nullptr; SC.seed = 0; SC.lw = nullptr;
   }
-  const size_t wbytes = (size_t)h->xdim * sizeof(float);
+  const Mat& xl = mask ? h->x_lik : h->x_in;      // the likelihood's copy of the images
   int u0 = 0;                                    // first image of the current first-layer group (fused)
   for (int i0 = 0; i0 < N; i0 += imgs) {
     const int n = std::min(imgs, N - i0), M = n * k;
@@ -4939,25 +4958,29 @@ int iwae_score(iwae_handle* h, const float* x, int N, int k, int chunk, const fl
     if (x && (!fused || i0 - u0 >= sup || i0 == 0)) {
       u0 = i0;
       const int ng = std::min(sup, N - i0);
-      HIPCHK(hipMemcpy2DAsync(h->x_in.p, (size_t)h->x_in.ld * sizeof(float), x + (size_t)i0 * h->xdim, wbytes, wbytes,
-                              ng, hipMemcpyDeviceToDevice, h->stream));
+      CHK(score_stage_x(h, x, mask, i0, ng));
       if (log_q) CHK(stoch_fwd(h, h->enc[0], h->x_in, ng, h->eb[0]));
     }
     const int io = x ? i0 - u0 : 0;              // the chunk's rows in x_in / eb[0]
     if (fused) {
       SC.rows = M; SC.kS = k; SC.eps_i0 = i0;
       SC.P0 = h->eb[0].P.p + (size_t)io * h->eb[0].P.ld; SC.ldP0 = h->eb[0].P.ld;
-      SC.x = h->x_in.p + (size_t)io * h->x_in.ld; SC.ldx = h->x_in.ld;
+      SC.x = xl.p + (size_t)io * xl.ld; SC.ldx = xl.ld;
       SC.log_q = log_q ? log_q + r0 : nullptr;
       SC.log_ph = log_ph ? log_ph + r0 : nullptr;
       SC.log_px = log_px ? log_px + r0 : nullptr;
       SC.probs = probs ? probs + r0 * ld_probs : nullptr; SC.ld_probs = ld_probs;
-      HIPCHK(launch_score(h->stream, SC, mg_rt, mg_waves, mg_lds));
-      ++h->count.score;
+      if (mask) {
+        HIPCHK(launch_score_masked(h->stream, SC, mg_rt, mg_waves, mg_lds));
+        ++h->count.score_pix;
+      } else {
+        HIPCHK(launch_score(h->stream, SC, mg_rt, mg_waves, mg_lds));
+        ++h->count.score;
+      }
       continue;
     }
     // ---- layer-wise: the latents into the workspace's rows, then forward_core's launches as density passes
-    ++h->count.score_lw;
+    ++(mask ? h->count.score_pix_lw : h->count.score_lw);
     ScRelayout G{};
     G.n = n; G.k = k; G.N = N; G.i0 = i0; G.gather = 1;
     for (int i = 0; i < L; ++i)
@@ -4978,11 +5001,11 @@ int iwae_score(iwae_handle* h, const float* x, int N, int k, int chunk, const fl
     }
     if (log_px) {
       GemmArgs ex{};
-      ex.aux = h->x_in.p; ex.ldaux = h->x_in.ld; ex.x_row_div = k;
+      ex.aux = xl.p; ex.ldaux = xl.ld; ex.x_row_div = k;
       ex.part = h->part; ex.part2 = h->part2; ex.ldpart = h->ldpart;
       ex.wa = 1.f; ex.wb = 0.f;
       Mat none;
-      CHK(gemm_fwd(h, EPI_BERN, h->ob.y2, M, h->dense[h->o3], none, ex));
+      CHK(gemm_fwd(h, mask ? EPI_BERN_MASK : EPI_BERN, h->ob.y2, M, h->dense[h->o3], none, ex));
       HIPCHK(launch_score_rowsum(h->stream, h->part, h->ldpart, h->npart, M, log_px + r0));
     }
     if (probs) {
@@ -4994,6 +5017,27 @@ int iwae_score(iwae_handle* h, const float* x, int N, int k, int chunk, const fl
     }
   }
   return IWAE_OK;
+}
+
+int iwae_score(iwae_handle* h, const float* x, int N, int k, int chunk, const float* const* lat, int n_lat,
+               float* log_q, float* log_ph, float* log_px, float* probs, int ld_probs) {
+  return score_core(h, x, nullptr, N, k, chunk, lat, n_lat, log_q, log_ph, log_px, probs, ld_probs);
+}
+
+// pixel-masked entries of this family: the checks they add (the siblings' own follow)
+static int check_observed(iwae_handle* h, const float* x, const float* mask) {
+  if (!h) return IWAE_EINVAL;
+  CHK(kernel_status(h));
+  if (!mask) return fail(h, IWAE_EINVAL, "mask is NULL");
+  if (!x) return fail(h, IWAE_EINVAL, "x is NULL (a call that needs no images has no use for a mask)");
+  return IWAE_OK;
+}
+
+int iwae_score_masked(iwae_handle* h, const float* x, const float* mask, int N, int k, int chunk,
+                      const float* const* lat, int n_lat, float* log_q, float* log_ph, float* log_px, float* probs,
+                      int ld_probs) {
+  CHK(check_observed(h, x, mask));
+  return score_core(h, x, mask, N, k, chunk, lat, n_lat, log_q, log_ph, log_px, probs, ld_probs);
 }
 
 // sg_kernel's plan (SgLaunch, iwae_kernels.h): the chains of the terms that are needed, each forward
@@ -5097,8 +5141,10 @@ static bool sgrad_plan(const iwae_handle* h, bool run_q, bool run_ph, bool run_p
 // epilogue writing c_px dlogit, and one scatter launch; its backward rows live
 // in a workspace of the call's own (sg_ws), so the arena and what was captured
 // over it stay as they are.
-int iwae_score_grad(iwae_handle* h, const float* x, int N, int k, int chunk, const float* const* lat, int n_lat,
-                    const float coef[3], float* const* grad, int n_grad, float* log_q, float* log_ph, float* log_px) {
+// (mask: iwae_score_grad_masked's, [N][x_dim], non-zero = observed; null: none)
+static int sgrad_core(iwae_handle* h, const float* x, const float* mask, int N, int k, int chunk,
+                      const float* const* lat, int n_lat, const float coef[3], float* const* grad, int n_grad,
+                      float* log_q, float* log_ph, float* log_px) {
   if (!h) return IWAE_EINVAL;
   CHK(kernel_status(h));
   const int L = h->L;
@@ -5143,7 +5189,7 @@ int iwae_score_grad(iwae_handle* h, const float* x, int N, int k, int chunk, con
       SG.lat_N = N;
       SG.cq = gq ? cq : 0.f; SG.cph = gph ? cph : 0.f;
       SG.want_q = log_q ? 1 : 0; SG.want_ph = log_ph ? 1 : 0;
-      const size_t xb = (size_t)h->xdim * sizeof(float);
+      const Mat& xl = mask ? h->x_lik : h->x_in;    // the likelihood's copy of the images
       int u0 = 0;                                  // first image of the current first-layer group
       for (int i0 = 0; i0 < N; i0 += imgs) {
         const int n = std::min(imgs, N - i0);
@@ -5151,19 +5197,23 @@ int iwae_score_grad(iwae_handle* h, const float* x, int N, int k, int chunk, con
         if (x && (i0 - u0 >= sup || i0 == 0)) {
           u0 = i0;
           const int ng = std::min(sup, N - i0);
-          HIPCHK(hipMemcpy2DAsync(h->x_in.p, (size_t)h->x_in.ld * sizeof(float), x + (size_t)i0 * h->xdim, xb, xb, ng,
-                                  hipMemcpyDeviceToDevice, h->stream));
+          CHK(score_stage_x(h, x, mask, i0, ng));
           if (run_q) CHK(stoch_fwd(h, h->enc[0], h->x_in, ng, h->eb[0]));
         }
         const int io = x ? i0 - u0 : 0;            // the chunk's rows in x_in / eb[0]
         SG.rows = n * k; SG.kS = k; SG.lat_i0 = i0;
         SG.P0 = h->eb[0].P.p + (size_t)io * h->eb[0].P.ld; SG.ldP0 = h->eb[0].P.ld;
-        SG.x = h->x_in.p + (size_t)io * h->x_in.ld; SG.ldx = h->x_in.ld;
+        SG.x = xl.p + (size_t)io * xl.ld; SG.ldx = xl.ld;
         SG.log_q = log_q ? log_q + r0 : nullptr;
         SG.log_ph = log_ph ? log_ph + r0 : nullptr;
         SG.log_px = log_px ? log_px + r0 : nullptr;
-        HIPCHK(launch_sgrad(h->stream, SG, sg_rt, sg_lds));
-        ++h->count.sgrad;
+        if (mask) {
+          HIPCHK(launch_sgrad_masked(h->stream, SG, sg_rt, sg_lds));
+          ++h->count.sgrad_pix;
+        } else {
+          HIPCHK(launch_sgrad(h->stream, SG, sg_rt, sg_lds));
+          ++h->count.sgrad;
+        }
       }
       return IWAE_OK;
     }
@@ -5237,16 +5287,15 @@ int iwae_score_grad(iwae_handle* h, const float* x, int N, int k, int chunk, con
     HIPCHK(launch_sg_dens(h->stream, a));
     return IWAE_OK;
   };
-  const size_t wbytes = (size_t)h->xdim * sizeof(float);
+  const Mat& xl = mask ? h->x_lik : h->x_in;      // the likelihood's copy of the images
   for (int i0 = 0; i0 < N; i0 += imgs) {
     const int n = std::min(imgs, N - i0), M = n * k;
     const size_t r0 = (size_t)i0 * k;            // the chunk's first row of the [N][k] outputs
     if (x) {
-      HIPCHK(hipMemcpy2DAsync(h->x_in.p, (size_t)h->x_in.ld * sizeof(float), x + (size_t)i0 * h->xdim, wbytes, wbytes,
-                              n, hipMemcpyDeviceToDevice, h->stream));
+      CHK(score_stage_x(h, x, mask, i0, n));
       if (run_q) CHK(stoch_fwd(h, h->enc[0], h->x_in, n, h->eb[0]));
     }
-    ++h->count.sgrad_lw;
+    ++(mask ? h->count.sgrad_pix_lw : h->count.sgrad_lw);
     ScRelayout G{};
     G.n = n; G.k = k; G.N = N; G.i0 = i0; G.gather = 1;
     for (int i = 0; i < L; ++i)
@@ -5292,13 +5341,13 @@ int iwae_score_grad(iwae_handle* h, const float* x, int N, int k, int chunk, con
       CHK(gemm_fwd(h, EPI_TANH, h->h[0], M, h->dense[h->o1], h->ob.y1));
       CHK(gemm_fwd(h, EPI_TANH, h->ob.y1, M, h->dense[h->o2], h->ob.y2));
       GemmArgs ex{};
-      ex.aux = h->x_in.p; ex.ldaux = h->x_in.ld; ex.x_row_div = k;
+      ex.aux = xl.p; ex.ldaux = xl.ld; ex.x_row_div = k;
       ex.part = h->part; ex.part2 = h->part2; ex.ldpart = h->ldpart;
       ex.wa = gpx ? cpx : 1.f; ex.wb = 0.f;
       ex.store_g = gpx ? 1 : 0;
       Mat gm;
       if (gpx) gm = dlogit;
-      CHK(gemm_fwd(h, EPI_BERN, h->ob.y2, M, h->dense[h->o3], gm, ex));
+      CHK(gemm_fwd(h, mask ? EPI_BERN_MASK : EPI_BERN, h->ob.y2, M, h->dense[h->o3], gm, ex));
       if (log_px) HIPCHK(launch_score_rowsum(h->stream, h->part, h->ldpart, h->npart, M, log_px + r0));
       if (gpx) {
         Mat &dY2 = dY2s[Ho], &dY1 = dY1s[Ho];
@@ -5328,6 +5377,18 @@ int iwae_score_grad(iwae_handle* h, const float* x, int N, int k, int chunk, con
   return IWAE_OK;
 }
 
+int iwae_score_grad(iwae_handle* h, const float* x, int N, int k, int chunk, const float* const* lat, int n_lat,
+                    const float coef[3], float* const* grad, int n_grad, float* log_q, float* log_ph, float* log_px) {
+  return sgrad_core(h, x, nullptr, N, k, chunk, lat, n_lat, coef, grad, n_grad, log_q, log_ph, log_px);
+}
+
+int iwae_score_grad_masked(iwae_handle* h, const float* x, const float* mask, int N, int k, int chunk,
+                           const float* const* lat, int n_lat, const float coef[3], float* const* grad, int n_grad,
+                           float* log_q, float* log_ph, float* log_px) {
+  CHK(check_observed(h, x, mask));
+  return sgrad_core(h, x, mask, N, k, chunk, lat, n_lat, coef, grad, n_grad, log_q, log_ph, log_px);
+}
+
 // Annealed importance sampling (include/iwae.h): per transition one gradient
 // pass at the state (iwae_score_grad, fused or layer-wise as it decides), the
 // begin launch, then n_leapfrog passes at the proposal, each followed by the
@@ -5335,9 +5396,10 @@ int iwae_score_grad(iwae_handle* h, const float* x, int N, int k, int chunk, con
 // per call.  Everything is enqueued on h->stream: coef is a host array and the
 // chains' buffers (ais_ws) only grow, so the host waits only where a workspace
 // grows.
-int iwae_ais(iwae_handle* h, const float* x, int N, int k, int chunk, float* const* lat, int n_lat,
-             const iwae_ais_config* cfg, const float* betas, const float* const* mom, int n_mom, const float* u,
-             float* step_io, float* log_w, float* accepts, float* logpx, float* ess) {
+// (mask: iwae_ais_masked's, handed to every gradient pass; null: none)
+static int ais_core(iwae_handle* h, const float* x, const float* mask, int N, int k, int chunk, float* const* lat,
+                    int n_lat, const iwae_ais_config* cfg, const float* betas, const float* const* mom, int n_mom,
+                    const float* u, float* step_io, float* log_w, float* accepts, float* logpx, float* ess) {
   if (!h) return IWAE_EINVAL;
   CHK(kernel_status(h));
   const int L = h->L;
@@ -5425,11 +5487,11 @@ int iwae_ais(iwae_handle* h, const float* x, int N, int k, int chunk, float* con
     a.t_off = (unsigned)(t - 1);
     for (int i = 0; i < L; ++i) a.mom[i] = n_mom ? mom[(size_t)(t - 1) * L + i] : nullptr;
     a.u = u ? u + (size_t)(t - 1) * chains : nullptr;
-    CHK(iwae_score_grad(h, x, N, k, chunk, lat, L, coef, gbuf, L, lq, lph, lpx));
+    CHK(sgrad_core(h, x, mask, N, k, chunk, lat, L, coef, gbuf, L, lq, lph, lpx));
     HIPCHK(launch_ais_begin(h->stream, a));
     ++h->count.ais_launch;
     for (int l = 1; l <= nl; ++l) {
-      CHK(iwae_score_grad(h, x, N, k, chunk, a.q, L, coef, gbuf, L, lq, lph, lpx));
+      CHK(sgrad_core(h, x, mask, N, k, chunk, a.q, L, coef, gbuf, L, lq, lph, lpx));
       if (l < nl) HIPCHK(launch_ais_step(h->stream, a));
       else HIPCHK(launch_ais_end(h->stream, a));
       ++h->count.ais_launch;
@@ -5440,6 +5502,19 @@ int iwae_ais(iwae_handle* h, const float* x, int N, int k, int chunk, float* con
   return IWAE_OK;
 }
 
+int iwae_ais(iwae_handle* h, const float* x, int N, int k, int chunk, float* const* lat, int n_lat,
+             const iwae_ais_config* cfg, const float* betas, const float* const* mom, int n_mom, const float* u,
+             float* step_io, float* log_w, float* accepts, float* logpx, float* ess) {
+  return ais_core(h, x, nullptr, N, k, chunk, lat, n_lat, cfg, betas, mom, n_mom, u, step_io, log_w, accepts, logpx, ess);
+}
+
+int iwae_ais_masked(iwae_handle* h, const float* x, const float* mask, int N, int k, int chunk, float* const* lat,
+                    int n_lat, const iwae_ais_config* cfg, const float* betas, const float* const* mom, int n_mom,
+                    const float* u, float* step_io, float* log_w, float* accepts, float* logpx, float* ess) {
+  CHK(check_observed(h, x, mask));
+  return ais_core(h, x, mask, N, k, chunk, lat, n_lat, cfg, betas, mom, n_mom, u, step_io, log_w, accepts, logpx, ess);
+}
+
 // Per-image variational refinement (include/iwae.h): n_iters gradient passes
 // at the samples of q* (iwae_score_grad under (0, 1, 1), fused or layer-wise as
 // it decides) with one launch of iwae_refine.hip before the first, between each
@@ -5447,9 +5522,11 @@ int iwae_ais(iwae_handle* h, const float* x, int N, int k, int chunk, float* con
 // the caller wants the evaluation.  Everything is enqueued on h->stream; the
 // samples' buffers (refine_ws) only grow, so the host waits only where a
 // workspace grows.
-int iwae_refine(iwae_handle* h, const float* x, int N, int k, int chunk, float* const* mean, float* const* logstd,
-                int n_par, const iwae_refine_config* cfg, const float* const* eps, int n_eps, float* const* adam,
-                int n_adam, float* bound, float* const* lat_out, int n_lat, float* log_w, float* logpx, float* ess) {
+// (mask: iwae_refine_masked's, handed to every gradient and scoring pass; null: none)
+static int refine_core(iwae_handle* h, const float* x, const float* mask, int N, int k, int chunk, float* const* mean,
+                       float* const* logstd, int n_par, const iwae_refine_config* cfg, const float* const* eps,
+                       int n_eps, float* const* adam, int n_adam, float* bound, float* const* lat_out, int n_lat,
+                       float* log_w, float* logpx, float* ess) {
   if (!h) return IWAE_EINVAL;
   CHK(kernel_status(h));
   const int L = h->L;
@@ -5553,7 +5630,7 @@ int iwae_refine(iwae_handle* h, const float* x, int N, int k, int chunk, float* 
   ++h->count.refine_launch;
   const double b1 = cfg->beta1, b2 = cfg->beta2;
   for (int t = 0; t < T; ++t) {
-    CHK(iwae_score_grad(h, x, N, k, chunk, lat, L, coef, gbuf, L, nullptr, lph, lpx));
+    CHK(sgrad_core(h, x, mask, N, k, chunk, lat, L, coef, gbuf, L, nullptr, lph, lpx));
     const double n = (double)cfg->step0 + t + 1;
     a.lr_n = (float)((double)cfg->lr * std::sqrt(1.0 - std::pow(b2, n)) / (1.0 - std::pow(b1, n)));
     a.zero = cfg->step0 == 0 && t == 0;
@@ -5565,9 +5642,25 @@ int iwae_refine(iwae_handle* h, const float* x, int N, int k, int chunk, float* 
     ++h->count.refine_launch;
     ++h->count.refine;
   }
-  if (eval) CHK(iwae_score_grad(h, x, N, k, chunk, lat, L, coef, nullptr, 0, nullptr, lph, lpx));
+  if (eval) CHK(sgrad_core(h, x, mask, N, k, chunk, lat, L, coef, nullptr, 0, nullptr, lph, lpx));
   HIPCHK(launch_refine_finish(h->stream, a));
   return IWAE_OK;
+}
+
+int iwae_refine(iwae_handle* h, const float* x, int N, int k, int chunk, float* const* mean, float* const* logstd,
+                int n_par, const iwae_refine_config* cfg, const float* const* eps, int n_eps, float* const* adam,
+                int n_adam, float* bound, float* const* lat_out, int n_lat, float* log_w, float* logpx, float* ess) {
+  return refine_core(h, x, nullptr, N, k, chunk, mean, logstd, n_par, cfg, eps, n_eps, adam, n_adam, bound, lat_out,
+                     n_lat, log_w, logpx, ess);
+}
+
+int iwae_refine_masked(iwae_handle* h, const float* x, const float* mask, int N, int k, int chunk, float* const* mean,
+                       float* const* logstd, int n_par, const iwae_refine_config* cfg, const float* const* eps,
+                       int n_eps, float* const* adam, int n_adam, float* bound, float* const* lat_out, int n_lat,
+                       float* log_w, float* logpx, float* ess) {
+  CHK(check_observed(h, x, mask));
+  return refine_core(h, x, mask, N, k, chunk, mean, logstd, n_par, cfg, eps, n_eps, adam, n_adam, bound, lat_out,
+                     n_lat, log_w, logpx, ess);
 }
 
 // Encoder.call (F:56-F:75): k samples of q(h|x) per image on the layer-wise
@@ -5720,6 +5813,10 @@ long long iwae_debug_count(const iwae_handle* h, int what) {
     case 28: return h->count.ais_launch;
     case 29: return h->count.refine;
     case 30: return h->count.refine_launch;
+    case 31: return h->count.score_pix;
+    case 32: return h->count.score_pix_lw;
+    case 33: return h->count.sgrad_pix;
+    case 34: return h->count.sgrad_pix_lw;
     default: return -1;
   }
 }

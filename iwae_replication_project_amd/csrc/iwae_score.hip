@@ -44,14 +44,16 @@ __device__ __forceinline__ void sc_operands(const ScLaunch& L, const MgStage& S,
 // (MG_DENSP).  Output stage: mg_bern into log p(x|h), and / or p = sigmoid(l)
 // (1 - 1e-6) + 1e-7 of the lane's four features stored (rows of the chunk only;
 // 16-byte stores: ld_probs is a multiple of 4 and probs 16-byte aligned).
-template <int RT, int ACT>
+// MASK: the pixel-masked likelihood (mg_bern<., true>: xv holds -1 at a missing
+// pixel); the probabilities stored are every pixel's, observed or not.
+template <int RT, int ACT, bool MASK>
 __device__ __forceinline__ void sc_epilogue(const ScLaunch& L, const MgStage& S, int t, const mg_f32x4 (&acc)[RT],
                                             const float4 (&xv)[RT], const ScTargets<RT, true>& T, ScRows<RT>& R) {
   const float2 (&tg)[RT] = T.v;
   const int lane = threadIdx.x & 63;
   const int r = lane & 15, g = lane >> 4;
   if (ACT == MG_BERNS) {
-    if (L.log_px) mg_bern<RT, false>(L, S, t, acc, xv, R);
+    if (L.log_px) mg_bern<RT, MASK>(L, S, t, acc, xv, R);
     if (L.probs) {
       const int f0 = t * 16 + 4 * g;
       const int row0 = blockIdx.x * 16 * RT;
@@ -97,8 +99,9 @@ __device__ __forceinline__ void sc_epilogue(const ScLaunch& L, const MgStage& S,
 // iwae_score's fused path (ScLaunch, iwae_kernels.h): the latents are the
 // caller's, so the prologue fills the LDS tiles the stage list reads and the
 // stages only evaluate densities.  Same row tiles, waves and LDS plan as
-// mega_fwd_kernel; nothing is drawn.
-template <int RT, int NW>
+// mega_fwd_kernel; nothing is drawn.  MASK: the pixel-masked likelihood of
+// iwae_score_masked; L.x is then the staged copy with -1 at the missing pixels.
+template <int RT, int NW, bool MASK>
 __global__ __launch_bounds__(NW * 64) void score_kernel(ScLaunch L) {
   constexpr int R = 16 * RT;
   constexpr int TPR = (NW * 64) / R;            // threads per row in the prologue
@@ -161,10 +164,10 @@ __global__ __launch_bounds__(NW * 64) void score_kernel(ScLaunch L) {
     const MgStage& S = L.st[s];
     if (S.act == MG_TANH) mg_pad<RT, NW>(mg_buf<RT>(L, S.out_buf), S.N, S.next_k);
     switch (S.act) {
-      case MG_TANH: mg_dense<RT, MG_TANH, NW, false>(L, S, 0ull, Rw); break;
-      case MG_DENSQ: mg_dense<RT, MG_DENSQ, NW, false>(L, S, 0ull, Rw); break;
-      case MG_DENSP: mg_dense<RT, MG_DENSP, NW, false>(L, S, 0ull, Rw); break;
-      default: mg_dense<RT, MG_BERNS, NW, false>(L, S, 0ull, Rw); break;
+      case MG_TANH: mg_dense<RT, MG_TANH, NW, MASK>(L, S, 0ull, Rw); break;
+      case MG_DENSQ: mg_dense<RT, MG_DENSQ, NW, MASK>(L, S, 0ull, Rw); break;
+      case MG_DENSP: mg_dense<RT, MG_DENSP, NW, MASK>(L, S, 0ull, Rw); break;
+      default: mg_dense<RT, MG_BERNS, NW, MASK>(L, S, 0ull, Rw); break;
     }
     mg_lds_barrier();
   }
@@ -198,29 +201,37 @@ __global__ __launch_bounds__(NW * 64) void score_kernel(ScLaunch L) {
   }
 }
 
-hipError_t launch_score(hipStream_t st, const ScLaunch& L, int rt, int waves, size_t lds_bytes) {
+template <bool MASK>
+static hipError_t launch_score_t(hipStream_t st, const ScLaunch& L, int rt, int waves, size_t lds_bytes) {
   if (L.rows <= 0) return hipSuccess;
   const int R = 16 * rt;
   const dim3 grid((L.rows + R - 1) / R), block(waves * 64);
   if (waves == 4) {
     if (rt != 2) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((score_kernel<2, 4>), grid, block, lds_bytes, st, L);
+    hipLaunchKernelGGL((score_kernel<2, 4, MASK>), grid, block, lds_bytes, st, L);
     return hipGetLastError();
   }
   if (waves != MG_WAVES) return hipErrorInvalidValue;
   switch (rt) {
-    case 1: hipLaunchKernelGGL((score_kernel<1, MG_WAVES>), grid, block, lds_bytes, st, L); break;
-    case 2: hipLaunchKernelGGL((score_kernel<2, MG_WAVES>), grid, block, lds_bytes, st, L); break;
-    case 4: hipLaunchKernelGGL((score_kernel<4, MG_WAVES>), grid, block, lds_bytes, st, L); break;
+    case 1: hipLaunchKernelGGL((score_kernel<1, MG_WAVES, MASK>), grid, block, lds_bytes, st, L); break;
+    case 2: hipLaunchKernelGGL((score_kernel<2, MG_WAVES, MASK>), grid, block, lds_bytes, st, L); break;
+    case 4: hipLaunchKernelGGL((score_kernel<4, MG_WAVES, MASK>), grid, block, lds_bytes, st, L); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
-
+hipError_t launch_score(hipStream_t st, const ScLaunch& L, int rt, int waves, size_t lds_bytes) {
+  return launch_score_t<false>(st, L, rt, waves, lds_bytes);
+}
+hipError_t launch_score_masked(hipStream_t st, const ScLaunch& L, int rt, int waves, size_t lds_bytes) {
+  return launch_score_t<true>(st, L, rt, waves, lds_bytes);
+}
 
 hipError_t score_setup_attributes() {
-  const void* fns[] = {(const void*)score_kernel<1, MG_WAVES>, (const void*)score_kernel<2, MG_WAVES>,
-                       (const void*)score_kernel<4, MG_WAVES>, (const void*)score_kernel<2, 4>};
+  const void* fns[] = {(const void*)score_kernel<1, MG_WAVES, false>, (const void*)score_kernel<2, MG_WAVES, false>,
+                       (const void*)score_kernel<4, MG_WAVES, false>, (const void*)score_kernel<2, 4, false>,
+                       (const void*)score_kernel<1, MG_WAVES, true>, (const void*)score_kernel<2, MG_WAVES, true>,
+                       (const void*)score_kernel<4, MG_WAVES, true>, (const void*)score_kernel<2, 4, true>};
   for (const void* f : fns) {
     const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;

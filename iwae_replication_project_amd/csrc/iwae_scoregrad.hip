@@ -141,7 +141,10 @@ __device__ __forceinline__ void sg_gtanh(const MgBuf& Y, int t, int N, const mg_
 }
 
 // One workgroup: 16 RT rows of the chunk, 8 waves; wave w owns column tiles w, w + 8, ...
-template <int RT>
+// MASK (iwae_score_grad_masked): L.x is the staged copy with -1 at the missing pixels; such a
+// pixel's term of log p(x|h) and its dlogit are selected to 0 (both are computed for every
+// pixel: a -1 keeps each expression finite).
+template <int RT, bool MASK>
 __global__ __launch_bounds__(MG_WAVES * 64) void sg_kernel(SgLaunch L) {
   constexpr int NW = MG_WAVES;
   static_assert(kSgWaves == MG_WAVES, "sgrad_plan sizes the workgroup by kSgWaves");
@@ -355,7 +358,7 @@ __global__ __launch_bounds__(MG_WAVES * 64) void sg_kernel(SgLaunch L) {
               const float rc = frcp(1.f + a), ar = a * rc;
               const float p1 = __builtin_fmaf(l >= 0.f ? rc : ar, kProbScale, kProbShift);
               const float p0 = __builtin_fmaf(l >= 0.f ? ar : rc, kProbScale, kBernOff0);
-              const bool ok = t < ntile && f0 + i < S.N;
+              const bool ok = t < ntile && f0 + i < S.N && !(MASK && x < 0.f);
               const float v = x * __builtin_amdgcn_logf(p1) + (1.f - x) * __builtin_amdgcn_logf(p0);
               l2[rt] += ok ? v : 0.f;
               const float gl1 = x * frcp(p1) - (1.f - x) * frcp(p0);
@@ -427,21 +430,29 @@ __global__ __launch_bounds__(MG_WAVES * 64) void sg_kernel(SgLaunch L) {
   }
 }
 
-hipError_t launch_sgrad(hipStream_t st, const SgLaunch& L, int rt, size_t lds_bytes) {
+template <bool MASK>
+static hipError_t launch_sgrad_t(hipStream_t st, const SgLaunch& L, int rt, size_t lds_bytes) {
   if (L.rows <= 0) return hipSuccess;
   const int R = 16 * rt;
   const dim3 grid((L.rows + R - 1) / R), block(MG_WAVES * 64);
   switch (rt) {
-    case 1: hipLaunchKernelGGL((sg_kernel<1>), grid, block, lds_bytes, st, L); break;
-    case 2: hipLaunchKernelGGL((sg_kernel<2>), grid, block, lds_bytes, st, L); break;
-    case 4: hipLaunchKernelGGL((sg_kernel<4>), grid, block, lds_bytes, st, L); break;
+    case 1: hipLaunchKernelGGL((sg_kernel<1, MASK>), grid, block, lds_bytes, st, L); break;
+    case 2: hipLaunchKernelGGL((sg_kernel<2, MASK>), grid, block, lds_bytes, st, L); break;
+    case 4: hipLaunchKernelGGL((sg_kernel<4, MASK>), grid, block, lds_bytes, st, L); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
+hipError_t launch_sgrad(hipStream_t st, const SgLaunch& L, int rt, size_t lds_bytes) {
+  return launch_sgrad_t<false>(st, L, rt, lds_bytes);
+}
+hipError_t launch_sgrad_masked(hipStream_t st, const SgLaunch& L, int rt, size_t lds_bytes) {
+  return launch_sgrad_t<true>(st, L, rt, lds_bytes);
+}
 
 hipError_t sgrad_setup_attributes() {
-  const void* fns[] = {(const void*)sg_kernel<1>, (const void*)sg_kernel<2>, (const void*)sg_kernel<4>};
+  const void* fns[] = {(const void*)sg_kernel<1, false>, (const void*)sg_kernel<2, false>, (const void*)sg_kernel<4, false>,
+                       (const void*)sg_kernel<1, true>, (const void*)sg_kernel<2, true>, (const void*)sg_kernel<4, true>};
   for (const void* f : fns) {
     const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;

@@ -999,6 +999,10 @@ class Flexible_Model:
         item of the decoder's call.  ``x`` may be None when neither log_q nor
         log_px is asked for.  Nothing is drawn; ``chunk``: images per chunk (0:
         automatic)."""
+        return self._score(x, None, h, want, chunk)
+
+    def _score(self, x, mask, h, want, chunk):
+        """``score`` (mask None) and ``score_observed``."""
         want = (want,) if isinstance(want, str) else tuple(want)
         bad = [w for w in want if w not in self.SCORE_OUTPUTS]
         if bad or not want:
@@ -1013,14 +1017,18 @@ class Flexible_Model:
                 raise ValueError(f"x has {xd.shape[0]} images, the latents {B}")
         elif "log_q" in want or "log_px" in want:
             raise ValueError("log_q and log_px need x")
+        mt = self._observed_mask(mask, xd, B)
         with torch.cuda.stream(self._stream):
             ld = (self.x_dim + 3) // 4 * 4
             terms = {n: torch.empty(B, k, device=self.device) for n in ("log_q", "log_ph", "log_px") if n in want}
             probs = torch.empty(B * k, ld, device=self.device) if "probs" in want else None
         arr, n = _lib.fptr_array(ts)
-        self._call(self._lib.iwae_score(self._h, _lib.fptr(xd), B, k, int(chunk), arr, n,
-                                        _lib.fptr(terms.get("log_q")), _lib.fptr(terms.get("log_ph")),
-                                        _lib.fptr(terms.get("log_px")), _lib.fptr(probs), ld if probs is not None else 0))
+        outs = (_lib.fptr(terms.get("log_q")), _lib.fptr(terms.get("log_ph")), _lib.fptr(terms.get("log_px")),
+                _lib.fptr(probs), ld if probs is not None else 0)
+        if mt is None:
+            self._call(self._lib.iwae_score(self._h, _lib.fptr(xd), B, k, int(chunk), arr, n, *outs))
+        else:
+            self._call(self._lib.iwae_score_masked(self._h, _lib.fptr(xd), _lib.fptr(mt), B, k, int(chunk), arr, n, *outs))
         with torch.cuda.stream(self._stream):
             out = {n: t.t().contiguous() for n, t in terms.items()}
             if len(terms) == 3:
@@ -1043,6 +1051,10 @@ class Flexible_Model:
         are asked for).  A term with coefficient 0 is not computed unless its value
         is asked for; ``x`` may be None when neither c_q nor c_px nor their values
         need it.  Nothing is drawn."""
+        return self._score_grad(x, None, h, coef, want, chunk)
+
+    def _score_grad(self, x, mask, h, coef, want, chunk):
+        """``score_grad`` (mask None) and ``score_grad_observed``."""
         want = (want,) if isinstance(want, str) else tuple(want)
         bad = [w for w in want if w not in self.SCORE_GRAD_OUTPUTS]
         if bad or not want:
@@ -1061,15 +1073,19 @@ class Flexible_Model:
                 raise ValueError(f"x has {xd.shape[0]} images, the latents {B}")
         elif "log_q" in want or "log_px" in want or (with_g and (cf[0] != 0.0 or cf[2] != 0.0)):
             raise ValueError("log q and log p(x|h), values or gradient terms, need x")
+        mt = self._observed_mask(mask, xd, B)
         with torch.cuda.stream(self._stream):
             terms = {n: torch.empty(B, k, device=self.device) for n in ("log_q", "log_ph", "log_px") if n in want}
             gs = [torch.empty_like(t) for t in ts] if with_g else []
         arr, n = _lib.fptr_array(ts)
         garr, ng = _lib.fptr_array(gs)
         carr = (ctypes.c_float * 3)(*cf)
-        self._call(self._lib.iwae_score_grad(self._h, _lib.fptr(xd), B, k, int(chunk), arr, n, carr, garr, ng,
-                                             _lib.fptr(terms.get("log_q")), _lib.fptr(terms.get("log_ph")),
-                                             _lib.fptr(terms.get("log_px"))))
+        outs = (_lib.fptr(terms.get("log_q")), _lib.fptr(terms.get("log_ph")), _lib.fptr(terms.get("log_px")))
+        if mt is None:
+            self._call(self._lib.iwae_score_grad(self._h, _lib.fptr(xd), B, k, int(chunk), arr, n, carr, garr, ng, *outs))
+        else:
+            self._call(self._lib.iwae_score_grad_masked(self._h, _lib.fptr(xd), _lib.fptr(mt), B, k, int(chunk), arr, n,
+                                                        carr, garr, ng, *outs))
         with torch.cuda.stream(self._stream):
             out = {n: t.t().contiguous() for n, t in terms.items()}
             if len(terms) == 3:
@@ -1096,12 +1112,17 @@ class Flexible_Model:
         the last iteration, mean acceptance rate over chains and iterations,
         log p(x, h_new) [n_samples, B]); ``self.hmc_info`` keeps the last
         iteration's proposal and its H_old / H_new per chain (diagnostics)."""
+        return self._hmc(x, None, h, step_size, n_leapfrog, n_iter, momentum, u, chunk)
+
+    def _hmc(self, x, mask, h, step_size, n_leapfrog, n_iter, momentum, u, chunk):
+        """``hmc`` (mask None) and ``hmc_observed``."""
         n_leapfrog, n_iter = int(n_leapfrog), int(n_iter)
         if n_leapfrog <= 0 or n_iter <= 0:
             raise ValueError("n_leapfrog and n_iter must be positive")
         eps = float(step_size)
         ts, k, B = self._latents(h)
         xd = self._x(x)
+        mt = self._observed_mask(mask, xd, xd.shape[0])
         if momentum is not None and len(momentum) != n_iter:
             raise ValueError(f"momentum must hold {n_iter} lists (one per iteration)")
         if self._hmc_gen is None and (momentum is None or u is None):
@@ -1110,7 +1131,7 @@ class Flexible_Model:
         VALS = ("grad", "log_ph", "log_px")
 
         def joint(hs):
-            o = self.score_grad(xd, hs, coef=(0.0, 1.0, 1.0), want=VALS, chunk=chunk)
+            o = self._score_grad(xd, mt, hs, (0.0, 1.0, 1.0), VALS, chunk)
             return o["grad"], o["log_ph"] + o["log_px"]
 
         with torch.cuda.stream(self._stream):
@@ -1178,12 +1199,17 @@ class Flexible_Model:
         ``"accept_rate"`` [k, B] and ``"step"`` [k, B] (the final step sizes).
         The chain itself never waits for the host; the call synchronizes once,
         at the end (drawing the initial latents is a call of its own)."""
+        return self._ais(x, None, k, betas, n_temps, init, h0, step_size, n_leapfrog, adapt, momentum, u, step, chunk)
+
+    def _ais(self, x, mask, k, betas, n_temps, init, h0, step_size, n_leapfrog, adapt, momentum, u, step, chunk):
+        """``ais`` (mask None) and ``ais_observed``."""
         if init not in ("prior", "q"):
             raise ValueError('init must be "prior" or "q"')
         xd = self._x(x)
         B, k = xd.shape[0], int(k)
         if B <= 0 or k <= 0:
             raise ValueError("B and k must be positive")
+        mt = self._observed_mask(mask, xd, B)
         bt = np.ascontiguousarray(ais_schedule(int(n_temps)) if betas is None else betas, dtype=np.float32).ravel()
         T = bt.size - 1
         n_leapfrog = int(n_leapfrog)
@@ -1200,7 +1226,7 @@ class Flexible_Model:
             with torch.cuda.stream(self._stream):
                 hs = [t.clone() for t in ts]
         elif init == "q":
-            hs = self._encode(xd, k, chunk=chunk)[0]
+            hs = self._encode(self._observed_x(xd, mt), k, chunk=chunk)[0]
         else:
             # (iwae_generate wants an image output: the probabilities, which draw nothing more)
             hs = [t.reshape(k, B, d) for t, d in zip(self._generate(k * B, None, None, None, True, False, True)[2], dims)]
@@ -1237,9 +1263,12 @@ class Flexible_Model:
                                  step=float(step_size), adapt_inc=float(adapt[0]), adapt_dec=float(adapt[1]),
                                  step_min=float(adapt[2]), step_max=float(adapt[3]))
         harr, nh = _lib.fptr_array(hs)
-        self._call(self._lib.iwae_ais(self._h, _lib.fptr(xd), B, k, int(chunk), harr, nh, ctypes.byref(cfg),
-                                      bt.ctypes.data_as(_lib.FP), marr, nm, _lib.fptr(ut), _lib.fptr(st), _lib.fptr(lw),
-                                      _lib.fptr(acc), _lib.fptr(lpx), _lib.fptr(ess)))
+        tail = (harr, nh, ctypes.byref(cfg), bt.ctypes.data_as(_lib.FP), marr, nm, _lib.fptr(ut), _lib.fptr(st),
+                _lib.fptr(lw), _lib.fptr(acc), _lib.fptr(lpx), _lib.fptr(ess))
+        if mt is None:
+            self._call(self._lib.iwae_ais(self._h, _lib.fptr(xd), B, k, int(chunk), *tail))
+        else:
+            self._call(self._lib.iwae_ais_masked(self._h, _lib.fptr(xd), _lib.fptr(mt), B, k, int(chunk), *tail))
         with torch.cuda.stream(self._stream):
             out = {"logpx": lpx, "log_w": lw.t().contiguous(), "ess": ess, "h": hs,
                    "accept_rate": (acc / T).t().contiguous(), "step": st.t().contiguous()}
@@ -1292,6 +1321,10 @@ class Flexible_Model:
         out["logstd"])``, to continue the run: two such calls give bit for bit
         what one call over all the steps gives when the first evaluated nothing
         (``want=("bound",)``).  The call synchronizes once, at the end."""
+        return self._refine(x, None, k, n_iters, objective, lr, betas, epsilon, logstd_range, init, state, eps, chunk, want)
+
+    def _refine(self, x, mask, k, n_iters, objective, lr, betas, epsilon, logstd_range, init, state, eps, chunk, want):
+        """``refine`` (mask None) and ``refine_observed``."""
         if objective not in ("ELBO", "IWAE"):
             raise ValueError('objective must be "ELBO" or "IWAE"')
         want = (want,) if isinstance(want, str) else tuple(want)
@@ -1302,6 +1335,7 @@ class Flexible_Model:
         B, k, T = xd.shape[0], int(k), int(n_iters)
         if B <= 0 or k <= 0 or T < 0:
             raise ValueError("B and k must be positive, n_iters non-negative")
+        mt = self._observed_mask(mask, xd, B)
         if len(betas) != 2 or len(logstd_range) != 2:
             raise ValueError("betas must be (beta1, beta2), logstd_range (min, max)")
         dims = self.n_latent_encoder
@@ -1309,7 +1343,7 @@ class Flexible_Model:
         if isinstance(init, str):
             if init != "encoder":
                 raise ValueError('init must be "encoder" or a (means, logstds) pair')
-            mean, logstd = self._encoder_gaussian(xd)
+            mean, logstd = self._encoder_gaussian(self._observed_x(xd, mt))
         else:
             if len(init) != 2 or len(init[0]) != L or len(init[1]) != L:
                 raise ValueError(f"init must be (means, logstds), {L} arrays [B, d_i] each")
@@ -1353,9 +1387,12 @@ class Flexible_Model:
         sarr, _ = _lib.fptr_array(logstd)
         aarr, na = _lib.fptr_array(adam)
         harr, nh = _lib.fptr_array(hs)
-        self._call(self._lib.iwae_refine(self._h, _lib.fptr(xd), B, k, int(chunk), marr, sarr, nm, ctypes.byref(cfg),
-                                         earr, ne, aarr, na, _lib.fptr(bound), harr, nh, _lib.fptr(lw), _lib.fptr(lpx),
-                                         _lib.fptr(ess)))
+        tail = (marr, sarr, nm, ctypes.byref(cfg), earr, ne, aarr, na, _lib.fptr(bound), harr, nh, _lib.fptr(lw),
+                _lib.fptr(lpx), _lib.fptr(ess))
+        if mt is None:
+            self._call(self._lib.iwae_refine(self._h, _lib.fptr(xd), B, k, int(chunk), *tail))
+        else:
+            self._call(self._lib.iwae_refine_masked(self._h, _lib.fptr(xd), _lib.fptr(mt), B, k, int(chunk), *tail))
         out = {"mean": mean, "logstd": logstd, "state": {"adam": adam, "step": step0 + T}}
         with torch.cuda.stream(self._stream):
             if "bound" in want:
@@ -1475,6 +1512,76 @@ class Flexible_Model:
         """The k-sample estimate of log p(x_obs) per image, device [N]
         (``impute(..., want="log_px")["log_px"]``)."""
         return self.impute(x, mask, k, eps=eps, chunk=chunk, want="log_px")["log_px"]
+
+    # ---- inference on caller-controlled latents for incomplete images: the model of ``impute`` and
+    # ``train_step(mask=)`` (the encoder sees x where observed and 0 elsewhere, log p(x|h_1) sums the
+    # observed pixels, whatever x holds at a missing pixel is ignored, NaN included)
+    def _observed_mask(self, mask, xd, B):
+        """None for an unmasked call; else the device mask of an ``*_observed`` call."""
+        if mask is None:
+            return None
+        if xd is None:
+            raise ValueError("a pixel mask needs x")
+        return self._mask(mask, B)
+
+    def _observed_x(self, xd, mt):
+        """What the encoder sees: x where observed, 0 where missing (x itself without a mask)."""
+        if mt is None:
+            return xd
+        with torch.cuda.stream(self._stream):
+            return torch.where(mt != 0, xd, torch.zeros_like(xd))
+
+    @staticmethod
+    def _need_mask(mask):
+        if mask is None:
+            raise ValueError("mask is required (an all-observed call is the unmasked method's)")
+
+    def score_observed(self, x, mask, h, want=("log_q", "log_ph", "log_px"), chunk=0):
+        """``score`` for incomplete images (iwae_score_masked).  ``mask`` [B, x_dim]
+        (or x's shape): non-zero = observed.  ``"log_q"`` is log q(h | x where
+        observed, 0 elsewhere), ``"log_px"`` sums the observed pixels (exactly 0 for
+        an image with none), ``"log_ph"`` is ``score``'s; ``"probs"`` are the
+        probabilities of every pixel, observed or not.  Outputs and keys are
+        ``score``'s; ``x`` is required."""
+        self._need_mask(mask)
+        if x is None:
+            raise ValueError("x is required")
+        return self._score(x, mask, h, want, chunk)
+
+    def score_grad_observed(self, x, mask, h, coef=(0.0, 1.0, 1.0), want=("grad",), chunk=0):
+        """``score_grad`` for incomplete images (iwae_score_grad_masked): the
+        densities are ``score_observed``'s, a missing pixel pulls on nothing (an
+        image with no observed pixel has a zero likelihood gradient).  Outputs
+        and keys are ``score_grad``'s; ``x`` is required."""
+        self._need_mask(mask)
+        if x is None:
+            raise ValueError("x is required")
+        return self._score_grad(x, mask, h, coef, want, chunk)
+
+    def hmc_observed(self, x, mask, h, step_size, n_leapfrog, n_iter=1, momentum=None, u=None, chunk=0):
+        """``hmc`` with target p(h | x_obs): its torch steps on
+        ``score_grad_observed``.  Returns what ``hmc`` returns."""
+        self._need_mask(mask)
+        return self._hmc(x, mask, h, step_size, n_leapfrog, n_iter, momentum, u, chunk)
+
+    def ais_observed(self, x, mask, k, betas=None, n_temps=1000, init="prior", h0=None, step_size=0.1, n_leapfrog=10,
+                     adapt=(1.02, 0.98, 1e-4, 1.0), momentum=None, u=None, step=None, chunk=0):
+        """``ais`` for incomplete images (iwae_ais_masked): annealed importance
+        sampling of log p(x_obs).  With ``init="q"`` and no ``h0`` the initial
+        latents are the encoder's samples at x where observed, 0 elsewhere.
+        Every other parameter, and the returned dict, are ``ais``'s."""
+        self._need_mask(mask)
+        return self._ais(x, mask, k, betas, n_temps, init, h0, step_size, n_leapfrog, adapt, momentum, u, step, chunk)
+
+    def refine_observed(self, x, mask, k, n_iters=100, objective="ELBO", lr=0.01, betas=(0.9, 0.999), epsilon=1e-7,
+                        logstd_range=(-12.0, 4.0), init="encoder", state=None, eps=None, chunk=0, want=REFINE_OUTPUTS):
+        """``refine`` for incomplete images (iwae_refine_masked): q* is fitted to
+        p(h | x_obs).  ``init="encoder"`` starts from the encoder's Gaussian at x
+        where observed, 0 elsewhere; a continued run passes the same mask.
+        Every other parameter, and the returned dict, are ``refine``'s."""
+        self._need_mask(mask)
+        return self._refine(x, mask, k, n_iters, objective, lr, betas, epsilon, logstd_range, init, state, eps, chunk,
+                            want)
 
     def get_levels_of_units_activity(self, x, n_samples, eps=None):
         """F:264-F:281: per stochastic layer, the variance over the batch of
