@@ -919,6 +919,69 @@ int iwae_encode(iwae_handle* h, const float* x, int N, int k, int chunk,
 int iwae_nll_masked(iwae_handle* h, const float* x, int N, int k, const float* const* eps,
                     int n_eps, const float* const* masks, int n_masks, float* out_logpx);
 
+/* --- reweighted wake-sleep ------------------------------------------------- */
+/* Reweighted wake-sleep (Bornschein & Bengio 2015; Le et al. 2019): k samples
+ * per image, n_dream dream pairs, and the two encoder coefficients.  (1, 0) is
+ * wake-wake, (0, 1) wake-sleep, (0.5, 0.5) Bornschein & Bengio's mix. */
+typedef struct iwae_ws_config { int k; int n_dream; float c_wake, c_sleep; } iwae_ws_config;
+/* One reweighted wake-sleep step on x [B][x_dim] [dev].  Wake forward:
+ * iwae_log_weights' pass with k samples (device noise: eps NULL, n_eps 0; or
+ * injected eps[i] [k][B][d_i], n_eps = L, as iwae_train_step takes them),
+ * giving h_i, lw and sm = softmax_s(lw) per image.  Three values, float32:
+ *   L_theta = -(1/B) sum_b (logsumexp_s lw_bs - log k), the IWAE loss: the
+ *             bits of an IWAE_LOSS_IWAE iwae_train_step / iwae_forward_backward
+ *             on the same noise and path, and of -iwae_bound wherever a train
+ *             step's forward and a bound's use the same products (every GEMM
+ *             under iwae_set_precision(h, 0));
+ *   L_wake  = -(1/B) sum_b sum_s sm_bs log q(h_bs | x_b), sm and h constants;
+ *   L_sleep = -(1/n) sum_j log q(h^j | x^j) over the n = n_dream dream pairs.
+ * Gradient buffer: the decoder's parameters get grad L_theta (exactly an
+ * IWAE_LOSS_IWAE step's), the encoder's c_wake grad L_wake + c_sleep grad
+ * L_sleep: per head -a z/s on mu and -a (z^2 - 1)(s - 1e-6)/s on zs, row
+ * weight a = c_wake sm_bs / B (wake rows) or c_sleep / n (dream rows), through
+ * head -> l2 -> l1 into that layer's weight gradients only: the latent a
+ * layer reads is data, there is no dL/dh into another layer.  A coefficient
+ * of exactly 0 leaves its phase out of every launch (not even a NaN of it
+ * reaches the encoder's gradient) and its value is reported as 0.
+ * Dreams: dream_x [n][x_dim] [dev] (the encoder's input) with dream_lat[i]
+ * [n][d_i] [dev], encoder order h_1 .. h_L, n_dream_lat = L; or both NULL
+ * (n_dream_lat 0) with n_dream > 0: the step dreams its own from the current
+ * weights by one internal iwae_generate(n, h_top NULL, device noise, pixels
+ * and h_out), bit for bit that call's result at that noise position, on the
+ * generation path that call takes.  With c_sleep == 0 dream buffers are never
+ * read.  The noise position advances once for the wake forward and once more
+ * iff the step dreamt its own.
+ * values_dev [dev], 3 floats (L_theta, L_wake, L_sleep), may be NULL.
+ * iwae_wake_sleep_step then applies the handle's Adam to the whole buffer (the
+ * Adam launch an f32 row-block or layer-wise train step ends in);
+ * iwae_wake_sleep_grad leaves the gradient in the buffer (iwae_get_grads,
+ * iwae_apply_adam) and the Adam state untouched.
+ * Paths: chosen as IWAE_LOSS_IWAE_STL's are, over B k + n_dream rows: the f32
+ * row-block kernels (rb_bwd_kernel's GM_FIT jobs; the dream rows' encoder
+ * forward on rb_fwd_kernel with the target-given density epilogue), else the
+ * layer-wise GEMMs (gauss_bwd_enc_kernel's GM_FIT launches), never an error;
+ * never the bf16x3 engine, the fused update or the weight ring.
+ * iwae_set_graphs does not apply: every launch is enqueued on the handle's
+ * stream, with no host synchronisation unless a workspace grows (before
+ * anything is enqueued).  No float atomics; deterministic.  The dream rows
+ * lie behind the wake rows in the train step's workspace, which grows to
+ * B + n_dream image rows and B k + n_dream sample rows; captured train-step
+ * graphs and engine plans survive a call that does not grow it.
+ * IWAE_EINVAL, nothing launched and the noise position untouched (after the
+ * sticky iwae_status error, returned first): cfg or x NULL; k < 1 or B < 1; a
+ * coefficient negative or not finite; both 0; c_sleep > 0 with n_dream < 1;
+ * c_sleep == 0 with n_dream != 0; only one of dream_x and dream_lat; n_dream_lat
+ * not L with dream_lat and not 0 without; a NULL dream_lat[i]; a wrong n_eps
+ * or a NULL eps[i]; B k + n_dream above 2^30; a data-parallel world > 1. */
+int iwae_wake_sleep_step(iwae_handle* h, const iwae_ws_config* cfg, const float* x, int B,
+                         const float* const* eps, int n_eps,
+                         const float* dream_x, const float* const* dream_lat, int n_dream_lat,
+                         float* values_dev);
+int iwae_wake_sleep_grad(iwae_handle* h, const iwae_ws_config* cfg, const float* x, int B,
+                         const float* const* eps, int n_eps,
+                         const float* dream_x, const float* const* dream_lat, int n_dream_lat,
+                         float* values_dev);
+
 /* --- diagnostics ---------------------------------------------------------- */
 /* C[M][N] = A[M][K] @ B[K][N] (all [dev], row-major, leading dims given) via
  * the f32 MFMA GEMM used on the hot path (unit-test entry). */
@@ -974,7 +1037,12 @@ double iwae_workspace_bytes(const iwae_handle* h);
  * masked fused score_kernel launches, 32 masked layer-wise score passes, 33
  * masked fused sg_kernel launches, 34 masked layer-wise score-gradient passes
  * (iwae_ais_masked and iwae_refine_masked count under 27-30 as their
- * siblings do); -1 for an unknown id. */
+ * siblings do); iwae_wake_sleep_step / iwae_wake_sleep_grad: 35 calls that
+ * enqueued work, 36 GM_FIT jobs issued on rb_bwd_kernel (one per encoder
+ * layer of a row-block call), 37 GM_FIT launches of gauss_bwd_enc_kernel (one
+ * per encoder layer of a layer-wise call), 38 dream generations the step ran
+ * itself (also counted under 10 where gen_kernel ran them); -1 for an unknown
+ * id. */
 long long iwae_debug_count(const iwae_handle* h, int what);
 /* Live kernel timing: bracket every launch of one kernel class with HIP events
  * on the handle's stream -- a GEMM class (kind: 0 forward, 1 backward-data,

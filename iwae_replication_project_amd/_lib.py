@@ -63,6 +63,10 @@ class IwaeRefineConfig(ctypes.Structure):
     ]
 
 
+class IwaeWsConfig(ctypes.Structure):
+    _fields_ = [("k", c_int), ("n_dream", c_int), ("c_wake", c_float), ("c_sleep", c_float)]
+
+
 FP = POINTER(c_float)
 FPP = POINTER(FP)
 H = c_void_p
@@ -140,6 +144,8 @@ SIGNATURES = {
     "iwae_profile_gemm": (c_int, [H, c_int, c_int]),
     "iwae_profile_read": (c_int, [H, POINTER(c_double), POINTER(c_double), POINTER(c_longlong)]),
     "iwae_profile_replay": (c_int, [H, c_int, POINTER(c_double), POINTER(c_double)]),
+    "iwae_wake_sleep_step": (c_int, [H, POINTER(IwaeWsConfig), FP, c_int, FPP, c_int, FP, FPP, c_int, FP]),
+    "iwae_wake_sleep_grad": (c_int, [H, POINTER(IwaeWsConfig), FP, c_int, FPP, c_int, FP, FPP, c_int, FP]),
 }
 
 _lib = None

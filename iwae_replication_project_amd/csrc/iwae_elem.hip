@@ -130,13 +130,16 @@ hipError_t launch_gauss_fwd(hipStream_t st, int mode, const GaussArgs& a) {
 // Mode 0 (encoder sampling layer): block = 4 P-rows (prow_div == 1) or one
 // image (prow_div > 1; waves split its rows, LDS combine).  grad_mode keeps
 // both kinds of partials (GM_TOTAL) or one of them (GradMode, iwae_kernels.h).
+// GM_FIT: the density partials weighted by the row weight in a.dlw, no eps and
+// no dL/dh sources read; per image, P rows from nk_img on own one row of H.
 __global__ __launch_bounds__(256) void gauss_bwd_enc_kernel(GaussBwdArgs a) {
   __shared__ float red[2][4][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const bool per_image = a.prow_div > 1;
   const int pr = per_image ? blockIdx.x : blockIdx.x * 4 + wave;
-  const int nP = (a.M + a.prow_div - 1) / a.prow_div;
+  const int nP = gauss_bwd_prows(a);
   const bool row_ok = pr < nP;
+  const bool fit = a.grad_mode == GM_FIT;
   const float* __restrict__ H = a.H;
   const float* __restrict__ E = a.eps_rows;
   const float* __restrict__ DL = a.dlw;
@@ -156,17 +159,21 @@ __global__ __launch_bounds__(256) void gauss_bwd_enc_kernel(GaussBwdArgs a) {
     }
     float amu = 0.f, asc = 0.f;
     if (act) {
-      const int r_begin = pr * a.prow_div;
+      int r_begin = pr * a.prow_div;
       const int s_begin = per_image ? wave : 0, s_step = per_image ? 4 : 1;
-      const int s_end = min(a.prow_div, a.M - r_begin);
+      int s_end = min(a.prow_div, a.M - r_begin);
+      if (a.nk_img > 0 && pr >= a.nk_img) {      // a dream row: one row of H, behind the sample rows
+        r_begin = a.nk_img * a.prow_div + (pr - a.nk_img);
+        s_end = 1;
+      }
 #pragma unroll 4
       for (int s = s_begin; s < s_end; s += s_step) {
         const int r = r_begin + s;
         const float h = H[(size_t)r * a.ldH + j];
-        const float ev = E[(size_t)r * a.ld_eps + j];
+        const float ev = fit ? 0.f : E[(size_t)r * a.ld_eps + j];
         const float dl = DL[r], dlq = -dl;
         const float z = h * rs - mu * rs;
-        if (a.grad_mode == GM_DENSITY) {
+        if (a.grad_mode == GM_DENSITY || fit) {
           amu += dlq * (z * rs);
           asc += dlq * ((z * z - 1.f) * rs);
           continue;
@@ -234,12 +241,76 @@ __global__ __launch_bounds__(256) void gauss_bwd_prior_kernel(GaussBwdArgs a) {
 hipError_t launch_gauss_bwd(hipStream_t st, int mode, const GaussBwdArgs& a) {
   if (a.M <= 0) return hipSuccess;
   if (mode == 0) {
-    const int nP = (a.M + a.prow_div - 1) / a.prow_div;
+    const int nP = gauss_bwd_prows(a);
     dim3 grid(a.prow_div > 1 ? nP : (nP + 3) / 4);
     hipLaunchKernelGGL(gauss_bwd_enc_kernel, grid, dim3(256), 0, st, a);
   } else {
     hipLaunchKernelGGL(gauss_bwd_prior_kernel, dim3((a.M + 3) / 4), dim3(256), 0, st, a);
   }
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------- wake-sleep step
+__global__ __launch_bounds__(256) void ws_stage_kernel(WsStageArgs a) {
+  const int q = blockIdx.y;
+  const int w = a.width[q];
+  const float* __restrict__ src = a.src[q];
+  float* __restrict__ dst = a.dst[q];
+  const long long tot = (long long)a.n * w;
+  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < tot; e += (long long)gridDim.x * blockDim.x) {
+    const long long r = e / w;
+    const int c = (int)(e - r * w);
+    dst[r * a.ld_dst[q] + c] = src[r * a.ld_src[q] + c];
+  }
+}
+
+hipError_t launch_ws_stage(hipStream_t st, const WsStageArgs& a) {
+  if (a.n <= 0 || a.nbuf <= 0) return hipSuccess;
+  int wmax = 1;
+  for (int q = 0; q < a.nbuf; ++q) wmax = wmax > a.width[q] ? wmax : a.width[q];
+  const long long blocks = std::min<long long>(((long long)a.n * wmax + 255) / 256, 1024);
+  hipLaunchKernelGGL(ws_stage_kernel, dim3((unsigned)blocks, (unsigned)a.nbuf), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void ws_weights_kernel(const float* __restrict__ dlw, float* __restrict__ w, int M,
+                                                         int n, float c_wake, float a_sleep) {
+  const int r0 = c_wake != 0.f ? 0 : M;           // (c_wake == 0: the wake rows are never read)
+  for (int r = r0 + blockIdx.x * blockDim.x + threadIdx.x; r < M + n; r += gridDim.x * blockDim.x)
+    w[r] = r < M ? -c_wake * dlw[r] : a_sleep;
+}
+
+hipError_t launch_ws_weights(hipStream_t st, const float* dlw, float* w, int M, int n, float c_wake, float a_sleep) {
+  const int rows = (c_wake != 0.f ? M : 0) + n;
+  if (rows <= 0) return hipSuccess;
+  hipLaunchKernelGGL(ws_weights_kernel, dim3(std::min((rows + 255) / 256, 1024)), dim3(256), 0, st, dlw, w, M, n,
+                     c_wake, a_sleep);
+  return hipGetLastError();
+}
+
+// thread t sums its rows t, t + 256, ... in order; lanes by wave_sum's fixed
+// butterfly, the four waves in order
+__global__ __launch_bounds__(256) void ws_values_kernel(const float* __restrict__ dlw, const float* __restrict__ logq,
+                                                        int M, int n, int wake, float* __restrict__ values) {
+  __shared__ float red[2][4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float sw = 0.f, ss = 0.f;
+  if (wake)
+    for (int r = threadIdx.x; r < M; r += 256) sw += dlw[r] * logq[r];
+  for (int j = threadIdx.x; j < n; j += 256) ss += logq[M + j];
+  sw = wave_sum(sw);
+  ss = wave_sum(ss);
+  if (lane == 0) { red[0][wave] = sw; red[1][wave] = ss; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    values[0] = wake ? ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3] : 0.f;
+    values[1] = n > 0 ? -((((red[1][0] + red[1][1]) + red[1][2]) + red[1][3]) / (float)n) : 0.f;
+  }
+}
+
+hipError_t launch_ws_values(hipStream_t st, const float* dlw, const float* logq, int M, int n, int wake,
+                            float* values) {
+  hipLaunchKernelGGL(ws_values_kernel, dim3(1), dim3(256), 0, st, dlw, logq, M, n, wake, values);
   return hipGetLastError();
 }
 

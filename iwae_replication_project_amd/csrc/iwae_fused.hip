@@ -517,8 +517,9 @@ __global__ __launch_bounds__(RB_WAVES * 64) void rb_bwd_kernel(RbBwdLaunch L) {
           zs[q] = Pr[d + c];
           hv[q] = Hr[c];
           // pro 2 has no eps / dh sources: every such load reads 0 (kOOB)
+          // (nor has a GM_FIT job: its eps is null)
           const bool p1 = J.pro == 1;
-          ev[q] = bld1(reps, p1 ? (unsigned)(rg * J.ld_eps + c) * 4u : kOOB);
+          ev[q] = bld1(reps, (p1 && J.gmode != GM_FIT) ? (unsigned)(rg * J.ld_eps + c) * 4u : kOOB);
           G[q] = 0.f;
 #pragma unroll
           for (int u = 0; u < 4; ++u)
@@ -546,7 +547,8 @@ __global__ __launch_bounds__(RB_WAVES * 64) void rb_bwd_kernel(RbBwdLaunch L) {
             if (J.gmode == GM_PATH) {
               dmu = Gq;
               dsc = Gq * ev[q];
-            } else if (J.gmode == GM_DENSITY) {
+            } else if (J.gmode == GM_DENSITY || J.gmode == GM_FIT) {
+              // (GM_FIT: dl is the row's weight a, so these are -a z/s and -a (z^2 - 1)/s)
               dmu = dlq * (z * rs);
               dsc = dlq * ((z * z - 1.f) * rs);
             } else {
@@ -572,7 +574,10 @@ __global__ __launch_bounds__(RB_WAVES * 64) void rb_bwd_kernel(RbBwdLaunch L) {
     // pro 3: first encoder layer, rows = images; reduce the sampling-layer
     // partials over the kS sample rows of each image (mu, scale broadcast over k).
     // Thread t: column quad t % nq, samples s = t / nq (+ sgroups ...).
+    // GM_FIT: the density partials weighted by the row weight in J.dlw (no eps,
+    // no sources); images from nk_img on own one row behind the sample rows.
     const int d = J.d, kS = J.kS;
+    const bool fit = J.gmode == GM_FIT;
     const int t = threadIdx.x;
     const int nq = (d + 3) >> 2;
     const int sgroups = max(1, (int)blockDim.x / nq);
@@ -596,15 +601,17 @@ __global__ __launch_bounds__(RB_WAVES * 64) void rb_bwd_kernel(RbBwdLaunch L) {
           sc[q] = ez[q] + kScaleEps;
           rs[q] = frcp(sc[q]);
         }
+        const bool one = J.nk_img > 0 && img >= J.nk_img;
+        const int rg0 = one ? J.nk_img * kS + (img - J.nk_img) : img * kS, cnt = one ? 1 : kS;
 #pragma unroll 4
-        for (int s = sg; s < kS; s += sgroups) {
-          const int rg = img * kS + s;
+        for (int s = sg; s < cnt; s += sgroups) {
+          const int rg = rg0 + s;
           float hv[4], ev[4], G[4];
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const int c = min(4 * gq + q, d - 1);
             hv[q] = J.H[(size_t)rg * J.ldH + c];
-            ev[q] = J.eps[(size_t)rg * J.ld_eps + c];
+            ev[q] = fit ? 0.f : J.eps[(size_t)rg * J.ld_eps + c];
             G[q] = 0.f;
 #pragma unroll
             for (int u = 0; u < 4; ++u)
@@ -620,6 +627,9 @@ __global__ __launch_bounds__(RB_WAVES * 64) void rb_bwd_kernel(RbBwdLaunch L) {
             if (J.gmode == GM_PATH) {
               amu[q] += Gq;
               asc[q] += Gq * ev[q];
+            } else if (fit) {
+              amu[q] += dlq * (z * rs[q]);
+              asc[q] += dlq * ((z * z - 1.f) * rs[q]);
             } else {
               amu[q] += Gq + dlq * (z * rs[q]);
               asc[q] += Gq * ev[q] + dlq * ((z * z - 1.f) * rs[q]);

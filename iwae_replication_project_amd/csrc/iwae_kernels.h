@@ -262,7 +262,11 @@ hipError_t launch_gauss_fwd(hipStream_t st, int mode, const GaussArgs& a);
 //   GM_PATH     dmu = dht,            dsc = dht eps    (through the sample only: STL / DReG)
 //   GM_DENSITY  dmu = dlq z/s,        dsc = dlq (z^2 - 1)/s   (through (mu, s) only; no dL/dh
 //               sources: the chain below it yields the density's dL/dh of the layer underneath)
-enum GradMode { GM_TOTAL = 0, GM_PATH = 1, GM_DENSITY = 2 };
+//   GM_FIT      the density partials of the loss -a log q(h | .) at fixed h, a = the row's weight
+//               read where the other modes read dL/dlw: dmu = -a z/s, dsc = -a (z^2 - 1)/s.  No
+//               dL/dh sources, no eps, no dX below (the latent a layer reads is data); also on the
+//               first encoder layer (reduced over an image's rows).  iwae_wake_sleep_step's mode.
+enum GradMode { GM_TOTAL = 0, GM_PATH = 1, GM_DENSITY = 2, GM_FIT = 3 };
 
 struct GaussBwdArgs {
   const float* P; int ldP; int prow_div; int d;
@@ -275,11 +279,38 @@ struct GaussBwdArgs {
   float* dP; int lddP;       // (dmu | dzs) per P row
   float* dh_out; int ldh_out;  // prior mode: dL/dh of the target
   int M;                     // rows of H
-  int grad_mode;             // encoder mode: GM_TOTAL (0), GM_PATH or GM_DENSITY
+  int grad_mode;             // encoder mode: GM_TOTAL (0), GM_PATH, GM_DENSITY or GM_FIT
+  int nk_img;                // GM_FIT, prow_div > 1: P rows from nk_img on own ONE row of H each, behind the
+                             // nk_img * prow_div rows of the first nk_img (the dream rows); 0: every P row owns prow_div
 };
+// P rows of an encoder Gaussian backward over M rows of H
+__host__ __device__ inline int gauss_bwd_prows(const GaussBwdArgs& a) {
+  if (a.nk_img > 0) return a.nk_img + (a.M - a.nk_img * a.prow_div);
+  return (a.M + a.prow_div - 1) / a.prow_div;
+}
 // mode 0: backward of an encoder sampling layer -> dP (reduced over prow_div rows)
 // mode 1: backward of a decoder prior head      -> dP (per row) and dh_out
 hipError_t launch_gauss_bwd(hipStream_t st, int mode, const GaussBwdArgs& a);
+
+// ------------------------------------------------------ wake-sleep step ----
+// Dream rows into the workspace (iwae_wake_sleep_step): buffer q's n rows of
+// width[q] floats from src[q] (row stride ld_src[q]) to dst[q] (row stride
+// ld_dst[q]); the ones column and the padding of the destination rows stay.
+struct WsStageArgs {
+  const float* src[9]; float* dst[9];
+  int width[9], ld_src[9], ld_dst[9];
+  int n, nbuf;
+};
+hipError_t launch_ws_stage(hipStream_t st, const WsStageArgs& a);
+// Row weights of the GM_FIT backward: w[r] = -c_wake dlw[r] on the wake rows
+// r < M (c_wake softmax / B; not written, dlw not read, when c_wake == 0),
+// w[M + j] = a_sleep on the n dream rows.
+hipError_t launch_ws_weights(hipStream_t st, const float* dlw, float* w, int M, int n, float c_wake, float a_sleep);
+// values[0] = sum_{r < M} dlw[r] logq[r]  (L_wake; 0 when !wake),
+// values[1] = -(1/n) sum_j logq[M + j]    (L_sleep; 0 when n == 0):
+// one workgroup, fixed summation order, no atomics.
+hipError_t launch_ws_values(hipStream_t st, const float* dlw, const float* logq, int M, int n, int wake,
+                            float* values);
 
 // --------------------------------------------------------------- bounds ----
 // BM_SM2: value as BM_IWAE, row weights the squared softmax (e/se)^2 (DReG's encoder weighting)
@@ -531,6 +562,8 @@ struct RbBwdJob {
   float* dP_out; int ld_dP; float* dh_out; int ld_dh;   // (pro 1: dP_out may be null -- a dX-only density job)
   int nst; RbStage st[3];
   int gmode;                 // pro 1 / 3: GradMode of the sampling layer's partials
+  int nk_img;                // pro 3, GM_FIT: images from nk_img on own ONE row each, behind the nk_img * kS rows
+                             // of the first nk_img (the dream rows); 0: every image owns kS rows
 };
 struct RbBwdLaunch {
   RbBwdJob job[kRbMaxJobs];

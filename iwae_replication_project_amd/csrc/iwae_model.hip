@@ -220,6 +220,9 @@ struct Counters {
   long long refine = 0, refine_launch = 0;   // 29, 30: iwae_refine iterations / its begin, step and end launches
   long long score_pix = 0, score_pix_lw = 0;   // 31, 32: pixel-masked iwae_score chunks: masked score_kernel launches / layer-wise passes
   long long sgrad_pix = 0, sgrad_pix_lw = 0;   // 33, 34: pixel-masked iwae_score_grad chunks: masked sg_kernel launches / layer-wise passes
+  long long ws = 0;                      // 35: wake-sleep calls that enqueued work
+  long long ws_rb = 0, ws_gauss = 0;     // 36, 37: GM_FIT jobs issued on rb_bwd_kernel / GM_FIT launches of gauss_bwd_enc_kernel
+  long long ws_dream = 0;                // 38: dream generations a wake-sleep step ran itself
 };
 
 // row-chain train engine plan (device resident, per shape; iwae_train.hip)
@@ -313,6 +316,8 @@ struct iwae_handle {
   size_t ais_ws_floats = 0;          // terms, and the weights / steps the caller did not give): its own allocation
   float* refine_ws = nullptr;        // iwae_refine's samples (latents, noise, gradients per layer; the value terms,
   size_t refine_ws_floats = 0;       // the weights, and the Adam moments the caller did not give): its own allocation
+  float* ws_ws = nullptr;            // iwae_wake_sleep_step's own dreams (pixels [n][r4(x_dim)], then h_1 .. h_L
+  size_t ws_ws_floats = 0;           // [n][d_i]) and its three values when the caller wants none: its own allocation
   float* loss_slots = nullptr;       // multi-step graphs: step j's loss (kGraphSteps floats), then
                                      // [kGraphSteps, 2 kGraphSteps): where a graph's copy node writes
                                      // when the call wants no losses
@@ -854,8 +859,13 @@ static int prior_fwd(iwae_handle* h, int M, float* out = nullptr) {
   return IWAE_OK;
 }
 
+static int layerwise_forward(iwae_handle* h, const Plan& P, const EpsSet& E, bool train);
 static int forward_core(iwae_handle* h, const Plan& P, const EpsSet& E, bool train) {
   if (use_fused(h, P)) return fused_forward(h, P, E, train);
+  return layerwise_forward(h, P, E, train);
+}
+
+static int layerwise_forward(iwae_handle* h, const Plan& P, const EpsSet& E, bool train) {
   const int kS = P.kS, M = P.Bimg * kS;
   CHK(encoder_fwd(h, P, E, train));
   CHK(prior_fwd(h, M));
@@ -1724,9 +1734,8 @@ static std::vector<WJob> layer_jobs(const iwae_handle* h, const Plan& P, WGroups
   return js;
 }
 
-// weight gradients (X_aug^T dZ, split over rows) of the groups' layers in grouped launches
-static int weight_grads(iwae_handle* h, const Plan& P, WGroups groups) {
-  const std::vector<WJob> js = layer_jobs(h, P, groups);
+// weight-gradient jobs (X_aug^T dZ, split over rows) in grouped launches
+static int weight_grad_jobs(iwae_handle* h, const std::vector<WJob>& js) {
   for (size_t b = 0; b < js.size(); b += kMaxGroup) {
     GemmGroup gg{};
     for (size_t q = b; q < std::min(js.size(), b + kMaxGroup); ++q) {
@@ -1738,6 +1747,11 @@ static int weight_grads(iwae_handle* h, const Plan& P, WGroups groups) {
     HIPCHK(launch_gemm_group_bwd_weight(h->stream, gg));
   }
   return IWAE_OK;
+}
+
+// ... of the groups' layers
+static int weight_grads(iwae_handle* h, const Plan& P, WGroups groups) {
+  return weight_grad_jobs(h, layer_jobs(h, P, groups));
 }
 
 // Fused update (iwae_update.hip): every weight gradient over all the step's rows,
@@ -3328,6 +3342,7 @@ void iwae_destroy(iwae_handle* h) {
   if (h->sg_ws) (void)hipFree(h->sg_ws);
   if (h->ais_ws) (void)hipFree(h->ais_ws);
   if (h->refine_ws) (void)hipFree(h->refine_ws);
+  if (h->ws_ws) (void)hipFree(h->ws_ws);
   if (h->nr_units) (void)hipFree(h->nr_units);
   if (h->nrb_units) (void)hipFree(h->nrb_units);
   if (h->nre_units) (void)hipFree(h->nre_units);
@@ -5760,6 +5775,293 @@ int iwae_nll_masked(iwae_handle* h, const float* x, int N, int k, const float* c
   return rc;
 }
 
+// ------------------------------------------------ reweighted wake-sleep step
+// iwae_wake_sleep_step / _grad.  The decoder takes the IWAE
+// gradient of the wake forward; every encoder layer is a weighted regression of
+// log q(h_i | input) at fixed latents (GM_FIT) over two row sets laid out one
+// behind the other in the train step's own activation buffers: the wake rows
+// (B image rows / B k sample rows, weight c_wake softmax / B) and the n dream
+// rows behind them (weight c_sleep / n), so one weight-gradient job per Dense
+// sums both in a fixed order.  A phase whose coefficient is 0 is outside every
+// row range: none of its rows is read.
+static Mat rows_from(const Mat& m, long long r) {
+  Mat o = m;
+  if (o.p) o.p += r * o.ld;
+  return o;
+}
+static LayerBufs rows_from(const LayerBufs& b, long long r) {
+  LayerBufs o;
+  o.y1 = rows_from(b.y1, r); o.y2 = rows_from(b.y2, r); o.P = rows_from(b.P, r);
+  o.dP = rows_from(b.dP, r); o.dY2 = rows_from(b.dY2, r); o.dY1 = rows_from(b.dY1, r);
+  return o;
+}
+
+// Moves workspace pointers r rows down for its lifetime, so a routine written
+// for rows [0, n) of the handle's buffers runs on rows [r, r + n) instead.
+struct RowShift {
+  std::vector<std::pair<float**, long long>> moved;
+  void mat(Mat& m, long long r) {
+    if (!m.p) return;
+    m.p += r * m.ld;
+    moved.push_back({&m.p, r * m.ld});
+  }
+  void vec(float*& p, long long r) {
+    p += r;
+    moved.push_back({&p, r});
+  }
+  ~RowShift() {
+    for (auto& q : moved) *q.first -= q.second;
+  }
+};
+
+static bool ws_use_fused(const iwae_handle* h, long long rows) {
+  if (h->path == 1 || h->L > kRbMaxJobs || h->masked || !rb_width_ok(h)) return false;
+  return h->path == 2 || rows <= 65536;
+}
+
+// the encoder forward at the n dream rows' given latents: y1, y2 and P kept
+// for the weight gradient, log q(h^j | x^j) into logq[M + j]
+static int ws_sleep_forward(iwae_handle* h, const Plan& P, int n, bool fusedp) {
+  const int L = h->L, B = P.Bimg, M = P.Bimg * P.kS;
+  Plan P2 = P;
+  P2.B = P2.Bimg = P2.Bsplit = n; P2.kS = 1;
+  if (fusedp) {
+    // the first encoder layer's own launches (few-row or split-K GEMM + row-block job) on the image rows behind B
+    RowShift sh;
+    sh.mat(h->x_in, B); sh.mat(h->eb[0].y1, B); sh.mat(h->eb[0].y2, B); sh.mat(h->eb[0].P, B);
+    h->step.x_user = nullptr;
+    CHK(enc0_forward(h, P2));
+  } else {
+    LayerBufs b0 = rows_from(h->eb[0], B);
+    CHK(stoch_fwd(h, h->enc[0], rows_from(h->x_in, B), n, b0));
+  }
+  for (int i = 0; i < L; ++i) {
+    const StochL& S = h->enc[i];
+    LayerBufs b = rows_from(h->eb[i], i == 0 ? B : M);
+    Mat tgt = rows_from(h->h[i], M);
+    if (i > 0 && fusedp) {
+      Mat in = rows_from(h->h[i - 1], M);
+      RbFwdLaunch Lf{};
+      Lf.ld_lds = rb_ld(h, false);
+      RbFwdJob& J = Lf.job[0];
+      J.rows = n; J.rpb = 16;
+      J.in = in.p; J.ld_in = in.ld;
+      J.nst = 3;
+      J.st[0] = rb_fwd_stage(h, S.l1, 1, &b.y1);
+      J.st[1] = rb_fwd_stage(h, S.l2, 1, &b.y2);
+      J.st[2] = rb_fwd_stage(h, S.head, 0, &b.P);
+      // the target-given density epilogue (the decoder prior's), accumulated into the dream rows' log q
+      J.epi = 2; J.ep_d = S.d; J.ep_tgt = tgt.p; J.ep_ldtgt = tgt.ld;
+      J.logp = h->logq + M; J.logp_acc = 1;
+      Lf.njobs = 1;
+      CHK(run_rb_fwd(h, Lf));
+      continue;
+    }
+    if (i > 0) CHK(stoch_fwd(h, S, rows_from(h->h[i - 1], M), n, b));
+    GaussArgs g{};
+    g.P = b.P.p; g.ldP = b.P.ld; g.prow_div = 1; g.d = S.d;
+    g.H = tgt.p; g.ldH = tgt.ld;
+    g.out = h->logq + M; g.accumulate = i > 0; g.M = n;
+    HIPCHK(launch_gauss_fwd(h->stream, 1, g));
+  }
+  return IWAE_OK;
+}
+
+// GM_FIT backward of every encoder layer over image rows [i0, B + n) / sample
+// rows [r0, M + n) and the layers' weight gradients; w: the row weights
+static int ws_encoder_fit(iwae_handle* h, const Plan& P, int n, bool wake, const float* w, bool fusedp) {
+  const int L = h->L, B = P.Bimg, M = P.Bimg * P.kS;
+  const int i0 = wake ? 0 : B, r0 = wake ? 0 : M;
+  // images that own kS rows of h_1 each (the wake images), then one row each
+  // (the dream images); with kS == 1, or without the wake rows, image rows and
+  // sample rows run side by side
+  const bool per_image = wake && P.kS > 1;
+  std::vector<Mat> keep;
+  keep.reserve(6 * (size_t)L);
+  std::vector<WJob> js;
+  for (int i = L - 1; i >= 0; --i) {
+    const StochL& S = h->enc[i];
+    const int off = i == 0 ? i0 : r0, rows = (i == 0 ? B : M) + n - off;
+    LayerBufs b = rows_from(h->eb[i], off);
+    const Mat Hm = rows_from(h->h[i], r0);
+    const Mat in = i == 0 ? rows_from(h->x_in, i0) : rows_from(h->h[i - 1], r0);
+    const int kS = i == 0 && per_image ? P.kS : 1;
+    const int nk = i == 0 && per_image && n > 0 ? B : 0;
+    if (fusedp) {
+      RbBwdLaunch Lb{};
+      Lb.ld_lds = rb_ld(h, true);
+      RbBwdJob& J = Lb.job[0];
+      J.pro = i == 0 ? 3 : 1;
+      J.rows = rows; J.rpb = i == 0 ? 1 : 16;
+      J.kS = kS; J.nk_img = nk;
+      J.P = b.P.p; J.ldP = b.P.ld; J.d = S.d;
+      J.H = Hm.p; J.ldH = Hm.ld;
+      J.dlw = w + r0;
+      J.gmode = GM_FIT;
+      J.dP_out = b.dP.p; J.ld_dP = b.dP.ld;
+      // two stages, dY2 and dY1: no dX below (the layer's input is data)
+      const bool sm0 = i == 0 && smallm_ok(h, rows);
+      J.nst = sm0 ? 0 : 2;
+      if (!sm0) {
+        J.st[0] = rb_bwd_stage(h, S.head, &b.y2, &b.dY2);
+        J.st[1] = rb_bwd_stage(h, S.l2, &b.y1, &b.dY1);
+      }
+      Lb.njobs = 1;
+      HIPCHK(launch_rb_bwd(h->stream, Lb));
+      h->count.ws_rb++;
+      if (sm0) {
+        CHK(smallm(h, b.dP, rows, h->dense[S.head], true, 2, &b.y2, b.dY2));
+        CHK(smallm(h, b.dY2, rows, h->dense[S.l2], true, 2, &b.y1, b.dY1));
+      }
+      const size_t q = keep.size();
+      for (const Mat& m : {in, b.dY1, b.y1, b.dY2, b.y2, b.dP}) keep.push_back(m);
+      const WGroup grp = i == 0 ? WG_ENC0 : WG_ENC;
+      js.push_back({S.l1, &keep[q], &keep[q + 1], rows, nullptr, grp});
+      js.push_back({S.l2, &keep[q + 2], &keep[q + 3], rows, nullptr, grp});
+      js.push_back({S.head, &keep[q + 4], &keep[q + 5], rows, nullptr, grp});
+    } else {
+      GaussBwdArgs g{};
+      g.P = b.P.p; g.ldP = b.P.ld; g.prow_div = kS; g.d = S.d;
+      g.H = Hm.p; g.ldH = Hm.ld;
+      g.dlw = w + r0;
+      g.grad_mode = GM_FIT; g.nk_img = nk;
+      g.dP = b.dP.p; g.lddP = b.dP.ld;
+      g.M = M + n - r0;
+      HIPCHK(launch_gauss_bwd(h->stream, 0, g));
+      h->count.ws_gauss++;
+      CHK(stoch_bwd(h, S, in, rows, b, true, nullptr));      // (no dx: the third dX GEMM is not issued)
+    }
+  }
+  // row-block path: the encoder's weight gradients in grouped launches
+  return weight_grad_jobs(h, js);
+}
+
+static int do_wake_sleep(iwae_handle* h, const iwae_ws_config* cfg, const float* x, int B, const float* const* eps,
+                         int n_eps, const float* dream_x, const float* const* dream_lat, int n_dream_lat,
+                         float* values_dev, bool adam) {
+  if (!h) return IWAE_EINVAL;
+  CHK(kernel_status(h));
+  if (!cfg) return fail(h, IWAE_EINVAL, "wake-sleep config is NULL");
+  if (!x) return fail(h, IWAE_EINVAL, "x is NULL");
+  if (cfg->k < 1) return fail(h, IWAE_EINVAL, "k must be positive");
+  if (B < 1) return fail(h, IWAE_EINVAL, "batch must be positive");
+  const float cw = cfg->c_wake, cs = cfg->c_sleep;
+  if (!std::isfinite(cw) || !std::isfinite(cs) || cw < 0.f || cs < 0.f)
+    return fail(h, IWAE_EINVAL, "c_wake and c_sleep must be finite and not negative");
+  if (cw == 0.f && cs == 0.f) return fail(h, IWAE_EINVAL, "c_wake and c_sleep are both 0");
+  const int n = cfg->n_dream;
+  if (cs > 0.f && n < 1) return fail(h, IWAE_EINVAL, "c_sleep > 0 needs n_dream >= 1");
+  if (cs == 0.f && n != 0) return fail(h, IWAE_EINVAL, "c_sleep == 0 needs n_dream == 0");
+  if ((dream_x != nullptr) != (dream_lat != nullptr))
+    return fail(h, IWAE_EINVAL, "dream_x and dream_lat go together (both, or neither for the step's own dreams)");
+  const int L = h->L;
+  if (n_dream_lat != (dream_lat ? L : 0))
+    return fail(h, IWAE_EINVAL, "n_dream_lat must be " + std::to_string(L) + " with dream_lat and 0 without");
+  for (int i = 0; dream_lat && i < L; ++i)
+    if (!dream_lat[i]) return fail(h, IWAE_EINVAL, "NULL dream_lat buffer");
+  if ((long long)B * cfg->k + n > (1LL << 30)) return fail(h, IWAE_EINVAL, "B * k + n_dream exceeds 2^30 rows");
+  if (h->dp_world > 1)
+    return fail(h, IWAE_EINVAL, "wake-sleep steps are not built for data parallelism (world > 1)");
+  iwae_loss_config lc{IWAE_LOSS_IWAE, cfg->k, 1.f, 1.f, 0.5f, 0, 0};
+  Plan P;
+  CHK(make_plan(h, &lc, B, P));
+  EpsSet E;
+  CHK(parse_eps(h, P, eps, n_eps, E));
+  const int M = B * P.kS;
+  const bool wake = cw > 0.f, sleep = cs > 0.f, own = sleep && !dream_x;
+  const bool fusedp = ws_use_fused(h, (long long)M + n);
+  // every workspace at its size before anything is enqueued
+  CHK(ensure_capacity(h, B + n, M + n, true));
+  const int ldp = r4(h->xdim);
+  if (own) {
+    size_t need = (size_t)n * ldp;
+    for (int i = 0; i < L; ++i) need += ((size_t)n * h->enc[i].d + 3) & ~size_t(3);
+    if (need > h->ws_ws_floats) {
+      HIPCHK(hipStreamSynchronize(h->stream));
+      if (h->ws_ws) (void)hipFree(h->ws_ws);
+      h->ws_ws = nullptr; h->ws_ws_floats = 0;
+      HIPCHK(hipMalloc(&h->ws_ws, need * sizeof(float)));
+      h->ws_ws_floats = need;
+    }
+  }
+  const bool direct = fusedp && smallm_ok(h, P.Bimg);
+  if (!direct) CHK(copy_x(h, P, x));
+  StepScope scope{h};
+  h->step.x_user = direct ? x : nullptr;
+  h->step.in_train_step = true;
+  h->step.out_x3 = h->x3 && h->tune.out_x3_rows > 0 && (long long)M >= h->tune.out_x3_rows;
+  if (h->step.out_x3) CHK(run_wsplit_seg(h, h->o3));
+  float* vals = values_dev ? values_dev : &h->ds->scalars[4];
+  h->count.ws++;
+  // wake forward, the IWAE loss and its row weights, the decoder's gradient
+  if (fusedp) CHK(fused_forward(h, P, E, true));
+  else CHK(layerwise_forward(h, P, E, true));
+  CHK(run_bound(h, P, true, -1.f, vals, adam));
+  if (fusedp) {
+    CHK(fused_decoder_bwd(h, P, h->dlw, h->dpx, false));
+    CHK(weight_grads(h, P, WG_DECODER));
+  } else {
+    CHK(decoder_bwd(h, P, h->dlw, h->dpx, true, false));
+  }
+  if (sleep) {
+    const float* dx = dream_x;
+    int ld_dx = h->xdim;
+    const float* dl[IWAE_MAX_LAYERS] = {};
+    for (int i = 0; dream_lat && i < L; ++i) dl[i] = dream_lat[i];
+    if (own) {
+      // one iwae_generate call as a caller would make it (outside the train
+      // step's precision rules), its layer-wise launches on the rows behind the
+      // wake rows: the wake latents are the encoder fit's data
+      float* hl[IWAE_MAX_LAYERS] = {};
+      float* p = h->ws_ws + (size_t)n * ldp;
+      for (int i = 0; i < L; ++i) {
+        hl[i] = p;
+        p += ((size_t)n * h->enc[i].d + 3) & ~size_t(3);
+      }
+      h->step = StepState();
+      {
+        RowShift sh;
+        for (Mat& m : h->h) sh.mat(m, M);
+        for (LayerBufs& b : h->db) { sh.mat(b.y1, M); sh.mat(b.y2, M); sh.mat(b.P, M); }
+        sh.mat(h->ob.y1, M); sh.mat(h->ob.y2, M);
+        sh.vec(h->logp, M);
+        CHK(iwae_generate(h, n, nullptr, nullptr, 0, nullptr, nullptr, 0, h->ws_ws, ldp, hl, L));
+      }
+      h->count.ws_dream++;
+      h->step.in_train_step = true;
+      dx = h->ws_ws; ld_dx = ldp;
+      for (int i = 0; i < L; ++i) dl[i] = hl[i];
+    }
+    WsStageArgs sa{};
+    sa.n = n; sa.nbuf = L + 1;
+    sa.src[0] = dx; sa.ld_src[0] = ld_dx; sa.width[0] = h->xdim;
+    sa.dst[0] = h->x_in.p + (size_t)B * h->x_in.ld; sa.ld_dst[0] = h->x_in.ld;
+    for (int i = 0; i < L; ++i) {
+      sa.src[i + 1] = dl[i]; sa.ld_src[i + 1] = sa.width[i + 1] = h->enc[i].d;
+      sa.dst[i + 1] = h->h[i].p + (size_t)M * h->h[i].ld; sa.ld_dst[i + 1] = h->h[i].ld;
+    }
+    HIPCHK(launch_ws_stage(h->stream, sa));
+    CHK(ws_sleep_forward(h, P, n, fusedp));
+  }
+  // row weights (dlw2's rows: no second weighting in this plan), the two encoder values, the fit
+  HIPCHK(launch_ws_weights(h->stream, h->dlw, h->dlw2, M, n, cw, sleep ? cs / (float)n : 0.f));
+  HIPCHK(launch_ws_values(h->stream, h->dlw, h->logq, M, n, wake ? 1 : 0, vals + 1));
+  CHK(ws_encoder_fit(h, P, n, wake, h->dlw2, fusedp));
+  return finish_step(h, P, adam);
+}
+
+int iwae_wake_sleep_step(iwae_handle* h, const iwae_ws_config* cfg, const float* x, int B, const float* const* eps,
+                         int n_eps, const float* dream_x, const float* const* dream_lat, int n_dream_lat,
+                         float* values_dev) {
+  return do_wake_sleep(h, cfg, x, B, eps, n_eps, dream_x, dream_lat, n_dream_lat, values_dev, true);
+}
+
+int iwae_wake_sleep_grad(iwae_handle* h, const iwae_ws_config* cfg, const float* x, int B, const float* const* eps,
+                         int n_eps, const float* dream_x, const float* const* dream_lat, int n_dream_lat,
+                         float* values_dev) {
+  return do_wake_sleep(h, cfg, x, B, eps, n_eps, dream_x, dream_lat, n_dream_lat, values_dev, false);
+}
+
 int iwae_debug_gemm(iwae_handle* h, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
                     int M, int N, int K) {
   if (!h) return IWAE_EINVAL;
@@ -5817,6 +6119,10 @@ long long iwae_debug_count(const iwae_handle* h, int what) {
     case 32: return h->count.score_pix_lw;
     case 33: return h->count.sgrad_pix;
     case 34: return h->count.sgrad_pix_lw;
+    case 35: return h->count.ws;
+    case 36: return h->count.ws_rb;
+    case 37: return h->count.ws_gauss;
+    case 38: return h->count.ws_dream;
     default: return -1;
   }
 }

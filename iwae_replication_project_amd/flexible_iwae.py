@@ -551,6 +551,112 @@ class Flexible_Model:
         if n and not (self._dp is not None and self._dp.comm != "library"):
             self._call(self._lib.iwae_train_steps_prepare(self._h, self._lc(), _lib.fptr(xd), B, n))
 
+    # ----------------------------------------------------- reweighted wake-sleep
+    def _dreams(self, dreams):
+        """(x_dream, [h_1 .. h_L]) as contiguous device tensors [n, x_dim] and
+        [n, d_i]; (x tensor, latent tensors, n)."""
+        try:
+            xs, hs = dreams
+            hs = list(hs)
+        except (TypeError, ValueError):
+            raise ValueError("dreams must be (x_dream, [h_1 .. h_L])") from None
+        dims = self.n_latent_encoder
+        if len(hs) != len(dims):
+            raise ValueError(f"expected {len(dims)} dream latent arrays (one per stochastic layer), got {len(hs)}")
+        xt = self._x(xs)
+        n = int(xt.shape[0])
+        ts = []
+        with torch.cuda.stream(self._stream):
+            for i, v in enumerate(hs):
+                t = torch.as_tensor(v).to(device=self.device, dtype=torch.float32, non_blocking=True).contiguous()
+                if tuple(t.shape) != (n, dims[i]):
+                    raise ValueError(f"dream h[{i}] must be [n={n}, d={dims[i]}], got {tuple(t.shape)}")
+                ts.append(t)
+        return xt, ts, n
+
+    def _wake_sleep(self, xd, c_wake, c_sleep, n_dream, dreams, k, eps, update, values):
+        """One iwae_wake_sleep_step / _grad on the device batch xd; the three
+        values into the device tensor ``values`` (3 floats)."""
+        if self._dp is not None:
+            raise ValueError("wake_sleep_step is not supported under data parallelism")
+        if self.optimizer is None:
+            self.compile()
+        B = int(xd.shape[0])
+        k = self.k if k is None else int(k)
+        c_wake, c_sleep = float(c_wake), float(c_sleep)
+        dx, dh, harr, nh = None, [], None, 0
+        if dreams is not None:
+            dx, dh, n = self._dreams(dreams)
+            if n_dream is not None and int(n_dream) != n:
+                raise ValueError(f"n_dream = {n_dream} but the dreams hold {n} rows")
+            harr, nh = _lib.fptr_array(dh)
+            if c_sleep == 0.0:
+                n = 0                        # the dreams are never read
+        elif n_dream is None:
+            n = B if c_sleep > 0.0 else 0
+        else:
+            n = int(n_dream)
+        arr, ne, keep = self._eps(eps, B, k)
+        cfg = _lib.IwaeWsConfig(k, n, c_wake, c_sleep)
+        fn = self._lib.iwae_wake_sleep_step if update else self._lib.iwae_wake_sleep_grad
+        self._call(fn(self._h, cfg, _lib.fptr(xd), B, arr, ne, _lib.fptr(dx), harr, nh, _lib.fptr(values)))
+        if update:
+            self.epoch += 1
+        return keep, dx, dh                  # alive until the caller has synchronised or moved on in stream order
+
+    def wake_sleep_step(self, x, c_wake=1.0, c_sleep=0.0, n_dream=None, dreams=None, k=None, eps=None, sync=True,
+                        update=True):
+        """One reweighted wake-sleep step (iwae_wake_sleep_step; Bornschein &
+        Bengio 2015, Le et al. 2019): the decoder takes the IWAE gradient of a
+        k-sample wake forward on ``x``; the encoder descends
+        c_wake L_wake + c_sleep L_sleep, with L_wake = -mean_b sum_s
+        softmax_s(log w) log q(h_bs | x_b) at the wake samples and weights held
+        fixed and L_sleep = -mean_j log q(h^j | x^j) over dream pairs.  (1, 0) is
+        wake-wake, (0, 1) wake-sleep, (0.5, 0.5) the mix.  ``dreams`` =
+        (x_dream [n, x_dim], [h_1 .. h_L] each [n, d_i]), numpy arrays or device
+        tensors (any (x, h) pairs: the states ``ais`` or ``hmc`` leave, say);
+        without them the step dreams ``n_dream`` pairs (default: the batch size
+        when c_sleep > 0) from the current weights, as ``sample`` would.  ``k``
+        defaults to the model's; ``eps`` as for ``train_step``.
+        ``update=False`` leaves the gradient in the buffer (``get_gradients``)
+        and Adam untouched.  Returns {"IWAE": L_theta, "wake": L_wake, "sleep":
+        L_sleep} (a phase whose coefficient is 0 reports 0); device scalars
+        with ``sync=False``."""
+        xd = self._x(x)
+        with torch.cuda.stream(self._stream):
+            values = torch.empty(3, device=self.device)
+        keep = self._wake_sleep(xd, c_wake, c_sleep, n_dream, dreams, k, eps, update, values)
+        if not sync:
+            self._ws_keep = (xd, keep)
+            return {"IWAE": values[0], "wake": values[1], "sleep": values[2]}
+        self._stream.synchronize()
+        v = values.cpu().numpy()
+        self._call(self._lib.iwae_status(self._h))
+        return {"IWAE": float(v[0]), "wake": float(v[1]), "sleep": float(v[2])}
+
+    def wake_sleep_steps(self, x, batch_size, c_wake=1.0, c_sleep=0.0, n_dream=None, k=None, sync=True):
+        """len(x) // batch_size consecutive wake-sleep steps on the batches
+        x[i*batch_size:(i+1)*batch_size] with device noise and the steps' own
+        dreams, enqueued without synchronising between them.  Returns the
+        values [nsteps, 3] (IWAE, wake, sleep per step; a device tensor with
+        sync=False)."""
+        xd = self._x(x)
+        B = int(batch_size)
+        if B <= 0:
+            raise ValueError("batch_size must be positive")
+        n = xd.shape[0] // B
+        with torch.cuda.stream(self._stream):
+            values = torch.zeros(n, 3, device=self.device)
+        for i in range(n):
+            self._wake_sleep(xd[i * B:(i + 1) * B], c_wake, c_sleep, n_dream, None, k, None, True, values[i])
+        if not sync:
+            self._ws_keep = (xd,)
+            return values
+        self._stream.synchronize()
+        out = values.cpu().numpy()
+        self._call(self._lib.iwae_status(self._h))
+        return out
+
     def graph_captures(self):
         """Train-step graphs captured so far (iwae_debug_count id 7)."""
         return int(self._lib.iwae_debug_count(self._h, 7))
