@@ -134,6 +134,15 @@ AIS_CASES = {
 }
 
 
+# a second registry of (step, momentum seed), filled by tests/latent_shape_cases.py under the same search;
+# AIS_CASES and the tests parametrized over it stay as they are
+EXTRA_AIS_CASES = {}
+
+
+def ais_entry(name, init):
+    return AIS_CASES[name, init] if (name, init) in AIS_CASES else EXTRA_AIS_CASES[name, init]
+
+
 def momenta_of(name, seed, T):
     h = R.latents(name, "on")
     rng = np.random.default_rng(seed)
@@ -176,7 +185,7 @@ def search(name, init):
 @functools.lru_cache(maxsize=None)
 def ais_case(name, init):
     """The float64 run of a case (run()'s dict plus "momenta"): computed once, shared, read-only."""
-    step, seed = AIS_CASES[name, init]
+    step, seed = ais_entry(name, init)
     out = _run_case(name, init, step, seed)
     for v in out.values():
         for a in (v if isinstance(v, list) else [v]):
@@ -188,7 +197,7 @@ def ais_case(name, init):
 @functools.lru_cache(maxsize=None)
 def emulated_case(name, init):
     """The same momenta and log u through the float32 + bf16x3 emulation of the densities and gradients."""
-    step, seed = AIS_CASES[name, init]
+    step, seed = ais_entry(name, init)
     return _run_case(name, init, step, seed, log_u=ais_case(name, init)["log_u"], dtype=np.float32, dense=R.dense_bf16x3)
 
 
@@ -204,7 +213,7 @@ NOISE_CASES = {("S2", "q"): (0.2, 6025), ("S3", "prior"): (0.15, 6035)}
 
 def device_noise(name, seed, T, base0=0):
     """(momenta[t - 1][i] [k, B, d_i], u [T, k, B] float32) as iwae_ais draws them: row = b k + s, base0 + t - 1."""
-    _, B, k = R.CASES[name][:3]
+    _, B, k = R.entry(name)[:3]
     dims = R.case(name)[0].n_latent_encoder
     rows = NR.sample_rows(B, k)
     key = NR.key(seed)

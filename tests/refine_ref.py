@@ -50,11 +50,11 @@ def case(name):
         spec, params, _, x, _ = PR.make_case(arch, B, k, seed, x_dim=x_dim)
         return spec, params, x, B, k
     spec, params, x, _ = R.case(name)
-    return spec, params, x, R.CASES[name][1], R.CASES[name][2]
+    return spec, params, x, R.entry(name)[1], R.entry(name)[2]
 
 
 def arch(name):
-    return OWN[name][0] if name in OWN else R.CASES[name][0]
+    return OWN[name][0] if name in OWN else R.entry(name)[0]
 
 
 @functools.lru_cache(maxsize=None)

@@ -44,8 +44,8 @@ def _u(ref):
 
 def _run(m, name, init, ref, betas=A.BETAS, **kw):
     _, _, x, _ = R.case(name)
-    _, B, k = R.CASES[name][:3]
-    step, _ = A.AIS_CASES[name, init]
+    _, B, k = R.entry(name)[:3]
+    step, _ = A.ais_entry(name, init)
     n = len(betas) - 1
     kw.setdefault("momentum", [_f32(r) for r in ref["momenta"][:n]])
     kw.setdefault("u", _u(ref)[:n])
@@ -81,7 +81,7 @@ def test_parity(name, init, path):
     ref = A.ais_case(name, init)
     m = _model(name, path)
     out = _run(m, name, init, ref)
-    _, B, k = R.CASES[name][:3]
+    _, B, k = R.entry(name)[:3]
     assert tuple(out["log_w"].shape) == (k, B) and tuple(out["logpx"].shape) == (B,) and tuple(out["ess"].shape) == (B,)
     _compare(out, ref, R.latents(name, A.START[init]), T, f"[{name} {init} {path}]")
     assert (ref["accepts"] == 0).any() or (ref["accepts"] < T).any()

@@ -46,7 +46,7 @@ ALL = ("log_q", "log_ph", "log_px", "probs")
 def _model(name, path, precision="bf16x3", seed=0):
     from oracle import iwae_oracle as O
     spec, params, _, _ = R.case(name)
-    he, hd, le, ld = R.CASES[name][0]
+    he, hd, le, ld = R.entry(name)[0]
     m = make_model(he, hd, le, ld, x_dim=spec.x_dim, kernel_path=path, precision=precision, seed=seed)
     m.set_weights(weights_from_flat(m, O.flatten_params(spec, params)))
     return m

@@ -326,7 +326,7 @@ def test_invalid_arguments_return_einval_and_launch_nothing(path):
 @pytest.mark.parametrize("name", list(G.HMC_CASES))
 def test_hmc_follows_the_float64_leapfrog_and_decides_as_it_does(name, path):
     _, _, x, _ = R.case(name)
-    step, nl, _ = G.HMC_CASES[name]
+    step, nl, _ = G.hmc_entry(name)
     r, q, H0, H1, lu, acc = G.hmc_case(name)
     h = _f32(R.latents(name, "on"))
     m = _model(name, path)
