@@ -33,6 +33,9 @@ SHAPES = {
     # (74.5 row tiles), and >= 8192, where a train step runs the output layer on bf16x3 products
     "M784k": ([200], [200], [50], 784, 20, 477, 1977),
 }
+# a second registry of the same tuples, filled by the modules that bring cases of their own
+# (tests/step_shape_cases.py): shape_case() finds them, SHAPES and every test parametrized over it stay as they are
+EXTRA_SHAPES = {}
 
 
 def make_mask(B, x_dim, seed, p_obs=0.5):
@@ -54,7 +57,7 @@ def with_holes(x, mask, fill=np.nan):
 
 def shape_case(name):
     """(arch, B, k, x_dim, (spec, params, mean, x, eps, eps2, mask)); x holds NaN where missing."""
-    he, hd, le, x_dim, B, k, seed = SHAPES[name]
+    he, hd, le, x_dim, B, k, seed = SHAPES[name] if name in SHAPES else EXTRA_SHAPES[name]
     arch = (he, hd, le, le[-2::-1] + [x_dim])
     spec, params, mean, x, eps = R.make_case(arch, B, k, seed, x_dim=x_dim)
     rng = np.random.default_rng(seed + 1)

@@ -18,7 +18,8 @@ Every mask: NaN at the missing entries of x, image 0 entirely missing, image 1
 entirely observed, Bernoulli(0.5) elsewhere.  Bars: test_gpu_pathgrad.py's (loss
 and whole gradient 1e-4 relative, each tensor 5e-4 of its largest entry, Adam
 as its _step_and_check); tests/test_missing_ref.py shows the reference run in
-float32 stays within a quarter of them on these very inputs."""
+float32 stays within a quarter of them on these very inputs.
+tests/test_gpu_step_shapes.py sweeps the masked step over odd widths, x_dim and depths."""
 import functools
 
 import numpy as np

@@ -12,7 +12,8 @@ at the smallest shapes that reach every branch (wakesleep_ref.CASES):
 Bars: test_gpu_pathgrad.py's (the three values and the whole gradient 1e-4
 relative, each parameter tensor 5e-4 of its largest entry, Adam as
 test_gpu_configs._check).  tests/test_wakesleep_ref.py shows the reference run
-in float32 stays within a quarter of them on these very inputs."""
+in float32 stays within a quarter of them on these very inputs.
+tests/test_gpu_step_shapes.py sweeps the step over odd widths, depths and row counts."""
 import functools
 
 import numpy as np

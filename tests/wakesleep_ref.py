@@ -27,6 +27,9 @@ CASES = {
     "W3": ([40, 24, 16], [16, 24, 40], [12, 10, 6], [10, 12, 64], 4, 6, 5, 1944),   # a middle layer
     "W4": ([48, 32], [32, 48], [70, 5], [70, 64], 2, 9, 3, 1955),                # d = 70 > 64
 }
+# a second registry, filled by the modules that bring cases of their own (tests/step_shape_cases.py), of the same
+# tuples with x_dim appended: case() finds them, CASES and every test parametrized over it stay as they are
+EXTRA_CASES = {}
 
 
 def enc_names(spec):
@@ -131,6 +134,9 @@ def make_case(arch, B, k, n, seed, x_dim=X_DIM):
 
 
 def case(name):
+    if name in EXTRA_CASES:
+        he, hd, le, ld, B, k, n, seed, x_dim = EXTRA_CASES[name]
+        return (he, hd, le, ld), B, k, n, make_case((he, hd, le, ld), B, k, n, seed, x_dim=x_dim)
     he, hd, le, ld, B, k, n, seed = CASES[name]
     return (he, hd, le, ld), B, k, n, make_case((he, hd, le, ld), B, k, n, seed)
 
