@@ -173,10 +173,14 @@ enum iwae_knob {
   IWAE_KNOB_TCU_WAIT_TEST = 41,   /* fault injection for tests (0): every in-launch wait of the TCU launch waits
                                       for one producer more than exists, with a short spin bound, so it gives up and
                                       the failure must surface through iwae_status (results of that step invalid) */
-  IWAE_KNOB_TCU_WT = 42           /* the TCU launch's hand-off write-through where every waiting tile is one
+  IWAE_KNOB_TCU_WT = 42,          /* the TCU launch's hand-off write-through where every waiting tile is one
                                       reduction iteration (1): job I' stores its outputs sc1 and adds to the counter
                                       without a release fence, the waiting tiles poll and load dZ sc1 without an
                                       acquire; 0: release / acquire fences */
+  IWAE_KNOB_NLL_GROUP = 43        /* fused evaluation entries (iwae_nll, iwae_posterior / iwae_impute, iwae_score,
+                                      iwae_score_grad): images per pass of the first encoder layer, whole chunks of
+                                      them, in [1, 2^20] (16384: three GEMM launches and the copy of x per ~16 K
+                                      images instead of per chunk, ~2 % of a k = 5000 NLL) */
   /* 10, 36-40: removed variants measured slower (64 x 32 update tiles, a short
      first graph, the chained / paired first-encoder-layer launches, dw_kernel
      cost-model terms); iwae_set_tuning rejects them with IWAE_EINVAL */

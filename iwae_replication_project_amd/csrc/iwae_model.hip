@@ -6,6 +6,7 @@
 //   train_step        F:221-F:247 -> get_log_weights F:327-F:351 -> bound -> tape.gradient -> Adam
 //   get_NLL           F:463-F:464 -> get_L_k with k = 5000
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -130,6 +131,7 @@ struct Tune {
   int mg_waves = 8;                  // mega_fwd_kernel workgroup: 8 waves (64 rows) or 4 (32 rows, 2 per CU)
   long long nll_rows = 1LL << 20;    // sample rows per NLL chunk (measured fastest: 2^17-2^20 within 10 %)
   int nll_imgs = 0;                  // images per NLL chunk when the caller passes chunk 0 (0: nll_rows / k)
+  int nll_group = 16384;             // fused evaluation paths: images per pass of the first encoder layer (ChunkWalk)
   int nring = 1;                     // NLL: the weight-ring kernel (nring_kernel) where its shapes apply
   int nring_train = 1;               // train-step forward on it (train mode) ...
   long long nr_train_rows = 4096;    // ... from this many sample rows
@@ -253,6 +255,27 @@ struct GraphRec {
 
 }  // namespace
 
+// A grow-only device workspace of one evaluation entry (floats).  reserve
+// (below) leaves it holding at least `floats`: a larger one is allocated after
+// the stream has drained (queued kernels may still read the old one), and
+// zeroed where asked (force: whatever it holds now).  What it held is gone
+// when it grows.
+struct GrowWs {
+  float* p = nullptr;
+  size_t floats = 0;
+  int reserve(iwae_handle* h, size_t need, bool zero = false, bool force = false);
+};
+
+// Offsets into such a workspace, each on a 64-float boundary.
+struct WsLayout {
+  size_t floats = 0;
+  size_t take(size_t n) {
+    const size_t o = floats;
+    floats += (n + 63) & ~size_t(63);
+    return o;
+  }
+};
+
 struct iwae_handle {
   int device = 0;
   hipStream_t own_stream = nullptr;
@@ -306,18 +329,18 @@ struct iwae_handle {
   unsigned* tcu_ctr = nullptr;       // tcu_kernel's in-launch counters (UpdWait::ctr; zero between launches)
   unsigned* err_host = nullptr;      // host-mapped error word a kernel sets when an in-launch wait gives up
   unsigned* err_dev = nullptr;       // ... its device address (UpdWait::err)
-  char* post_ws = nullptr;           // iwae_posterior's workspace (weights, SIR indices, partial sums, probabilities,
-  size_t post_ws_bytes = 0;          // a chunk's injected noise): its own allocation, so the arena and what was
-                                     // captured over it stay as they are
-  float* sg_ws = nullptr;            // iwae_score_grad's backward rows (layer-wise path): its own allocation, zeroed
-  size_t sg_ws_floats = 0;           // when it grows, laid out for sg_rows rows (padding columns stay zero)
-  int sg_rows = 0;
-  float* ais_ws = nullptr;           // iwae_ais's chains (momenta, proposals, gradients per layer; H_old, the value
-  size_t ais_ws_floats = 0;          // terms, and the weights / steps the caller did not give): its own allocation
-  float* refine_ws = nullptr;        // iwae_refine's samples (latents, noise, gradients per layer; the value terms,
-  size_t refine_ws_floats = 0;       // the weights, and the Adam moments the caller did not give): its own allocation
-  float* ws_ws = nullptr;            // iwae_wake_sleep_step's own dreams (pixels [n][r4(x_dim)], then h_1 .. h_L
-  size_t ws_ws_floats = 0;           // [n][d_i]) and its three values when the caller wants none: its own allocation
+  // the evaluation entries' workspaces: each its own allocation, so the arena and what was captured over it
+  // stay as they are
+  GrowWs post_ws;                    // iwae_posterior's (weights, SIR indices, partial sums, probabilities, a chunk's
+                                     // injected noise) and iwae_encode's (a chunk's injected noise)
+  GrowWs sg_ws;                      // iwae_score_grad's backward rows (layer-wise path): zeroed when it grows, laid
+  int sg_rows = 0;                   // out for sg_rows rows (padding columns stay zero)
+  GrowWs ais_ws;                     // iwae_ais's chains (momenta, proposals, gradients per layer; H_old, the value
+                                     // terms, and the weights / steps the caller did not give)
+  GrowWs refine_ws;                  // iwae_refine's samples (latents, noise, gradients per layer; the value terms,
+                                     // the weights, and the Adam moments the caller did not give)
+  GrowWs ws_ws;                      // iwae_wake_sleep_step's own dreams (pixels [n][r4(x_dim)], then h_1 .. h_L
+                                     // [n][d_i]) and its three values when the caller wants none
   float* loss_slots = nullptr;       // multi-step graphs: step j's loss (kGraphSteps floats), then
                                      // [kGraphSteps, 2 kGraphSteps): where a graph's copy node writes
                                      // when the call wants no losses
@@ -387,6 +410,18 @@ struct StepScope {
 static int fail(iwae_handle* h, int code, const std::string& msg) {
   h->err = msg;
   return code;
+}
+
+int GrowWs::reserve(iwae_handle* h, size_t need, bool zero, bool force) {
+  if (need <= floats && !force) return IWAE_OK;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (p) (void)hipFree(p);
+  p = nullptr;
+  floats = 0;
+  HIPCHK(hipMalloc(&p, need * sizeof(float)));
+  if (zero) HIPCHK(hipMemsetAsync(p, 0, need * sizeof(float), h->stream));
+  floats = need;
+  return IWAE_OK;
 }
 
 // ------------------------------------------------------------------ plan
@@ -3201,6 +3236,237 @@ static bool ring_plan_tail(iwae_handle* h, NrUnit*& dev, int cap, const std::vec
   return true;
 }
 
+// ------------------------------------------------ evaluation entries: shared host code
+// What iwae_nll, iwae_posterior / iwae_impute, iwae_score, iwae_score_grad and
+// iwae_encode share: the argument checks, the chunk rule, the walk over chunks
+// and first-layer groups, the per-chunk launch fields and the layer-wise blocks.
+
+// a[0 .. L-1], one buffer per stochastic layer, none null (optional: or n == 0)
+static int ptrs_ok(iwae_handle* h, const float* const* a, int n, const char* what, bool optional) {
+  if (optional && n == 0) return IWAE_OK;
+  if (n != h->L || !a)
+    return fail(h, IWAE_EINVAL, std::string("expected ") + std::to_string(h->L) + " " + what + " buffers (one per "
+                                "stochastic layer), got " + std::to_string(n));
+  for (int i = 0; i < h->L; ++i)
+    if (!a[i]) return fail(h, IWAE_EINVAL, std::string("NULL ") + what + " buffer");
+  return IWAE_OK;
+}
+
+// rows of x_dim floats the kernels store as float4 (ld <= 2^22: a workgroup's
+// 64 rows stay within 32-bit buffer offsets); p null: nothing to check
+static int ld_ok(iwae_handle* h, const float* p, int ld, const char* what) {
+  if (p && (ld < h->xdim || ld > (1 << 22) || (ld & 3) || ((uintptr_t)p & 15)))
+    return fail(h, IWAE_EINVAL, std::string(what) + " needs x_dim <= ld <= 2^22, a multiple of 4, 16-byte aligned");
+  return IWAE_OK;
+}
+
+// N images of k samples each; whole_k: all k of an image go through one chunk, which bounds k
+static int nk_ok(iwae_handle* h, int N, int k, bool whole_k = true) {
+  if (N <= 0 || k <= 0) return fail(h, IWAE_EINVAL, "N and k must be positive");
+  if (whole_k && k > (1 << 20)) return fail(h, IWAE_EINVAL, "k above 2^20 per image is not supported");
+  return IWAE_OK;
+}
+
+// At most 256 MB of what a chunk keeps per sample row (row_bytes each), at least one image
+static int cap_chunk_bytes(int imgs, int k, long long row_bytes) {
+  return (int)std::min<long long>(imgs, std::max<long long>(1, (256LL << 20) / (k * row_bytes)));
+}
+
+// Images per chunk: the caller's chunk, else IWAE_KNOB_NLL_IMGS, else
+// floor(nll_rows / k), at least 1 and at most N; with row_bytes (what a chunk
+// keeps per sample row) at most 256 MB of those.  whole_k: a chunk holds all k
+// samples of its images, which bounds k and the chunk's rows (iwae_nll splits
+// the samples instead).  0 with the error set.
+static int chunk_images(iwae_handle* h, int N, int k, int chunk, bool whole_k = true, long long row_bytes = 0) {
+  if (nk_ok(h, N, k, whole_k) != IWAE_OK) return 0;
+  if (chunk <= 0) chunk = h->tune.nll_imgs;
+  // (k above nll_rows: one image; rows past what an int holds ask for no more images than N can give)
+  const long long target_rows = std::max<long long>(std::min<long long>(h->tune.nll_rows, INT_MAX), k);
+  int imgs = chunk > 0 ? chunk : (int)std::max<long long>(1, target_rows / k);
+  if (row_bytes > 0) imgs = cap_chunk_bytes(imgs, k, row_bytes);
+  imgs = std::min(imgs, N);
+  if (whole_k && (long long)imgs * k > (1LL << 30)) { fail(h, IWAE_EINVAL, "chunk * k above 2^30 sample rows"); return 0; }
+  return imgs;
+}
+
+// ng images from row i0 on into x_in: a copy, or with a pixel mask the two
+// staged copies by select (x_in = mask ? x : 0, lik = mask ? x : -1;
+// impute_stage_kernel; lik.p null: the first alone).
+static int stage_x(iwae_handle* h, const float* x, const float* mask, int i0, int ng, const Mat& lik = Mat()) {
+  x += (size_t)i0 * h->xdim;
+  if (mask) {
+    HIPCHK(launch_impute_stage(h->stream, x, mask + (size_t)i0 * h->xdim, ng, h->xdim, h->x_in.p, h->x_in.ld, lik.p,
+                               lik.ld));
+    return IWAE_OK;
+  }
+  const size_t wbytes = (size_t)h->xdim * sizeof(float);
+  HIPCHK(hipMemcpy2DAsync(h->x_in.p, (size_t)h->x_in.ld * sizeof(float), x, wbytes, wbytes, ng, hipMemcpyDeviceToDevice,
+                          h->stream));
+  return IWAE_OK;
+}
+
+// The walk of an evaluation call over its N images: chunks of imgs images
+// (one set of launches each) inside groups of sup images, staged into x_in
+// together.  Fused, a group is up to IWAE_KNOB_NLL_GROUP images and (enc0) the
+// first encoder layer runs once per group -- three GEMM launches and the copy
+// of x per ~16 K images instead of per chunk (k = 5000: 78 chunks of 209 images;
+// the per-chunk launches were ~2 % of the NLL's time) -- and the fused kernels
+// read each chunk's rows of eb[0].P and x_in.  Layer-wise a group is a chunk.
+//   for (ChunkWalk W(h, ...); W.i0 < N; W.i0 += W.imgs) { CHK(walk_step(h, W)); ... }
+struct ChunkWalk {
+  int N, k, imgs, sup;
+  bool fused, enc0;
+  const float *x, *mask;             // (x null: a call that needs no images; nothing is staged)
+  const Mat* lik;                    // masked: where the likelihood's -1 copy is staged (read at each group)
+  // the chunk, set by walk_step: images [i0, i0 + n), rows io .. of x_in / eb[0], rows r0 .. of [N][k] outputs
+  int i0 = 0, n = 0, io = 0, u0 = 0;
+  size_t r0 = 0;
+  ChunkWalk(const iwae_handle* h, int N_, int k_, int imgs_, bool fused_, const float* x_, const float* mask_, bool enc0_,
+            const Mat* lik_ = nullptr)
+      : N(N_), k(k_), imgs(imgs_), sup(fused_ ? std::min(N_, imgs_ * std::max(1, h->tune.nll_group / imgs_)) : imgs_),
+        fused(fused_), enc0(enc0_), x(x_), mask(mask_), lik(lik_ ? lik_ : &h->x_lik) {}
+};
+
+static int walk_step(iwae_handle* h, ChunkWalk& W) {
+  W.n = std::min(W.imgs, W.N - W.i0);
+  W.r0 = (size_t)W.i0 * W.k;
+  if (W.x && (W.i0 == 0 || W.i0 - W.u0 >= W.sup)) {          // a new group (layer-wise: every chunk)
+    W.u0 = W.i0;
+    const int ng = std::min(W.sup, W.N - W.i0);
+    CHK(stage_x(h, W.x, W.mask, W.i0, ng, *W.lik));
+    if (W.enc0) CHK(stoch_fwd(h, h->enc[0], h->x_in, ng, h->eb[0]));
+  }
+  W.io = W.x ? W.i0 - W.u0 : 0;
+  return IWAE_OK;
+}
+
+// The launch fields of the chunk's rows that MgLaunch, ScLaunch and SgLaunch
+// share: kS samples of each image, the first encoder layer's output rows and
+// the likelihood's copy xl of the images.
+template <class Launch>
+static void chunk_rows(const iwae_handle* h, const ChunkWalk& W, int kS, const Mat& xl, Launch& A) {
+  A.rows = W.n * kS; A.kS = kS;
+  A.P0 = h->eb[0].P.p + (size_t)W.io * h->eb[0].P.ld; A.ldP0 = h->eb[0].P.ld;
+  A.x = xl.p + (size_t)W.io * xl.ld; A.ldx = xl.ld;
+}
+
+// mega_fwd_kernel's plan and, where its shapes apply, nring_kernel's: the
+// fused k-sample forward of iwae_nll and of iwae_posterior's first pass.
+struct FwdPlan {
+  MgLaunch MG;
+  NrLaunch NR;
+  int rt = 0, waves = 8;
+  size_t lds = 0;
+  bool ring = false;
+};
+
+// The noise (the caller's eps [k][N][d_i], or null: Philox) and log-weight
+// fields of a call's launches, after ensure_capacity.
+static void fwd_call_fields(const iwae_handle* h, FwdPlan& F, const float* const* eps, int N) {
+  for (int i = 0; i < 8; ++i) F.MG.eps[i] = F.NR.eps[i] = (eps && i < h->L) ? eps[i] : nullptr;
+  F.MG.eps_N = F.NR.eps_N = N;
+  F.MG.seed = h->seed; F.MG.rng_base = &h->ds->rng[0];
+  F.MG.lw = h->lw;
+}
+
+// Samples [s0, s0 + P.kS) of the chunk's images: the weight-ring kernel where it
+// is planned and P.kS >= 128 (same rows, same noise; 128 rows per workgroup span
+// at most two images), else mega_fwd_kernel.
+static int launch_fwd_chunk(iwae_handle* h, FwdPlan& F, const ChunkWalk& W, const Plan& P, int s0, bool injected) {
+  MgLaunch& MG = F.MG;
+  chunk_rows(h, W, P.kS, h->x_in, MG);
+  MG.eps_i0 = W.i0; MG.eps_s0 = s0;
+  if (F.ring && P.kS >= 128) {
+    NrLaunch& NR = F.NR;
+    NR.rows = MG.rows; NR.kS = MG.kS; NR.eps_i0 = W.i0; NR.eps_s0 = s0;
+    NR.P0 = MG.P0; NR.ldP0 = MG.ldP0; NR.x = MG.x; NR.ldx = MG.ldx;
+    NR.seed = MG.seed; NR.rng_base = MG.rng_base; NR.lw = MG.lw;
+    HIPCHK(launch_nring(h->stream, NR));
+    ++h->count.nring;
+  } else {
+    HIPCHK(launch_mega_fwd(h->stream, MG, F.rt, F.waves, F.lds));
+  }
+  ++h->count.mega;
+  if (injected) ++h->count.mega_eps;
+  return IWAE_OK;
+}
+
+// launch_lse's arguments for kS samples of n images (init: the first samples
+// of these images) from the workspace's logp / logq and Bernoulli partials; a
+// fused forward's caller points lw at its log weights instead
+static LseArgs lse_args(const iwae_handle* h, int kS, int n, bool init) {
+  LseArgs a{};
+  a.part = h->part; a.ldpart = h->ldpart; a.npart = h->npart; a.logp = h->logp; a.logq = h->logq;
+  a.kS = kS; a.Bimg = n; a.run_m = h->run_m; a.run_s = h->run_s; a.init = init;
+  a.ticket = &h->ds->tickets[1]; a.rng_base = &h->ds->rng[0];
+  return a;
+}
+
+// Layer-wise injected noise of the chunk: the caller's buffers [k][N][d_i], or
+// (gather: a chunk of a longer call) sample s of the chunk's images, n * d
+// floats at (s * N + i0) * d, copied contiguous to ws + o_eps[i] as [k][n][d_i].
+static int chunk_eps(iwae_handle* h, const ChunkWalk& W, const float* const* eps, bool gather, float* ws,
+                     const size_t* o_eps, EpsSet& E) {
+  std::memset(&E, 0, sizeof(E));
+  for (int i = 0; eps && i < h->L; ++i) {
+    E.a[i] = eps[i];
+    if (!gather) continue;
+    const int d = h->enc[i].d;
+    const size_t rb = (size_t)W.n * d * sizeof(float);
+    HIPCHK(hipMemcpy2DAsync(ws + o_eps[i], rb, eps[i] + (size_t)W.i0 * d, (size_t)W.N * d * sizeof(float), rb, W.k,
+                            hipMemcpyDeviceToDevice, h->stream));
+    E.a[i] = ws + o_eps[i];
+  }
+  return IWAE_OK;
+}
+
+// The caller's latents lat[i] [k][N][d_i] of the chunk's images into the rows of h[i]
+static int gather_latents(iwae_handle* h, const ChunkWalk& W, const float* const* lat) {
+  ScRelayout G{};
+  G.n = W.n; G.k = W.k; G.N = W.N; G.i0 = W.i0; G.gather = 1;
+  for (int i = 0; i < h->L; ++i)
+    G.seg[G.nseg++] = ScSeg{h->h[i].p, h->h[i].ld, 0, h->enc[i].d, const_cast<float*>(lat[i]), 0, 0};
+  HIPCHK(launch_score_relayout(h->stream, G));
+  return IWAE_OK;
+}
+
+// One Gaussian log-density pass: rows of H (d wide) under the (mu | zs) rows of
+// P, row r's at P[r / prow_div], into out (accumulate: added to it)
+static int gauss_logdens(iwae_handle* h, const Mat& P, int prow_div, int d, const Mat& H, float* out, bool accumulate,
+                         int M) {
+  GaussArgs g{};
+  g.P = P.p; g.ldP = P.ld; g.prow_div = prow_div; g.d = d;
+  g.H = H.p; g.ldH = H.ld;
+  g.out = out; g.accumulate = accumulate; g.M = M;
+  HIPCHK(launch_gauss_fwd(h->stream, 1, g));
+  return IWAE_OK;
+}
+
+// The output MLP's hidden layers of M rows of h[0] into ob.y1, ob.y2
+static int out_hidden(iwae_handle* h, int M) {
+  CHK(gemm_fwd(h, EPI_TANH, h->h[0], M, h->dense[h->o1], h->ob.y1));
+  return gemm_fwd(h, EPI_TANH, h->ob.y1, M, h->dense[h->o2], h->ob.y2);
+}
+
+// ... and its output Dense: the logits of those rows into p, turned into probabilities in place
+static int out_probs(iwae_handle* h, int M, float* p, int ld) {
+  Mat pm;
+  pm.p = p; pm.ld = ld;
+  CHK(gemm_fwd(h, EPI_STORE, h->ob.y2, M, h->dense[h->o3], pm));
+  HIPCHK(launch_bern_probs(h->stream, p, M, h->xdim, ld));
+  return IWAE_OK;
+}
+
+// The Bernoulli epilogue's arguments for log p(x | h_1) of rows that belong k
+// to an image of xl, weighted wa
+static GemmArgs bern_args(const iwae_handle* h, const Mat& xl, int k, float wa) {
+  GemmArgs ex{};
+  ex.aux = xl.p; ex.ldaux = xl.ld; ex.x_row_div = k;
+  ex.part = h->part; ex.part2 = h->part2; ex.ldpart = h->ldpart;
+  ex.wa = wa; ex.wb = 0.f;
+  return ex;
+}
+
 // ---------------------------------------------------------------- ABI
 extern "C" {
 
@@ -3338,11 +3604,8 @@ void iwae_destroy(iwae_handle* h) {
   if (h->tcu_ctr) (void)hipFree(h->tcu_ctr);
   if (h->err_host) (void)hipHostFree(h->err_host);
   if (h->loss_slots) (void)hipFree(h->loss_slots);
-  if (h->post_ws) (void)hipFree(h->post_ws);
-  if (h->sg_ws) (void)hipFree(h->sg_ws);
-  if (h->ais_ws) (void)hipFree(h->ais_ws);
-  if (h->refine_ws) (void)hipFree(h->refine_ws);
-  if (h->ws_ws) (void)hipFree(h->ws_ws);
+  for (GrowWs* w : {&h->post_ws, &h->sg_ws, &h->ais_ws, &h->refine_ws, &h->ws_ws})
+    if (w->p) (void)hipFree(w->p);
   if (h->nr_units) (void)hipFree(h->nr_units);
   if (h->nrb_units) (void)hipFree(h->nrb_units);
   if (h->nre_units) (void)hipFree(h->nre_units);
@@ -3492,6 +3755,7 @@ int iwae_set_tuning(iwae_handle* h, int knob, long long value) {
       break;
     case IWAE_KNOB_NLL_ROWS: h->tune.nll_rows = std::max(1LL, value); break;
     case IWAE_KNOB_NLL_IMGS: h->tune.nll_imgs = (int)std::max(0LL, std::min(value, 1LL << 20)); break;
+    case IWAE_KNOB_NLL_GROUP: h->tune.nll_group = (int)std::max(1LL, std::min(value, 1LL << 20)); break;
     case IWAE_KNOB_WIDE_ROWS: h->tune.wide_rows = std::max(0LL, value); break;
     case IWAE_KNOB_DW_WIDE: h->tune.dw_wide = on; break;
     case IWAE_KNOB_DW_WG: h->tune.dw_wg = (int)std::max(8LL, std::min(value, 4096LL)); break;
@@ -4171,9 +4435,6 @@ static bool nring_train_backward_enc(iwae_handle* h, const Plan& P, bool& ran) {
   return true;
 }
 
-// images per first-encoder-layer group of the fused NLL path
-constexpr int kNllFirstLayerImages = 16384;
-
 // chunked k-sample NLL over N images; accumulates per-image (m, s)
 // eps (optional, parity): L buffers [k][N][d_i]; only the fused kernel takes
 // them chunk by chunk (the caller checks nll_mega_ok first)
@@ -4188,81 +4449,36 @@ static int nll_core(iwae_handle* h, const float* x, int N, int k, int chunk, flo
                     float* out_logpx, const float* const* eps = nullptr) {
   if (!h) return IWAE_EINVAL;
   if (!x) return fail(h, IWAE_EINVAL, "x is NULL");
-  if (N <= 0 || k <= 0) return fail(h, IWAE_EINVAL, "N and k must be positive");
-  // 2^20 sample rows per chunk (measured fastest: 2^17-2^20 within 10 %, smaller slower)
-  const long long nll_rows = h->tune.nll_rows;
-  const long long target_rows = std::max<long long>(nll_rows, k);
-  if (chunk <= 0) chunk = h->tune.nll_imgs;
-  int imgs = chunk > 0 ? chunk : (int)std::max<long long>(1, target_rows / k);
-  imgs = std::min(imgs, N);
+  const int imgs = chunk_images(h, N, k, chunk, false);
+  if (!imgs) return IWAE_EINVAL;
+  // 2^20 sample rows per chunk (measured fastest: 2^17-2^20 within 10 %, smaller slower): the samples split
+  const long long target_rows = std::max<long long>(h->tune.nll_rows, k);
   const int kS = (int)std::min<long long>(k, std::max<long long>(1, target_rows / imgs));
-  MgLaunch MG;
-  int mg_rt = 0, mg_waves = 8;
-  size_t mg_lds = 0;
-  const bool mega = h->x3 && h->nll_fused && !h->masked && mega_plan(h, MG, mg_rt, mg_waves, mg_lds);
-  // fused path: the first encoder layer (three GEMM launches and the copy of
-  // x) runs once per group of up to ~16 K images instead of once per chunk
-  // (k = 5000: 78 chunks of 209 images; the per-chunk launches were ~2 % of
-  // the NLL's time); the fused kernel reads each chunk's rows of P0 and x_in
-  const int sup = mega ? imgs * std::max(1, kNllFirstLayerImages / imgs) : imgs;
-  CHK(ensure_capacity(h, sup, imgs * kS, false));
+  FwdPlan F;
+  const bool mega = h->x3 && h->nll_fused && !h->masked && mega_plan(h, F.MG, F.rt, F.waves, F.lds);
+  ChunkWalk W(h, N, k, imgs, mega, x, nullptr, mega);
+  CHK(ensure_capacity(h, W.sup, imgs * kS, false));
   if (h->x3) CHK(ensure_wsplit(h));
   if (mega) CHK(ensure_fx(h));
   if (eps && !mega) return fail(h, IWAE_EINVAL, "injected-noise NLL chunks need the fused kernel");
-  for (int i = 0; i < 8; ++i) MG.eps[i] = (eps && i < h->L) ? eps[i] : nullptr;
-  MG.eps_N = N;
-  NrLaunch NR;
-  const bool ring = mega && nring_plan(h, NR);
-  for (int i = 0; i < 8; ++i) NR.eps[i] = MG.eps[i];
-  NR.eps_N = N;
-  const size_t wbytes = (size_t)h->xdim * sizeof(float);
-  int u0 = 0;                                    // first image of the current first-layer group
-  for (int i0 = 0; i0 < N; i0 += imgs) {
-    const int n = std::min(imgs, N - i0);
-    if (!mega || i0 - u0 >= sup || i0 == 0) {
-      // x (and, fused, the first encoder layer) of the next group: sup images
-      // fused, this chunk's images otherwise
-      u0 = i0;
-      const int ng = std::min(mega ? sup : imgs, N - i0);
-      HIPCHK(hipMemcpy2DAsync(h->x_in.p, (size_t)h->x_in.ld * sizeof(float), x + (size_t)i0 * h->xdim, wbytes,
-                              wbytes, ng, hipMemcpyDeviceToDevice, h->stream));
-      if (mega) CHK(stoch_fwd(h, h->enc[0], h->x_in, ng, h->eb[0]));
-    }
-    const int io = i0 - u0;                      // the chunk's rows in x_in / eb[0]
+  F.ring = mega && nring_plan(h, F.NR);
+  fwd_call_fields(h, F, eps, N);
+  for (; W.i0 < N; W.i0 += imgs) {
+    CHK(walk_step(h, W));
+    const int i0 = W.i0, n = W.n;
     for (int s0 = 0; s0 < k; s0 += kS) {
       Plan P;
       P.B = n; P.Bimg = n; P.Bsplit = n; P.kS = std::min(kS, k - s0);
-      EpsSet E;
-      std::memset(&E, 0, sizeof(E));
-      LseArgs a{};
+      LseArgs a = lse_args(h, P.kS, n, s0 == 0);
       if (mega) {
         // the chunk's rows of the first encoder layer's output, then everything else fused
-        MG.rows = n * P.kS; MG.kS = P.kS;
-        MG.eps_i0 = i0; MG.eps_s0 = s0;
-        MG.P0 = h->eb[0].P.p + (size_t)io * h->eb[0].P.ld; MG.ldP0 = h->eb[0].P.ld;
-        MG.x = h->x_in.p + (size_t)io * h->x_in.ld; MG.ldx = h->x_in.ld;
-        MG.seed = h->seed; MG.rng_base = &h->ds->rng[0];
-        MG.lw = h->lw;
-        if (ring && P.kS >= 128) {
-          // the weight-ring kernel (same rows, same noise; 128 rows per workgroup
-          // span at most two images)
-          NR.rows = MG.rows; NR.kS = MG.kS; NR.eps_i0 = i0; NR.eps_s0 = s0;
-          NR.P0 = MG.P0; NR.ldP0 = MG.ldP0; NR.x = MG.x; NR.ldx = MG.ldx;
-          NR.seed = MG.seed; NR.rng_base = MG.rng_base; NR.lw = MG.lw;
-          HIPCHK(launch_nring(h->stream, NR));
-          ++h->count.nring;
-        } else {
-          HIPCHK(launch_mega_fwd(h->stream, MG, mg_rt, mg_waves, mg_lds));
-        }
-        ++h->count.mega;
-        if (eps) ++h->count.mega_eps;
+        CHK(launch_fwd_chunk(h, F, W, P, s0, eps != nullptr));
         a.lw = h->lw;
       } else {
+        EpsSet E;
+        std::memset(&E, 0, sizeof(E));
         CHK(forward_core(h, P, E, false));
       }
-      a.part = h->part; a.ldpart = h->ldpart; a.npart = h->npart; a.logp = h->logp; a.logq = h->logq;
-      a.kS = P.kS; a.Bimg = n; a.run_m = h->run_m; a.run_s = h->run_s; a.init = s0 == 0;
-      a.ticket = &h->ds->tickets[1]; a.rng_base = &h->ds->rng[0];
       HIPCHK(launch_lse(h->stream, a));
     }
     if (out_logpx) HIPCHK(launch_lse_final(h->stream, h->run_m, h->run_s, n, logf((float)k), out_logpx + i0));
@@ -4300,11 +4516,7 @@ int iwae_nll_eps(iwae_handle* h, const float* x, int N, int k, const float* cons
   CHK(make_plan(h, &lc, N, P));
   EpsSet E;
   CHK(eval_forward(h, P, x, eps, n_eps, E));
-  LseArgs a{};
-  a.part = h->part; a.ldpart = h->ldpart; a.npart = h->npart; a.logp = h->logp; a.logq = h->logq;
-  a.kS = k; a.Bimg = N; a.run_m = h->run_m; a.run_s = h->run_s; a.init = 1;
-  a.ticket = &h->ds->tickets[1]; a.rng_base = &h->ds->rng[0];
-  HIPCHK(launch_lse(h->stream, a));
+  HIPCHK(launch_lse(h->stream, lse_args(h, k, N, true)));
   HIPCHK(launch_lse_final(h->stream, h->run_m, h->run_s, N, logf((float)k), out_logpx));
   return IWAE_OK;
 }
@@ -4327,15 +4539,13 @@ int iwae_encoder_means(iwae_handle* h, const float* x, int N, int n, const float
   imgs = std::min(imgs, N);
   if (h->x3) CHK(ensure_wsplit(h));
   CHK(ensure_capacity(h, imgs, imgs * n, false));
-  const size_t wbytes = (size_t)h->xdim * sizeof(float);
   for (int i0 = 0; i0 < N; i0 += imgs) {
     const int m = std::min(imgs, N - i0);
     Plan P;
     P.B = m; P.Bimg = m; P.Bsplit = m; P.kS = n;
     EpsSet E;
     CHK(parse_eps(h, P, eps, n_eps, E));
-    HIPCHK(hipMemcpy2DAsync(h->x_in.p, (size_t)h->x_in.ld * sizeof(float), x + (size_t)i0 * h->xdim, wbytes,
-                            wbytes, m, hipMemcpyDeviceToDevice, h->stream));
+    CHK(stage_x(h, x, nullptr, i0, m));
     CHK(encoder_fwd(h, P, E, false));
     for (int l = 0; l < h->L; ++l) {
       const int d = h->enc[l].d;
@@ -4397,14 +4607,8 @@ int iwae_reconstruct(iwae_handle* h, const float* x, int B, const float* const* 
   CHK(copy_x(h, P, x));
   CHK(encoder_fwd(h, P, E, false));
   CHK(prior_chain_fwd(h, B, injected ? eps + L : nullptr, nullptr));
-  CHK(gemm_fwd(h, EPI_TANH, h->h[0], B, h->dense[h->o1], h->ob.y1));
-  CHK(gemm_fwd(h, EPI_TANH, h->ob.y1, B, h->dense[h->o2], h->ob.y2));
-  if (probs) {
-    Mat pm;
-    pm.p = probs; pm.ld = ld_probs;
-    CHK(gemm_fwd(h, EPI_STORE, h->ob.y2, B, h->dense[h->o3], pm));
-    HIPCHK(launch_bern_probs(h->stream, probs, B, h->xdim, ld_probs));
-  }
+  CHK(out_hidden(h, B));
+  if (probs) CHK(out_probs(h, B, probs, ld_probs));
   // Keras BCE of x against those probabilities, summed over pixels, mean over
   // the batch (F:257-F:261) = -(E_q log p(x|h) with the BCE form); this pass
   // also advances the Philox base
@@ -4460,12 +4664,8 @@ int iwae_generate(iwae_handle* h, int n, const float* h_top, const float* const*
   const int L = h->L;
   if (n < 0) return fail(h, IWAE_EINVAL, "n must not be negative");
   if (!probs && !pixels) return fail(h, IWAE_EINVAL, "probs and pixels are both NULL");
-  // (ld <= 2^22: a workgroup's 64 rows stay within gen_kernel's 32-bit buffer offsets)
-  constexpr int kMaxLd = 1 << 22;
-  if (probs && (ld_probs < h->xdim || ld_probs > kMaxLd || (ld_probs & 3) || ((uintptr_t)probs & 15)))
-    return fail(h, IWAE_EINVAL, "probs needs x_dim <= ld <= 2^22, a multiple of 4, 16-byte aligned");
-  if (pixels && (ld_pixels < h->xdim || ld_pixels > kMaxLd || (ld_pixels & 3) || ((uintptr_t)pixels & 15)))
-    return fail(h, IWAE_EINVAL, "pixels needs x_dim <= ld <= 2^22, a multiple of 4, 16-byte aligned");
+  CHK(ld_ok(h, probs, ld_probs, "probs"));
+  CHK(ld_ok(h, pixels, ld_pixels, "pixels"));
   const bool injected = eps && n_eps > 0;
   const int need = h_top ? L - 1 : L;
   if (n_eps != 0 && n_eps != need)
@@ -4509,12 +4709,10 @@ int iwae_generate(iwae_handle* h, int n, const float* h_top, const float* const*
   HIPCHK(launch_gen_top(h->stream, h_top ? h_top : eps_top, n, dL, h->h[L - 1].p, h->h[L - 1].ld,
                         keep ? h_out[L - 1] : nullptr, h->seed, &h->ds->rng[0], IWAE_MAX_LAYERS + L - 1));
   CHK(prior_chain_fwd(h, n, eps_pri, keep ? h_out : nullptr));
-  CHK(gemm_fwd(h, EPI_TANH, h->h[0], n, h->dense[h->o1], h->ob.y1));
-  CHK(gemm_fwd(h, EPI_TANH, h->ob.y1, n, h->dense[h->o2], h->ob.y2));
+  CHK(out_hidden(h, n));
   Mat pm;                                        // the logits, then the probabilities, in the caller's buffer
   pm.p = probs ? probs : pixels; pm.ld = probs ? ld_probs : ld_pixels;
-  CHK(gemm_fwd(h, EPI_STORE, h->ob.y2, n, h->dense[h->o3], pm));
-  HIPCHK(launch_bern_probs(h->stream, pm.p, n, h->xdim, pm.ld));
+  CHK(out_probs(h, n, pm.p, pm.ld));
   if (pixels)
     HIPCHK(launch_gen_pixels(h->stream, pm.p, pm.ld, u, n, h->xdim, pixels, ld_pixels, h->seed, &h->ds->rng[0],
                              2 * IWAE_MAX_LAYERS));
@@ -4533,8 +4731,7 @@ int iwae_binarize(iwae_handle* h, const float* x, long long n_src, const long lo
   if (n < 0 || n > (1 << 24)) return fail(h, IWAE_EINVAL, "n must be in [0, 2^24]");
   if (n_src < 0) return fail(h, IWAE_EINVAL, "n_src must not be negative");
   if (!perm && n > n_src) return fail(h, IWAE_EINVAL, "n > n_src needs perm");
-  if (ld_out < h->xdim || ld_out > (1 << 22) || (ld_out & 3) || ((uintptr_t)out & 15))
-    return fail(h, IWAE_EINVAL, "out needs x_dim <= ld <= 2^22, a multiple of 4, 16-byte aligned");
+  CHK(ld_ok(h, out, ld_out, "out"));
   if ((long long)n * ((h->xdim + 3) >> 2) + 255 >= (1LL << 32))
     return fail(h, IWAE_EINVAL, "n * ceil(x_dim / 4) must stay below 2^32 - 255 (one launch)");
   if (n == 0) return IWAE_OK;
@@ -4618,139 +4815,81 @@ static int posterior_core(iwae_handle* h, const float* x, const float* mask, int
                           float* const* h_sir, int n_sir, float* weights, float* ess, float* logpx) {
   const int L = h->L;
   if (!x) return fail(h, IWAE_EINVAL, "x is NULL");
-  if (N <= 0 || k <= 0) return fail(h, IWAE_EINVAL, "N and k must be positive");
-  if (k > (1 << 20)) return fail(h, IWAE_EINVAL, "k above 2^20 per image is not supported");
-  auto ptrs_ok = [&](const float* const* a, int n, const char* what) {
-    if (n == 0) return IWAE_OK;
-    if (n != L || !a)
-      return fail(h, IWAE_EINVAL, std::string("expected ") + std::to_string(L) + " " + what + " buffers (one per "
-                                  "stochastic layer), got " + std::to_string(n));
-    for (int i = 0; i < L; ++i)
-      if (!a[i]) return fail(h, IWAE_EINVAL, std::string("NULL ") + what + " buffer");
-    return IWAE_OK;
-  };
-  CHK(ptrs_ok(eps, n_eps, "eps"));
-  CHK(ptrs_ok(h_mean, n_mean, "h_mean"));
-  CHK(ptrs_ok(h_sir, n_sir, "h_sir"));
+  CHK(nk_ok(h, N, k));
+  CHK(ptrs_ok(h, eps, n_eps, "eps", true));
+  CHK(ptrs_ok(h, h_mean, n_mean, "h_mean", true));
+  CHK(ptrs_ok(h, h_sir, n_sir, "h_sir", true));
   const bool injected = n_eps > 0, want_mean = n_mean > 0, want_sir = n_sir > 0, draw = x_draw != nullptr;
   if (!want_mean && !probs && !draw && !want_sir && !weights && !ess && !logpx)
     return fail(h, IWAE_EINVAL, "every output is NULL");
-  constexpr int kMaxLd = 1 << 22;
-  auto ld_ok = [&](const float* p, int ld, const char* what) {
-    if (p && (ld < h->xdim || ld > kMaxLd || (ld & 3) || ((uintptr_t)p & 15)))
-      return fail(h, IWAE_EINVAL, std::string(what) + " needs x_dim <= ld <= 2^22, a multiple of 4, 16-byte aligned");
-    return IWAE_OK;
-  };
-  CHK(ld_ok(probs, ld_probs, mask ? "x_mean" : "probs"));
-  CHK(ld_ok(x_draw, ld_draw, "x_draw"));
+  CHK(ld_ok(h, probs, ld_probs, mask ? "x_mean" : "probs"));
+  CHK(ld_ok(h, x_draw, ld_draw, "x_draw"));
   const bool need_sir = want_sir || draw;        // the SIR index, and h_1 of the resampled sample
   const bool second = want_mean || probs || need_sir;
   // ---- path and chunk
-  MgLaunch MG;
+  FwdPlan F;
+  MgLaunch& MG = F.MG;
   PoLaunch PO;
-  int mg_rt = 0, mg_waves = 8, po_rt = 0;
-  size_t mg_lds = 0, po_lds = 0;
-  const bool fused = h->x3 && h->nll_fused && h->path != 1 && !h->masked && mega_plan(h, MG, mg_rt, mg_waves, mg_lds) &&
+  int po_rt = 0;
+  size_t po_lds = 0;
+  const bool fused = h->x3 && h->nll_fused && h->path != 1 && !h->masked && mega_plan(h, MG, F.rt, F.waves, F.lds) &&
                      post_plan(h, want_mean || want_sir, probs != nullptr, PO, po_rt, po_lds);
-  if (chunk <= 0) chunk = h->tune.nll_imgs;
-  long long imgs_ll = chunk > 0 ? chunk : std::max<long long>(1, h->tune.nll_rows / k);
   const int ldp = r4(h->xdim);                   // layer-wise: the rows' probabilities, at most 256 MB of them
   const bool rows_px = !fused && (probs || mask);          // (masked: the rows' logits, whatever the call wants)
-  if (rows_px) imgs_ll = std::min(imgs_ll, std::max<long long>(1, (256LL << 20) / ((long long)k * ldp * 4)));
-  const int imgs = (int)std::min<long long>(imgs_ll, N);
-  if ((long long)imgs * k > (1LL << 30)) return fail(h, IWAE_EINVAL, "chunk * k above 2^30 sample rows");
+  const int imgs = chunk_images(h, N, k, chunk, true, rows_px ? ldp * 4 : 0);
+  if (!imgs) return IWAE_EINVAL;
   const int rows = imgs * k;
-  const int sup = fused ? std::min(N, imgs * std::max(1, kNllFirstLayerImages / imgs)) : imgs;
-  CHK(ensure_capacity(h, sup, rows, false));
+  Mat xm;                                        // fused masked calls: the -1 copy of the staged images
+  ChunkWalk W(h, N, k, imgs, fused, x, mask, fused, &xm);
+  CHK(ensure_capacity(h, W.sup, rows, false));
   if (h->x3) CHK(ensure_wsplit(h));
   if (fused) CHK(ensure_fx(h));
-  NrLaunch NR;
-  const bool ring = fused && !mask && k >= 128 && nring_plan(h, NR);
+  F.ring = fused && !mask && k >= 128 && nring_plan(h, F.NR);
   // ---- workspace of its own (floats): w~, SIR indices, then the path's
   const int tiles = fused ? (k + 16 * po_rt - 1) / (16 * po_rt) : 0;
   const bool gather = !fused && injected && imgs < N;     // a chunk's [k][n][d] noise, contiguous
   const int d0 = h->enc[0].d, ldx = h->x_in.ld;
-  size_t off = 0;
-  auto take = [&](size_t n) { const size_t o = off; off += (n + 63) & ~size_t(63); return o; };
-  const size_t o_wt = take(weights ? 0 : rows), o_sir = take(need_sir ? imgs : 0);
-  const size_t o_part = take(fused && second ? (size_t)imgs * tiles * PO.ld_part : 0);
-  const size_t o_pw = take(rows_px ? (size_t)rows * ldp : 0);
+  WsLayout lay;
+  const size_t o_wt = lay.take(weights ? 0 : rows), o_sir = lay.take(need_sir ? imgs : 0);
+  const size_t o_part = lay.take(fused && second ? (size_t)imgs * tiles * PO.ld_part : 0);
+  const size_t o_pw = lay.take(rows_px ? (size_t)rows * ldp : 0);
   size_t o_eps[IWAE_MAX_LAYERS] = {};
-  for (int i = 0; i < L; ++i) o_eps[i] = take(gather ? (size_t)rows * h->enc[i].d : 0);
+  for (int i = 0; i < L; ++i) o_eps[i] = lay.take(gather ? (size_t)rows * h->enc[i].d : 0);
   // masked calls: the -1 copy of the staged images (fused), the rows' Bernoulli sums (layer-wise),
   // h_1 of the resampled samples when the caller keeps no h_sir, and the draw's probabilities
-  const size_t o_xm = take(mask && fused ? (size_t)sup * ldx : 0);
-  const size_t o_rs = take(mask && !fused ? (size_t)rows * 4 : 0);
-  const size_t o_h1 = take(draw && !want_sir ? (size_t)imgs * d0 : 0);
-  const size_t o_dp = take(draw ? (size_t)imgs * ldp : 0);
-  if (off * sizeof(float) > h->post_ws_bytes) {
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->post_ws) (void)hipFree(h->post_ws);
-    h->post_ws = nullptr;
-    h->post_ws_bytes = 0;
-    HIPCHK(hipMalloc(&h->post_ws, off * sizeof(float)));
-    h->post_ws_bytes = off * sizeof(float);
-  }
-  float* ws = reinterpret_cast<float*>(h->post_ws);
+  const size_t o_xm = lay.take(mask && fused ? (size_t)W.sup * ldx : 0);
+  const size_t o_rs = lay.take(mask && !fused ? (size_t)rows * 4 : 0);
+  const size_t o_h1 = lay.take(draw && !want_sir ? (size_t)imgs * d0 : 0);
+  const size_t o_dp = lay.take(draw ? (size_t)imgs * ldp : 0);
+  CHK(h->post_ws.reserve(h, lay.floats));
+  float* ws = h->post_ws.p;
   int* sir = need_sir ? reinterpret_cast<int*>(ws + o_sir) : nullptr;
-  for (int i = 0; i < 8; ++i) MG.eps[i] = NR.eps[i] = PO.eps[i] = (injected && i < L) ? eps[i] : nullptr;
-  MG.eps_N = NR.eps_N = PO.eps_N = N;
-  const size_t wbytes = (size_t)h->xdim * sizeof(float);
-  int u0 = 0;                                    // first image of the current first-layer group (fused)
-  for (int i0 = 0; i0 < N; i0 += imgs) {
-    const int n = std::min(imgs, N - i0);
+  xm.p = mask && fused ? ws + o_xm : nullptr; xm.ld = ldx;
+  fwd_call_fields(h, F, injected ? eps : nullptr, N);
+  for (int i = 0; i < 8; ++i) PO.eps[i] = MG.eps[i];
+  PO.eps_N = N;
+  for (; W.i0 < N; W.i0 += imgs) {
+    CHK(walk_step(h, W));
+    const int i0 = W.i0, n = W.n;
     const float* xc = x + (size_t)i0 * h->xdim;                         // the chunk's images and mask rows
     const float* mc = mask ? mask + (size_t)i0 * h->xdim : nullptr;
-    if (!fused || i0 - u0 >= sup || i0 == 0) {
-      u0 = i0;
-      const int ng = std::min(sup, N - i0);
-      if (mask)
-        HIPCHK(launch_impute_stage(h->stream, xc, mc, ng, h->xdim, h->x_in.p, ldx, fused ? ws + o_xm : nullptr, ldx));
-      else
-        HIPCHK(hipMemcpy2DAsync(h->x_in.p, (size_t)h->x_in.ld * sizeof(float), x + (size_t)i0 * h->xdim, wbytes,
-                                wbytes, ng, hipMemcpyDeviceToDevice, h->stream));
-      if (fused) CHK(stoch_fwd(h, h->enc[0], h->x_in, ng, h->eb[0]));
-    }
-    const int io = i0 - u0;                      // the chunk's rows in x_in / eb[0]
     // ---- pass 1: the chunk's log weights and (m, sum e), as nll_core / iwae_nll_eps
     Plan P;
     P.B = n; P.Bimg = n; P.Bsplit = n; P.kS = k;
-    LseArgs a{};
+    LseArgs a = lse_args(h, k, n, true);
     if (fused) {
-      MG.rows = n * k; MG.kS = k; MG.eps_i0 = i0; MG.eps_s0 = 0;
-      MG.P0 = h->eb[0].P.p + (size_t)io * h->eb[0].P.ld; MG.ldP0 = h->eb[0].P.ld;
-      MG.x = (mask ? ws + o_xm : h->x_in.p) + (size_t)io * ldx; MG.ldx = ldx;
-      MG.seed = h->seed; MG.rng_base = &h->ds->rng[0];
-      MG.lw = h->lw;
       if (mask) {
-        HIPCHK(launch_mega_fwd_masked(h->stream, MG, mg_rt, mg_waves, mg_lds));
+        chunk_rows(h, W, k, xm, MG);
+        MG.eps_i0 = i0; MG.eps_s0 = 0;
+        HIPCHK(launch_mega_fwd_masked(h->stream, MG, F.rt, F.waves, F.lds));
         ++h->count.imp;
       } else {
-        if (ring) {
-          NR.rows = MG.rows; NR.kS = MG.kS; NR.eps_i0 = i0; NR.eps_s0 = 0;
-          NR.P0 = MG.P0; NR.ldP0 = MG.ldP0; NR.x = MG.x; NR.ldx = MG.ldx;
-          NR.seed = MG.seed; NR.rng_base = MG.rng_base; NR.lw = MG.lw;
-          HIPCHK(launch_nring(h->stream, NR));
-          ++h->count.nring;
-        } else {
-          HIPCHK(launch_mega_fwd(h->stream, MG, mg_rt, mg_waves, mg_lds));
-        }
-        ++h->count.mega;
-        if (injected) ++h->count.mega_eps;
+        CHK(launch_fwd_chunk(h, F, W, P, 0, injected));
       }
       a.lw = h->lw;
     } else {
       EpsSet E;
-      std::memset(&E, 0, sizeof(E));
-      for (int i = 0; injected && i < L; ++i) {
-        E.a[i] = eps[i];
-        if (gather) {                            // sample s of the chunk's images: n * d floats at (s * N + i0) * d
-          const size_t rb = (size_t)n * h->enc[i].d * sizeof(float);
-          HIPCHK(hipMemcpy2DAsync(ws + o_eps[i], rb, eps[i] + (size_t)i0 * h->enc[i].d,
-                                  (size_t)N * h->enc[i].d * sizeof(float), rb, k, hipMemcpyDeviceToDevice, h->stream));
-          E.a[i] = ws + o_eps[i];
-        }
-      }
+      CHK(chunk_eps(h, W, injected ? eps : nullptr, gather, ws, o_eps, E));
       if (mask) {
         Mat Z;
         Z.p = ws + o_pw; Z.ld = ldp;
@@ -4760,10 +4899,7 @@ static int posterior_core(iwae_handle* h, const float* x, const float* mask, int
         CHK(forward_core(h, P, E, false));
       }
     }
-    a.part = h->part; a.ldpart = h->ldpart; a.npart = h->npart; a.logp = h->logp; a.logq = h->logq;
     if (mask && !fused) { a.part = ws + o_rs; a.ldpart = 4; a.npart = 1; }
-    a.kS = k; a.Bimg = n; a.run_m = h->run_m; a.run_s = h->run_s; a.init = 1;
-    a.ticket = &h->ds->tickets[1]; a.rng_base = &h->ds->rng[0];
     HIPCHK(launch_lse(h->stream, a));
     if (logpx) HIPCHK(launch_lse_final(h->stream, h->run_m, h->run_s, n, logf((float)k), logpx + i0));
     if (!second && !weights && !ess) continue;
@@ -4818,16 +4954,11 @@ static int posterior_core(iwae_handle* h, const float* x, const float* mask, int
                                  want_mean ? h_mean[i] + (size_t)i0 * d : nullptr, d, sir, sel(i), d));
       }
       if (probs) {
-        Mat pm;
-        pm.p = ws + o_pw; pm.ld = ldp;
-        if (!mask) {
-          // the output MLP's o1 / o2 outputs of these rows are pass 1's (its Bernoulli
-          // GEMM read them from ob.y2): the output Dense again, storing the logits
-          CHK(gemm_fwd(h, EPI_STORE, h->ob.y2, n * k, h->dense[h->o3], pm));
-          HIPCHK(launch_bern_probs(h->stream, pm.p, n * k, h->xdim, ldp));
-        }                                        // (masked: pass 1 left the rows' probabilities there)
-        HIPCHK(launch_group_wsum(h->stream, pm.p, ldp, k, h->xdim, n, w.wt, probs + (size_t)i0 * ld_probs, ld_probs,
-                                 nullptr, nullptr, 0));
+        // the output MLP's o1 / o2 outputs of these rows are pass 1's (its Bernoulli GEMM read them from
+        // ob.y2): the output Dense again, storing the logits (masked: pass 1 left the rows' probabilities there)
+        if (!mask) CHK(out_probs(h, n * k, ws + o_pw, ldp));
+        HIPCHK(launch_group_wsum(h->stream, ws + o_pw, ldp, k, h->xdim, n, w.wt, probs + (size_t)i0 * ld_probs,
+                                 ld_probs, nullptr, nullptr, 0));
       }
     }
     if (!mask) continue;
@@ -4838,13 +4969,9 @@ static int posterior_core(iwae_handle* h, const float* x, const float* mask, int
       // reader of this chunk's h[0] / ob rows is ahead on the stream)
       HIPCHK(hipMemcpy2DAsync(h->h[0].p, (size_t)h->h[0].ld * sizeof(float), sel(0), (size_t)d0 * sizeof(float),
                               (size_t)d0 * sizeof(float), n, hipMemcpyDeviceToDevice, h->stream));
-      CHK(gemm_fwd(h, EPI_TANH, h->h[0], n, h->dense[h->o1], h->ob.y1));
-      CHK(gemm_fwd(h, EPI_TANH, h->ob.y1, n, h->dense[h->o2], h->ob.y2));
-      Mat pm;
-      pm.p = ws + o_dp; pm.ld = ldp;
-      CHK(gemm_fwd(h, EPI_STORE, h->ob.y2, n, h->dense[h->o3], pm));
-      HIPCHK(launch_bern_probs(h->stream, pm.p, n, h->xdim, ldp));
-      HIPCHK(launch_impute_draw(h->stream, xc, mc, pm.p, ldp, u_pix ? u_pix + (size_t)i0 * h->xdim : nullptr, n,
+      CHK(out_hidden(h, n));
+      CHK(out_probs(h, n, ws + o_dp, ldp));
+      HIPCHK(launch_impute_draw(h->stream, xc, mc, ws + o_dp, ldp, u_pix ? u_pix + (size_t)i0 * h->xdim : nullptr, n,
                                 h->xdim, x_draw + (size_t)i0 * ld_draw, ld_draw, h->seed, &h->ds->rng[1],
                                 2 * IWAE_MAX_LAYERS + 2));
     }
@@ -4875,17 +5002,6 @@ int iwae_impute(iwae_handle* h, const float* x, const float* mask, int N, int k,
 }
 
 // ------------------------------------------------ scoring given latents
-// Images per chunk of iwae_score / iwae_encode (iwae_posterior's rule); 0 with the error set.
-static int score_chunk(iwae_handle* h, int N, int k, int chunk) {
-  if (N <= 0 || k <= 0) { fail(h, IWAE_EINVAL, "N and k must be positive"); return 0; }
-  if (k > (1 << 20)) { fail(h, IWAE_EINVAL, "k above 2^20 per image is not supported"); return 0; }
-  if (chunk <= 0) chunk = h->tune.nll_imgs;
-  const long long imgs_ll = chunk > 0 ? chunk : std::max<long long>(1, h->tune.nll_rows / k);
-  const int imgs = (int)std::min<long long>(imgs_ll, N);
-  if ((long long)imgs * k > (1LL << 30)) { fail(h, IWAE_EINVAL, "chunk * k above 2^30 sample rows"); return 0; }
-  return imgs;
-}
-
 // score_kernel's launch from mega_fwd_kernel's plan MG (same buffers, row
 // tiles and LDS): the chains of the outputs asked for, heads as density heads.
 // mega_plan's stage order: encoder layers 1 .. L-1, prior layers 0 .. L-2, the
@@ -4914,21 +5030,6 @@ static void score_plan(const iwae_handle* h, const MgLaunch& MG, bool q, bool ph
   S.want_ph = ph ? 1 : 0;
 }
 
-// The chunk's (or the first-layer group's) ng images from row i0 on into x_in:
-// a copy, or with a pixel mask the two staged copies by select (x_in = mask ?
-// x : 0, x_lik = mask ? x : -1; impute_stage_kernel).
-static int score_stage_x(iwae_handle* h, const float* x, const float* mask, int i0, int ng) {
-  if (mask) {
-    HIPCHK(launch_impute_stage(h->stream, x + (size_t)i0 * h->xdim, mask + (size_t)i0 * h->xdim, ng, h->xdim, h->x_in.p,
-                               h->x_in.ld, h->x_lik.p, h->x_lik.ld));
-    return IWAE_OK;
-  }
-  const size_t wbytes = (size_t)h->xdim * sizeof(float);
-  HIPCHK(hipMemcpy2DAsync(h->x_in.p, (size_t)h->x_in.ld * sizeof(float), x + (size_t)i0 * h->xdim, wbytes, wbytes, ng,
-                          hipMemcpyDeviceToDevice, h->stream));
-  return IWAE_OK;
-}
-
 // iwae_score and iwae_score_masked (mask: [N][x_dim], non-zero = observed; null: none)
 static int score_core(iwae_handle* h, const float* x, const float* mask, int N, int k, int chunk,
                       const float* const* lat, int n_lat, float* log_q, float* log_ph, float* log_px, float* probs,
@@ -4938,24 +5039,18 @@ static int score_core(iwae_handle* h, const float* x, const float* mask, int N, 
   const int L = h->L;
   if (!log_q && !log_ph && !log_px && !probs) return fail(h, IWAE_EINVAL, "every output is NULL");
   if (!x && (log_q || log_px)) return fail(h, IWAE_EINVAL, "x is NULL (log_q and log_px need the images)");
-  if (n_lat != L || !lat)
-    return fail(h, IWAE_EINVAL, "expected " + std::to_string(L) + " latent buffers (one per stochastic layer), got " +
-                                   std::to_string(n_lat));
-  for (int i = 0; i < L; ++i)
-    if (!lat[i]) return fail(h, IWAE_EINVAL, "NULL latent buffer");
-  if (probs && (ld_probs < h->xdim || ld_probs > (1 << 22) || (ld_probs & 3) || ((uintptr_t)probs & 15)))
-    return fail(h, IWAE_EINVAL, "probs needs x_dim <= ld <= 2^22, a multiple of 4, 16-byte aligned");
-  const int imgs = score_chunk(h, N, k, chunk);
+  CHK(ptrs_ok(h, lat, n_lat, "latent", false));
+  CHK(ld_ok(h, probs, ld_probs, "probs"));
+  const int imgs = chunk_images(h, N, k, chunk);
   if (!imgs) return IWAE_EINVAL;
   const bool want_out = log_px || probs;
   MgLaunch MG;
   int mg_rt = 0, mg_waves = 8;
   size_t mg_lds = 0;
   const bool fused = h->x3 && h->nll_fused && h->path != 1 && !h->masked && mega_plan(h, MG, mg_rt, mg_waves, mg_lds);
-  const int rows = imgs * k;
   // fused: the first encoder layer runs once per group of images, as nll_core's; no row buffer is used
-  const int sup = fused ? std::min(N, imgs * std::max(1, kNllFirstLayerImages / imgs)) : imgs;
-  CHK(ensure_capacity(h, sup, fused ? 1 : rows, false));
+  ChunkWalk W(h, N, k, imgs, fused, x, mask, log_q != nullptr);
+  CHK(ensure_capacity(h, W.sup, fused ? 1 : imgs * k, false));
   if (h->x3) CHK(ensure_wsplit(h));
   if (fused) CHK(ensure_fx(h));
   ScLaunch SC;
@@ -4966,21 +5061,13 @@ static int score_core(iwae_handle* h, const float* x, const float* mask, int N, 
     SC.rng_base = nullptr; SC.seed = 0; SC.lw = nullptr;
   }
   const Mat& xl = mask ? h->x_lik : h->x_in;      // the likelihood's copy of the images
-  int u0 = 0;                                    // first image of the current first-layer group (fused)
-  for (int i0 = 0; i0 < N; i0 += imgs) {
-    const int n = std::min(imgs, N - i0), M = n * k;
-    const size_t r0 = (size_t)i0 * k;            // the chunk's first row of the [N][k] outputs
-    if (x && (!fused || i0 - u0 >= sup || i0 == 0)) {
-      u0 = i0;
-      const int ng = std::min(sup, N - i0);
-      CHK(score_stage_x(h, x, mask, i0, ng));
-      if (log_q) CHK(stoch_fwd(h, h->enc[0], h->x_in, ng, h->eb[0]));
-    }
-    const int io = x ? i0 - u0 : 0;              // the chunk's rows in x_in / eb[0]
+  for (; W.i0 < N; W.i0 += imgs) {
+    CHK(walk_step(h, W));
+    const int i0 = W.i0, M = W.n * k;
+    const size_t r0 = W.r0;
     if (fused) {
-      SC.rows = M; SC.kS = k; SC.eps_i0 = i0;
-      SC.P0 = h->eb[0].P.p + (size_t)io * h->eb[0].P.ld; SC.ldP0 = h->eb[0].P.ld;
-      SC.x = xl.p + (size_t)io * xl.ld; SC.ldx = xl.ld;
+      chunk_rows(h, W, k, xl, SC);
+      SC.eps_i0 = i0;
       SC.log_q = log_q ? log_q + r0 : nullptr;
       SC.log_ph = log_ph ? log_ph + r0 : nullptr;
       SC.log_px = log_px ? log_px + r0 : nullptr;
@@ -4996,40 +5083,19 @@ static int score_core(iwae_handle* h, const float* x, const float* mask, int N, 
     }
     // ---- layer-wise: the latents into the workspace's rows, then forward_core's launches as density passes
     ++(mask ? h->count.score_pix_lw : h->count.score_lw);
-    ScRelayout G{};
-    G.n = n; G.k = k; G.N = N; G.i0 = i0; G.gather = 1;
-    for (int i = 0; i < L; ++i)
-      G.seg[G.nseg++] = ScSeg{h->h[i].p, h->h[i].ld, 0, h->enc[i].d, const_cast<float*>(lat[i]), 0, 0};
-    HIPCHK(launch_score_relayout(h->stream, G));
+    CHK(gather_latents(h, W, lat));
     for (int i = 0; log_q && i < L; ++i) {
       if (i > 0) CHK(stoch_fwd(h, h->enc[i], h->h[i - 1], M, h->eb[i]));
-      GaussArgs g{};
-      g.P = h->eb[i].P.p; g.ldP = h->eb[i].P.ld; g.prow_div = i == 0 ? k : 1; g.d = h->enc[i].d;
-      g.H = h->h[i].p; g.ldH = h->h[i].ld;
-      g.out = log_q + r0; g.accumulate = i > 0; g.M = M;
-      HIPCHK(launch_gauss_fwd(h->stream, 1, g));
+      CHK(gauss_logdens(h, h->eb[i].P, i == 0 ? k : 1, h->enc[i].d, h->h[i], log_q + r0, i > 0, M));
     }
     if (log_ph) CHK(prior_fwd(h, M, log_ph + r0));
-    if (want_out) {
-      CHK(gemm_fwd(h, EPI_TANH, h->h[0], M, h->dense[h->o1], h->ob.y1));
-      CHK(gemm_fwd(h, EPI_TANH, h->ob.y1, M, h->dense[h->o2], h->ob.y2));
-    }
+    if (want_out) CHK(out_hidden(h, M));
     if (log_px) {
-      GemmArgs ex{};
-      ex.aux = xl.p; ex.ldaux = xl.ld; ex.x_row_div = k;
-      ex.part = h->part; ex.part2 = h->part2; ex.ldpart = h->ldpart;
-      ex.wa = 1.f; ex.wb = 0.f;
       Mat none;
-      CHK(gemm_fwd(h, mask ? EPI_BERN_MASK : EPI_BERN, h->ob.y2, M, h->dense[h->o3], none, ex));
+      CHK(gemm_fwd(h, mask ? EPI_BERN_MASK : EPI_BERN, h->ob.y2, M, h->dense[h->o3], none, bern_args(h, xl, k, 1.f)));
       HIPCHK(launch_score_rowsum(h->stream, h->part, h->ldpart, h->npart, M, log_px + r0));
     }
-    if (probs) {
-      // the output Dense's logits into the caller's rows, turned into probabilities in place
-      Mat pm;
-      pm.p = probs + r0 * ld_probs; pm.ld = ld_probs;
-      CHK(gemm_fwd(h, EPI_STORE, h->ob.y2, M, h->dense[h->o3], pm));
-      HIPCHK(launch_bern_probs(h->stream, pm.p, M, h->xdim, ld_probs));
-    }
+    if (probs) CHK(out_probs(h, M, probs + r0 * ld_probs, ld_probs));
   }
   return IWAE_OK;
 }
@@ -5167,23 +5233,20 @@ static int sgrad_core(iwae_handle* h, const float* x, const float* mask, int N, 
   if (!coef) return fail(h, IWAE_EINVAL, "coef is NULL");
   for (int t = 0; t < 3; ++t)
     if (!std::isfinite(coef[t])) return fail(h, IWAE_EINVAL, "coef must be finite");
-  if (n_lat != L || !lat)
-    return fail(h, IWAE_EINVAL, "expected " + std::to_string(L) + " latent buffers (one per stochastic layer), got " +
-                                   std::to_string(n_lat));
+  CHK(ptrs_ok(h, lat, n_lat, "latent", false));
   if (n_grad != 0 && (n_grad != L || !grad))
     return fail(h, IWAE_EINVAL, "expected 0 or " + std::to_string(L) + " gradient buffers, got " + std::to_string(n_grad));
-  for (int i = 0; i < L; ++i) {
-    if (!lat[i]) return fail(h, IWAE_EINVAL, "NULL latent buffer");
-    if (n_grad && !grad[i]) return fail(h, IWAE_EINVAL, "NULL gradient buffer");
-  }
+  for (int i = 0; n_grad && i < L; ++i)
+    if (!grad[i]) return fail(h, IWAE_EINVAL, "NULL gradient buffer");
   const bool want_g = n_grad > 0;
   const float cq = coef[0], cph = coef[1], cpx = coef[2];
   const bool gq = want_g && cq != 0.f, gph = want_g && cph != 0.f, gpx = want_g && cpx != 0.f;
   const bool run_q = gq || log_q, run_ph = gph || log_ph, run_px = gpx || log_px;
   if (!x && (run_q || run_px))
     return fail(h, IWAE_EINVAL, "x is NULL (log q and log p(x|h), values or gradient terms, need the images)");
-  int imgs = score_chunk(h, N, k, chunk);
+  int imgs = chunk_images(h, N, k, chunk);
   if (!imgs) return IWAE_EINVAL;
+  const Mat& xl = mask ? h->x_lik : h->x_in;      // the likelihood's copy of the images
   // ---- fused: one sg_kernel launch per chunk where iwae_score's fused path applies and the plan fits
   {
     MgLaunch MG;
@@ -5195,8 +5258,8 @@ static int sgrad_core(iwae_handle* h, const float* x, const float* mask, int N, 
                                   sg_lds);
     if (fused) {
       // the first encoder layer runs once per group of images, as iwae_score's; no row buffer is used
-      const int sup = std::min(N, imgs * std::max(1, kNllFirstLayerImages / imgs));
-      CHK(ensure_capacity(h, sup, 1, false));
+      ChunkWalk W(h, N, k, imgs, true, x, mask, run_q);
+      CHK(ensure_capacity(h, W.sup, 1, false));
       CHK(ensure_wsplit(h));
       CHK(ensure_fx(h));
       SG.fx_hi = h->fx_hi; SG.fx_lo = h->fx_lo; SG.fx_elems = h->fx_elems;
@@ -5204,21 +5267,11 @@ static int sgrad_core(iwae_handle* h, const float* x, const float* mask, int N, 
       SG.lat_N = N;
       SG.cq = gq ? cq : 0.f; SG.cph = gph ? cph : 0.f;
       SG.want_q = log_q ? 1 : 0; SG.want_ph = log_ph ? 1 : 0;
-      const Mat& xl = mask ? h->x_lik : h->x_in;    // the likelihood's copy of the images
-      int u0 = 0;                                  // first image of the current first-layer group
-      for (int i0 = 0; i0 < N; i0 += imgs) {
-        const int n = std::min(imgs, N - i0);
-        const size_t r0 = (size_t)i0 * k;
-        if (x && (i0 - u0 >= sup || i0 == 0)) {
-          u0 = i0;
-          const int ng = std::min(sup, N - i0);
-          CHK(score_stage_x(h, x, mask, i0, ng));
-          if (run_q) CHK(stoch_fwd(h, h->enc[0], h->x_in, ng, h->eb[0]));
-        }
-        const int io = x ? i0 - u0 : 0;            // the chunk's rows in x_in / eb[0]
-        SG.rows = n * k; SG.kS = k; SG.lat_i0 = i0;
-        SG.P0 = h->eb[0].P.p + (size_t)io * h->eb[0].P.ld; SG.ldP0 = h->eb[0].P.ld;
-        SG.x = xl.p + (size_t)io * xl.ld; SG.ldx = xl.ld;
+      for (; W.i0 < N; W.i0 += imgs) {
+        CHK(walk_step(h, W));
+        const size_t r0 = W.r0;
+        chunk_rows(h, W, k, xl, SG);
+        SG.lat_i0 = W.i0;
         SG.log_q = log_q ? log_q + r0 : nullptr;
         SG.log_ph = log_ph ? log_ph + r0 : nullptr;
         SG.log_px = log_px ? log_px + r0 : nullptr;
@@ -5235,7 +5288,7 @@ static int sgrad_core(iwae_handle* h, const float* x, const float* mask, int N, 
   }
   const int ldp = r4(h->xdim), Ho = h->dense[h->o1].fout;
   // a chunk's dlogits: at most 256 MB of them (iwae_posterior's rule for its rows of probabilities)
-  if (gpx) imgs = (int)std::min<long long>(imgs, std::max<long long>(1, (256LL << 20) / ((long long)k * ldp * 4)));
+  if (gpx) imgs = cap_chunk_bytes(imgs, k, ldp * 4);
   const int rows = imgs * k;
   CHK(ensure_capacity(h, imgs, rows, false));
   if (h->x3) CHK(ensure_wsplit(h));
@@ -5246,15 +5299,13 @@ static int sgrad_core(iwae_handle* h, const float* x, const float* mask, int N, 
   std::map<int, Mat> dPs, dY2s, dY1s;
   if (want_g) {
     const int R = std::max(rows, h->sg_rows);
-    size_t off = 0;
+    WsLayout lay;
     std::vector<Mat*> all;
     auto mat = [&](Mat& m, int width) {
       m.ld = r4(width);
       m.p = nullptr;
       all.push_back(&m);
-      const size_t o = off;
-      off += ((size_t)R * m.ld + 63) & ~size_t(63);
-      return o;
+      return lay.take((size_t)R * m.ld);
     };
     std::vector<size_t> offs;
     auto hid = [&](int H) {
@@ -5270,18 +5321,12 @@ static int sgrad_core(iwae_handle* h, const float* x, const float* mask, int N, 
     offs.push_back(mat(Xo, h->enc[0].d));
     for (int i = 0; i < L; ++i)
       for (Mat* m : {&Tq[i], &Xq[i], &Tp[i], &Xp[i]}) offs.push_back(mat(*m, h->enc[i].d));
-    const size_t small = off;
+    const size_t small = lay.floats;
     offs.push_back(mat(dlogit, h->xdim));                         // last and largest: present once a call needs it
-    const size_t need = gpx ? off : small;
-    if (R > h->sg_rows || need > h->sg_ws_floats) {
-      HIPCHK(hipStreamSynchronize(h->stream));
-      if (h->sg_ws) (void)hipFree(h->sg_ws);
-      h->sg_ws = nullptr; h->sg_ws_floats = 0; h->sg_rows = 0;
-      HIPCHK(hipMalloc(&h->sg_ws, need * sizeof(float)));
-      HIPCHK(hipMemsetAsync(h->sg_ws, 0, need * sizeof(float), h->stream));
-      h->sg_ws_floats = need; h->sg_rows = R;
-    }
-    for (size_t i = 0; i < all.size(); ++i) all[i]->p = h->sg_ws + offs[i];
+    // (more rows are a new layout: allocated afresh and zeroed whatever the size)
+    CHK(h->sg_ws.reserve(h, gpx ? lay.floats : small, true, R > h->sg_rows));
+    h->sg_rows = R;
+    for (size_t i = 0; i < all.size(); ++i) all[i]->p = h->sg_ws.p + offs[i];
     if (!gpx) dlogit = Mat();
   }
   // dP (one chain's head gradients) back through head -> l2 -> l1 into dx
@@ -5302,30 +5347,16 @@ static int sgrad_core(iwae_handle* h, const float* x, const float* mask, int N, 
     HIPCHK(launch_sg_dens(h->stream, a));
     return IWAE_OK;
   };
-  const Mat& xl = mask ? h->x_lik : h->x_in;      // the likelihood's copy of the images
-  for (int i0 = 0; i0 < N; i0 += imgs) {
-    const int n = std::min(imgs, N - i0), M = n * k;
-    const size_t r0 = (size_t)i0 * k;            // the chunk's first row of the [N][k] outputs
-    if (x) {
-      CHK(score_stage_x(h, x, mask, i0, n));
-      if (run_q) CHK(stoch_fwd(h, h->enc[0], h->x_in, n, h->eb[0]));
-    }
+  for (ChunkWalk W(h, N, k, imgs, false, x, mask, run_q); W.i0 < N; W.i0 += imgs) {
+    CHK(walk_step(h, W));
+    const int i0 = W.i0, n = W.n, M = n * k;
+    const size_t r0 = W.r0;                      // the chunk's first row of the [N][k] outputs
     ++(mask ? h->count.sgrad_pix_lw : h->count.sgrad_lw);
-    ScRelayout G{};
-    G.n = n; G.k = k; G.N = N; G.i0 = i0; G.gather = 1;
-    for (int i = 0; i < L; ++i)
-      G.seg[G.nseg++] = ScSeg{h->h[i].p, h->h[i].ld, 0, h->enc[i].d, const_cast<float*>(lat[i]), 0, 0};
-    HIPCHK(launch_score_relayout(h->stream, G));
+    CHK(gather_latents(h, W, lat));
     // ---- log q: chain i scores h_{i+1} under enc_i(h_i); its dX is h_i's
     for (int i = 0; run_q && i < L; ++i) {
       if (i > 0) CHK(stoch_fwd(h, h->enc[i], h->h[i - 1], M, h->eb[i]));
-      if (log_q) {
-        GaussArgs g{};
-        g.P = h->eb[i].P.p; g.ldP = h->eb[i].P.ld; g.prow_div = i == 0 ? k : 1; g.d = h->enc[i].d;
-        g.H = h->h[i].p; g.ldH = h->h[i].ld;
-        g.out = log_q + r0; g.accumulate = i > 0; g.M = M;
-        HIPCHK(launch_gauss_fwd(h->stream, 1, g));
-      }
+      if (log_q) CHK(gauss_logdens(h, h->eb[i].P, i == 0 ? k : 1, h->enc[i].d, h->h[i], log_q + r0, i > 0, M));
       if (!gq) continue;
       CHK(dens(h->eb[i].P, i == 0 ? k : 1, h->enc[i].d, h->h[i], Tq[i], i > 0, M));
       if (i > 0) CHK(chain_bwd(h->enc[i], M, h->eb[i], Xq[i - 1]));
@@ -5340,25 +5371,15 @@ static int sgrad_core(iwae_handle* h, const float* x, const float* mask, int N, 
     for (int j = 0; run_ph && j < L - 1; ++j) {
       const int src = L - 1 - j, t = L - 2 - j;
       CHK(stoch_fwd(h, h->dec[j], h->h[src], M, h->db[j]));
-      if (log_ph) {
-        GaussArgs g{};
-        g.P = h->db[j].P.p; g.ldP = h->db[j].P.ld; g.prow_div = 1; g.d = h->dec[j].d;
-        g.H = h->h[t].p; g.ldH = h->h[t].ld;
-        g.out = log_ph + r0; g.accumulate = 1; g.M = M;
-        HIPCHK(launch_gauss_fwd(h->stream, 1, g));
-      }
+      if (log_ph) CHK(gauss_logdens(h, h->db[j].P, 1, h->dec[j].d, h->h[t], log_ph + r0, true, M));
       if (!gph) continue;
       CHK(dens(h->db[j].P, 1, h->dec[j].d, h->h[t], Tp[t], true, M));
       CHK(chain_bwd(h->dec[j], M, h->db[j], Xp[src]));
     }
     // ---- log p(x|h_1): the Bernoulli epilogue with the constant row weight c_px writes c_px dlogit
     if (run_px) {
-      CHK(gemm_fwd(h, EPI_TANH, h->h[0], M, h->dense[h->o1], h->ob.y1));
-      CHK(gemm_fwd(h, EPI_TANH, h->ob.y1, M, h->dense[h->o2], h->ob.y2));
-      GemmArgs ex{};
-      ex.aux = xl.p; ex.ldaux = xl.ld; ex.x_row_div = k;
-      ex.part = h->part; ex.part2 = h->part2; ex.ldpart = h->ldpart;
-      ex.wa = gpx ? cpx : 1.f; ex.wb = 0.f;
+      CHK(out_hidden(h, M));
+      GemmArgs ex = bern_args(h, xl, k, gpx ? cpx : 1.f);
       ex.store_g = gpx ? 1 : 0;
       Mat gm;
       if (gpx) gm = dlogit;
@@ -5421,11 +5442,7 @@ static int ais_core(iwae_handle* h, const float* x, const float* mask, int N, in
   if (!cfg) return fail(h, IWAE_EINVAL, "cfg is NULL");
   if (!betas) return fail(h, IWAE_EINVAL, "betas is NULL");
   if (!x) return fail(h, IWAE_EINVAL, "x is NULL");
-  if (n_lat != L || !lat)
-    return fail(h, IWAE_EINVAL, "expected " + std::to_string(L) + " latent buffers (one per stochastic layer), got " +
-                                   std::to_string(n_lat));
-  for (int i = 0; i < L; ++i)
-    if (!lat[i]) return fail(h, IWAE_EINVAL, "NULL latent buffer");
+  CHK(ptrs_ok(h, lat, n_lat, "latent", false));
   if (cfg->init != 0 && cfg->init != 1) return fail(h, IWAE_EINVAL, "init must be 0 (the prior) or 1 (q)");
   const int T = cfg->n_temps, nl = cfg->n_leapfrog;
   if (T < 1 || T > (1 << 24)) return fail(h, IWAE_EINVAL, "n_temps must be in [1, 2^24]");
@@ -5443,30 +5460,23 @@ static int ais_core(iwae_handle* h, const float* x, const float* mask, int N, in
                                    std::to_string(n_mom));
   for (int i = 0; i < n_mom; ++i)
     if (!mom[i]) return fail(h, IWAE_EINVAL, "NULL momentum buffer");
-  if (!score_chunk(h, N, k, chunk)) return IWAE_EINVAL;
+  if (!chunk_images(h, N, k, chunk)) return IWAE_EINVAL;
   const long long chains = (long long)N * k;
   if (chains > (1LL << 30)) return fail(h, IWAE_EINVAL, "N * k above 2^30 chains");
   // ---- the chains' buffers: per layer r, q, g [k][N][d_i]; per chain H_old, log q, log p(h), log p(x|h), and
-  // the weights / steps where the caller gave none.  Each starts on a 64-float boundary.
-  size_t off = 0;
-  auto take = [&](size_t n) { const size_t o = off; off += (n + 63) & ~size_t(63); return o; };
+  // the weights / steps where the caller gave none
+  WsLayout lay;
   size_t o_r[IWAE_MAX_LAYERS], o_q[IWAE_MAX_LAYERS], o_g[IWAE_MAX_LAYERS];
   int dmax = 0;
   for (int i = 0; i < L; ++i) {
     const size_t n = (size_t)chains * h->enc[i].d;
-    o_r[i] = take(n); o_q[i] = take(n); o_g[i] = take(n);
+    o_r[i] = lay.take(n); o_q[i] = lay.take(n); o_g[i] = lay.take(n);
     dmax = std::max(dmax, h->enc[i].d);
   }
-  const size_t o_H = take(chains), o_lq = take(chains), o_lph = take(chains), o_lpx = take(chains);
-  const size_t o_w = take(chains), o_step = take(chains);
-  if (off > h->ais_ws_floats) {
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->ais_ws) (void)hipFree(h->ais_ws);
-    h->ais_ws = nullptr; h->ais_ws_floats = 0;
-    HIPCHK(hipMalloc(&h->ais_ws, off * sizeof(float)));
-    h->ais_ws_floats = off;
-  }
-  float* ws = h->ais_ws;
+  const size_t o_H = lay.take(chains), o_lq = lay.take(chains), o_lph = lay.take(chains), o_lpx = lay.take(chains);
+  const size_t o_w = lay.take(chains), o_step = lay.take(chains);
+  CHK(h->ais_ws.reserve(h, lay.floats));
+  float* ws = h->ais_ws.p;
   AisArgs a{};
   a.L = L; a.N = N; a.k = k; a.chains = chains;
   a.group = dmax <= 64 ? 16 : 64;
@@ -5580,32 +5590,25 @@ static int refine_core(iwae_handle* h, const float* x, const float* mask, int N,
   for (int i = 0; i < n_adam; ++i)
     if (!adam[i]) return fail(h, IWAE_EINVAL, "NULL Adam buffer");
   if (cfg->step0 > 0 && n_adam == 0) return fail(h, IWAE_EINVAL, "step0 > 0 continues a run: it needs the Adam buffers");
-  if (!score_chunk(h, N, k, chunk)) return IWAE_EINVAL;
+  if (!chunk_images(h, N, k, chunk)) return IWAE_EINVAL;
   const long long rows = (long long)N * k;
   if (rows > (1LL << 30)) return fail(h, IWAE_EINVAL, "N * k above 2^30 rows");
   // ---- the samples' buffers: per layer latents, noise, gradients [k][N][d_i]; per row log p(h), log p(x|h), the
-  // weights; the moments [N][d_i] where the caller gave none.  Each starts on a 64-float boundary.
-  size_t off = 0;
-  auto take = [&](size_t n) { const size_t o = off; off += (n + 63) & ~size_t(63); return o; };
+  // weights; the moments [N][d_i] where the caller gave none
+  WsLayout lay;
   size_t o_h[IWAE_MAX_LAYERS], o_e[IWAE_MAX_LAYERS], o_g[IWAE_MAX_LAYERS], o_m[IWAE_MAX_LAYERS][4];
   int dmax = 0, D = 0;
   for (int i = 0; i < L; ++i) {
     const int d = h->enc[i].d;
     const size_t n = (size_t)rows * d;
-    o_h[i] = take(n); o_e[i] = take(n); o_g[i] = take(n);
-    for (int j = 0; j < 4; ++j) o_m[i][j] = n_adam ? 0 : take((size_t)N * d);
+    o_h[i] = lay.take(n); o_e[i] = lay.take(n); o_g[i] = lay.take(n);
+    for (int j = 0; j < 4; ++j) o_m[i][j] = n_adam ? 0 : lay.take((size_t)N * d);
     dmax = std::max(dmax, d);
     D += d;
   }
-  const size_t o_lph = take(rows), o_lpx = take(rows), o_w = take(rows);
-  if (off > h->refine_ws_floats) {
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->refine_ws) (void)hipFree(h->refine_ws);
-    h->refine_ws = nullptr; h->refine_ws_floats = 0;
-    HIPCHK(hipMalloc(&h->refine_ws, off * sizeof(float)));
-    h->refine_ws_floats = off;
-  }
-  float* ws = h->refine_ws;
+  const size_t o_lph = lay.take(rows), o_lpx = lay.take(rows), o_w = lay.take(rows);
+  CHK(h->refine_ws.reserve(h, lay.floats));
+  float* ws = h->refine_ws.p;
   RefineArgs a{};
   a.L = L; a.N = N; a.k = k; a.D = D;
   a.group = dmax <= 64 ? 16 : 64;
@@ -5687,19 +5690,10 @@ int iwae_encode(iwae_handle* h, const float* x, int N, int k, int chunk, const f
   CHK(kernel_status(h));
   const int L = h->L;
   if (!x) return fail(h, IWAE_EINVAL, "x is NULL");
-  auto ptrs_ok = [&](const float* const* a, int n, const char* what) {
-    if (n == 0) return IWAE_OK;
-    if (n != L || !a)
-      return fail(h, IWAE_EINVAL, std::string("expected ") + std::to_string(L) + " " + what + " buffers (one per "
-                                  "stochastic layer), got " + std::to_string(n));
-    for (int i = 0; i < L; ++i)
-      if (!a[i]) return fail(h, IWAE_EINVAL, std::string("NULL ") + what + " buffer");
-    return IWAE_OK;
-  };
-  CHK(ptrs_ok(eps, n_eps, "eps"));
-  CHK(ptrs_ok(lat_out, n_lat, "latent"));
+  CHK(ptrs_ok(h, eps, n_eps, "eps", true));
+  CHK(ptrs_ok(h, lat_out, n_lat, "latent", true));
   if (n_lat == 0 && !log_q && !loc_top && !scale_top) return fail(h, IWAE_EINVAL, "every output is NULL");
-  const int imgs = score_chunk(h, N, k, chunk);
+  const int imgs = chunk_images(h, N, k, chunk);
   if (!imgs) return IWAE_EINVAL;
   const bool injected = n_eps > 0;
   const int rows = imgs * k;
@@ -5707,38 +5701,17 @@ int iwae_encode(iwae_handle* h, const float* x, int N, int k, int chunk, const f
   if (h->x3) CHK(ensure_wsplit(h));
   // a chunk's [k][n][d] noise, contiguous, in iwae_posterior's workspace
   const bool gather = injected && imgs < N;
-  size_t off = 0, o_eps[IWAE_MAX_LAYERS] = {};
-  for (int i = 0; i < L; ++i) {
-    o_eps[i] = off;
-    off += gather ? ((size_t)rows * h->enc[i].d + 63) & ~size_t(63) : 0;
-  }
-  if (off * sizeof(float) > h->post_ws_bytes) {
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->post_ws) (void)hipFree(h->post_ws);
-    h->post_ws = nullptr;
-    h->post_ws_bytes = 0;
-    HIPCHK(hipMalloc(&h->post_ws, off * sizeof(float)));
-    h->post_ws_bytes = off * sizeof(float);
-  }
-  float* ws = reinterpret_cast<float*>(h->post_ws);
-  const size_t wbytes = (size_t)h->xdim * sizeof(float);
-  for (int i0 = 0; i0 < N; i0 += imgs) {
-    const int n = std::min(imgs, N - i0);
-    HIPCHK(hipMemcpy2DAsync(h->x_in.p, (size_t)h->x_in.ld * sizeof(float), x + (size_t)i0 * h->xdim, wbytes, wbytes, n,
-                            hipMemcpyDeviceToDevice, h->stream));
+  WsLayout lay;
+  size_t o_eps[IWAE_MAX_LAYERS] = {};
+  for (int i = 0; i < L; ++i) o_eps[i] = lay.take(gather ? (size_t)rows * h->enc[i].d : 0);
+  CHK(h->post_ws.reserve(h, lay.floats));
+  for (ChunkWalk W(h, N, k, imgs, false, x, nullptr, false); W.i0 < N; W.i0 += imgs) {
+    CHK(walk_step(h, W));
+    const int i0 = W.i0, n = W.n;
     Plan P;
     P.B = n; P.Bimg = n; P.Bsplit = n; P.kS = k;
     EpsSet E;
-    std::memset(&E, 0, sizeof(E));
-    for (int i = 0; injected && i < L; ++i) {
-      E.a[i] = eps[i];
-      if (gather) {                              // sample s of the chunk's images: n * d floats at (s * N + i0) * d
-        const size_t rb = (size_t)n * h->enc[i].d * sizeof(float);
-        HIPCHK(hipMemcpy2DAsync(ws + o_eps[i], rb, eps[i] + (size_t)i0 * h->enc[i].d,
-                                (size_t)N * h->enc[i].d * sizeof(float), rb, k, hipMemcpyDeviceToDevice, h->stream));
-        E.a[i] = ws + o_eps[i];
-      }
-    }
+    CHK(chunk_eps(h, W, injected ? eps : nullptr, gather, h->post_ws.p, o_eps, E));
     CHK(encoder_fwd(h, P, E, false));
     ScRelayout G{};
     G.n = n; G.k = k; G.N = N; G.i0 = i0; G.gather = 0;
@@ -5858,11 +5831,7 @@ static int ws_sleep_forward(iwae_handle* h, const Plan& P, int n, bool fusedp) {
       continue;
     }
     if (i > 0) CHK(stoch_fwd(h, S, rows_from(h->h[i - 1], M), n, b));
-    GaussArgs g{};
-    g.P = b.P.p; g.ldP = b.P.ld; g.prow_div = 1; g.d = S.d;
-    g.H = tgt.p; g.ldH = tgt.ld;
-    g.out = h->logq + M; g.accumulate = i > 0; g.M = n;
-    HIPCHK(launch_gauss_fwd(h->stream, 1, g));
+    CHK(gauss_logdens(h, b.P, 1, S.d, tgt, h->logq + M, i > 0, n));
   }
   return IWAE_OK;
 }
@@ -5976,13 +5945,7 @@ static int do_wake_sleep(iwae_handle* h, const iwae_ws_config* cfg, const float*
   if (own) {
     size_t need = (size_t)n * ldp;
     for (int i = 0; i < L; ++i) need += ((size_t)n * h->enc[i].d + 3) & ~size_t(3);
-    if (need > h->ws_ws_floats) {
-      HIPCHK(hipStreamSynchronize(h->stream));
-      if (h->ws_ws) (void)hipFree(h->ws_ws);
-      h->ws_ws = nullptr; h->ws_ws_floats = 0;
-      HIPCHK(hipMalloc(&h->ws_ws, need * sizeof(float)));
-      h->ws_ws_floats = need;
-    }
+    CHK(h->ws_ws.reserve(h, need));
   }
   const bool direct = fusedp && smallm_ok(h, P.Bimg);
   if (!direct) CHK(copy_x(h, P, x));
@@ -6013,7 +5976,7 @@ static int do_wake_sleep(iwae_handle* h, const iwae_ws_config* cfg, const float*
       // step's precision rules), its layer-wise launches on the rows behind the
       // wake rows: the wake latents are the encoder fit's data
       float* hl[IWAE_MAX_LAYERS] = {};
-      float* p = h->ws_ws + (size_t)n * ldp;
+      float* p = h->ws_ws.p + (size_t)n * ldp;
       for (int i = 0; i < L; ++i) {
         hl[i] = p;
         p += ((size_t)n * h->enc[i].d + 3) & ~size_t(3);
@@ -6025,11 +5988,11 @@ static int do_wake_sleep(iwae_handle* h, const iwae_ws_config* cfg, const float*
         for (LayerBufs& b : h->db) { sh.mat(b.y1, M); sh.mat(b.y2, M); sh.mat(b.P, M); }
         sh.mat(h->ob.y1, M); sh.mat(h->ob.y2, M);
         sh.vec(h->logp, M);
-        CHK(iwae_generate(h, n, nullptr, nullptr, 0, nullptr, nullptr, 0, h->ws_ws, ldp, hl, L));
+        CHK(iwae_generate(h, n, nullptr, nullptr, 0, nullptr, nullptr, 0, h->ws_ws.p, ldp, hl, L));
       }
       h->count.ws_dream++;
       h->step.in_train_step = true;
-      dx = h->ws_ws; ld_dx = ldp;
+      dx = h->ws_ws.p; ld_dx = ldp;
       for (int i = 0; i < L; ++i) dl[i] = hl[i];
     }
     WsStageArgs sa{};

@@ -76,8 +76,8 @@ def test_knob_ids_match_header():
     with the same ids (names lower-cased), in both directions."""
     src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
     header = dict((m.group(1).lower(), int(m.group(2))) for m in re.finditer(r"\bIWAE_KNOB_([A-Z_0-9]+)\s*=\s*(\d+)", src))
-    assert len(header) == 36
-    assert sorted(header.values()) == list(range(1, 10)) + list(range(11, 36)) + [41, 42]
+    assert len(header) == 37
+    assert sorted(header.values()) == list(range(1, 10)) + list(range(11, 36)) + [41, 42, 43]
     for name, kid in header.items():
         assert _lib.KNOBS.get(name) == kid, name
     for name, kid in _lib.KNOBS.items():

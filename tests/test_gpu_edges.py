@@ -189,6 +189,38 @@ def test_nll_k5000_ring_chunks_straddling_workgroups_match_oracle():
     assert np.max(np.abs(lp - lp_one)) <= 1e-3, (lp, lp_one)
 
 
+@pytest.mark.parametrize("k", [5, 128])
+def test_nll_first_layer_groups_of_four_and_three_images(k):
+    """The fused NLL's first encoder layer runs once per group of images
+    (set_tuning("nll_group")): 7 images in chunks of 2 with groups of 4 give the
+    groups [0, 4) and [4, 7), the third chunk starting a group in the middle of
+    the call and the last chunk holding one image.  k = 5 runs mega_fwd_kernel,
+    k = 128 nring_kernel (counters).  The oracle's noise injected: within 0.05
+    nats of the float64 oracle, and bit for bit the same call with the default
+    group size (one group: the chunks and their noise are the same, only the
+    first layer's rows come from a launch over 4 or 3 images instead of 7)."""
+    O, spec, params, x, eps = _oracle_case(ARCH2, 7, k, 7000 + k)
+    from iwae_replication_project_amd.flexible_iwae import _split, weight_shapes
+    x32, e32 = x.astype(np.float32), [e.astype(np.float32) for e in eps]
+    ref = O.log_px_per_image(params, spec, x, k, eps=eps, chunk=1000)
+    assert np.isfinite(ref).all()
+    m = _model(ARCH2, "IWAE", 5)
+    m.set_weights(_split(O.flatten_params(spec, params).astype(np.float32), weight_shapes(m.dense)))
+    m.set_tuning("nll_imgs", 2)
+    m.set_tuning("nll_group", 4)                      # the model's first call: no earlier call's rows in the workspace
+    ids = (0, 1, 3)                                   # fused launches, those on injected noise, ring launches
+    c0 = [m._lib.iwae_debug_count(m._h, i) for i in ids]
+    lp = m.log_px(x32, k, eps=e32).cpu().numpy()
+    d = [m._lib.iwae_debug_count(m._h, i) - c for i, c in zip(ids, c0)]
+    assert d == [4, 4, 4 if k >= 128 else 0], d       # chunks [0,2) [2,4) | [4,6) [6,7)
+    m.set_tuning("nll_group", 16384)
+    lp_one_group = m.log_px(x32, k, eps=e32).cpu().numpy()
+    print(f"k {k}: max |lp - ref| {np.max(np.abs(lp - ref)):.2e}, against one group {np.max(np.abs(lp - lp_one_group)):.2e}")
+    assert lp.shape == (7,)
+    assert np.max(np.abs(lp - ref)) <= 0.05, (lp, ref)
+    np.testing.assert_array_equal(lp, lp_one_group)
+
+
 @pytest.mark.parametrize("big", [60, 100, 512])
 def test_alternating_split_and_single_split_output_jobs_leave_no_stale_rows(big):
     """the engine's forward splits the 784-wide Bernoulli layer over

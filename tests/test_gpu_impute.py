@@ -35,6 +35,7 @@ import functools
 import numpy as np
 import pytest
 
+import group_cases as GC
 import impute_ref as I
 import posterior_ref as R
 import test_gpu_posterior as TP
@@ -310,6 +311,31 @@ def test_three_chunks_the_last_ragged(ai, path):
         for a, b, sc in zip(parts["h_mean"], whole["h_mean"], hm_abs):
             assert (np.abs(_np(a) - _np(b)) <= _bar(LATENT_TOL, sc)).all()
         assert (np.abs(_np(parts["x_mean"]) - _np(whole["x_mean"])) <= _bar(PROBS_TOL, p_abs)).all()
+
+
+def test_first_layer_groups_of_four_and_three_images():
+    """Fused, the first encoder layer runs once per group of images
+    (set_tuning("nll_group")), and so does the staging of x and of the
+    likelihood's -1 copy: 7 images in chunks of 2 with groups of 4 give the
+    groups [0, 4) and [4, 7), the third chunk starting a group in the middle of
+    the call and the last chunk holding one image (group_cases.py).  On a model
+    that has run nothing, so no earlier call's rows are in the workspaces: two
+    calls (_run) of four masked mega_fwd_kernel launches, none layer-wise;
+    checks 1-4 as every other case; and bit for bit the same call with the
+    default group size (one group: the chunks are the same, only the staged
+    rows and the first layer's come from launches over 4 or 3 images)."""
+    ai, N, k = 1, GC.N, GC.K
+    x, mask, eps, u_pix, ref = _case(ai, N, k)
+    m = _fresh(ai, "auto")
+    m.set_tuning("nll_group", GC.GROUP)
+    (out, u), d = GC.counter_deltas(m, (19, 20, 0, 3), lambda: _run(m, x, mask, eps, u_pix, k, np.random.default_rng(k + N),
+                                                                   chunk=GC.CHUNK))
+    assert d == [8, 0, 0, 0], d                                     # twice the chunks [0,2) [2,4) | [4,6) [6,7)
+    _check(out, x, mask, u, u_pix, ref, k, f"arch {ai} N {N} k {k} chunk 2 group 4")
+    m.set_tuning("nll_group", 16384)
+    one_group = m.impute(x, mask, k, eps=eps, u=u, u_pix=u_pix, chunk=GC.CHUNK, want=ALL)
+    for a, b in zip(TP._flatten(out), TP._flatten(one_group)):
+        np.testing.assert_array_equal(a, b)
 
 
 # ------------------------------------------------------------------------ 7

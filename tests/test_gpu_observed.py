@@ -22,6 +22,7 @@ import pytest
 
 from oracle import iwae_oracle as O
 import ais_ref as A
+import group_cases as GC
 import missing_ref as M
 import observed_ref as OB
 import refine_ref as RF
@@ -30,7 +31,7 @@ from test_gpu_ais import _compare as _compare_ais
 from test_gpu_generate import PROBS_TOL
 from test_gpu_parity import make_model, weights_from_flat
 from test_gpu_refine import ADAM, _compare as _compare_refine, _same as _same_refine
-from test_gpu_score import _f32, _model
+from test_gpu_score import _f32, _model, fresh_group_model
 
 pytestmark = pytest.mark.gpu
 
@@ -294,6 +295,36 @@ def test_chunks_do_not_change_a_bit(name, path):
         assert (c2[2] - c1[2]) + (c2[3] - c1[3]) == chunks and c2[:2] == c1[:2] and c2[4:] == c1[4:]
         _equal(out, whole, f"score chunk {chunk}")
         _equal(gout, gwhole, f"score_grad chunk {chunk}")
+
+
+def test_first_layer_groups_of_four_and_three_images():
+    """The masked entries under first-layer groups of 4 images, 7 images in
+    chunks of 2 (group_cases.py), each on a model that has run nothing: both
+    staged copies of x and the first layer's rows come from launches over 4 and
+    3 images.  Four masked score_kernel / sg_kernel launches and nothing else;
+    within the bars of the parity tests; bit for bit the calls with the default
+    group size."""
+    name = "O" + GC.GROUP_CASE
+    x, mask = _xm(name)
+    h = _f32(OB.latents(name, "off"))
+    ref, gref = OB.reference(name, "off"), OB.grad_reference(name, "off")
+    coef = (-1.0, 1.0, 1.0)
+    m = fresh_group_model()
+    out, one_group, d = GC.groups_then_one_group(m, IDS, lambda: m.score_observed(x, mask, h, want=ALL, chunk=GC.CHUNK))
+    assert d == [4] + [0] * (len(IDS) - 1), d             # chunks [0,2) [2,4) | [4,6) [6,7)
+    _check_terms(out, ref, f"[{name} off auto group 4]")
+    np.testing.assert_allclose(out["probs"].cpu().numpy(), ref["probs"], **PROBS_TOL)
+    _equal(out, one_group, "score, groups of 4")
+    m = fresh_group_model()
+    gout, gone_group, d = GC.groups_then_one_group(
+        m, IDS, lambda: m.score_grad_observed(x, mask, h, coef=coef, want=GALL, chunk=GC.CHUNK))
+    assert d == [0, 0, 4] + [0] * (len(IDS) - 3), d
+    tot, scale = G.combine(gref, coef)
+    errs = _layer_errors(_np(gout["grad"]), tot, scale)
+    print(f"[{name} off auto group 4] (-1, 1, 1): {max(errs):.2e} of sum |c_t| ||g_t||")
+    assert max(errs) <= BAR, errs
+    _check_terms(gout, ref, f"[{name} off auto group 4]")
+    _equal(gout, gone_group, "score_grad, groups of 4")
 
 
 # -------------------------------------------------------------- 7. path taken

@@ -35,6 +35,7 @@ import functools
 import numpy as np
 import pytest
 
+import group_cases as GC
 import posterior_ref as R
 from test_gpu_generate import ARCHS, LATENT_TOL, PROBS_TOL
 from test_gpu_parity import NLL_TOL, REL, make_model, weights_from_flat
@@ -304,7 +305,6 @@ def test_three_chunks_the_last_ragged(ai, path):
         np.testing.assert_allclose(_np(hd), hr, **LATENT_TOL)
 
 
-# ------------------------------------------------------------ 4. device noise
 def _fresh(ai, path):
     O, spec, params = _spec_params(ai)
     he, hd, le, ld = ARCHS[ai]
@@ -316,6 +316,47 @@ def _fresh(ai, path):
 def _flatten(out):
     return [_np(t) for name in sorted(out) for t in (out[name] if isinstance(out[name], list) else [out[name]])]
 
+
+def test_first_layer_groups_of_four_and_three_images():
+    """Fused, the first encoder layer runs once per group of images
+    (set_tuning("nll_group")): 7 images in chunks of 2 with groups of 4 give the
+    groups [0, 4) and [4, 7), the third chunk starting a group in the middle of
+    the call and the last chunk holding one image (group_cases.py).  On a model
+    that has run nothing, so no earlier call's rows are in the workspace: four
+    post_kernel launches, none layer-wise; parity as every other case; and bit
+    for bit the same call with the default group size (one group: the chunks
+    are the same, only the first layer's rows come from a launch over 4 or 3
+    images instead of 7)."""
+    ai, N, k = 1, GC.N, GC.K
+    x, eps, ref = _case(ai, N, k)
+    want = ("h_mean", "probs", "weights", "ess", "log_px")
+    m = _fresh(ai, "auto")
+    out, one_group, d = GC.groups_then_one_group(
+        m, (17, 18), lambda: m.posterior(x, k, eps=eps, chunk=GC.CHUNK, want=want))
+    assert d == [4, 0], d                                           # chunks [0,2) [2,4) | [4,6) [6,7)
+    _check_parity(out, ref, k, f"arch {ai} N {N} k {k} chunk 2 group 4")
+    for a, b in zip(_flatten(out), _flatten(one_group)):
+        np.testing.assert_array_equal(a, b)
+
+
+def test_log_px_of_a_few_images_then_their_posterior_on_a_fresh_model():
+    """The first evaluation call of a model sizes the workspace for its own
+    images (a first-layer group is at most the call's N images), and a later
+    call grows it: log_px of 4 images, then their posterior, both within the
+    bars, the posterior on post_kernel."""
+    ai, N, k = 1, 4, 5
+    x, eps, ref = _case(ai, N, k)
+    m = _fresh(ai, "auto")
+    lp = _np(m.log_px(x, k, eps=eps)).astype(np.float64)
+    assert np.abs(lp - ref["log_px"]).max() <= NLL_TOL, (lp, ref["log_px"])
+    c0 = _counts(m)
+    out = m.posterior(x, k, eps=eps, want=("h_mean", "probs", "weights", "ess", "log_px"))
+    c1 = _counts(m)
+    assert [c1[0] - c0[0], c1[1] - c0[1]] == [1, 0], (c0, c1)
+    _check_parity(out, ref, k, f"arch {ai} N {N} k {k} after log_px")
+
+
+# ------------------------------------------------------------ 4. device noise
 
 @pytest.mark.parametrize("path", PATHS)
 @pytest.mark.parametrize("ai,N,k", [(1, 5, 17), (2, 3, 130)])

@@ -30,6 +30,7 @@ import itertools
 import numpy as np
 import pytest
 
+import group_cases as GC
 import score_ref as R
 from test_gpu_generate import PROBS_TOL
 from test_gpu_parity import make_model, weights_from_flat
@@ -217,6 +218,29 @@ def test_chunks_do_not_change_a_bit(path):
         assert sum(_counts(m)[:2]) == sum(c0[:2]) + launches
         for n in whole:
             np.testing.assert_array_equal(out[n].cpu().numpy(), whole[n].cpu().numpy(), err_msg=f"chunk {chunk} {n}")
+
+
+def fresh_group_model():
+    """The group case's model with nothing run on it (group_cases.py says why)."""
+    return _model.__wrapped__(GC.GROUP_CASE, "auto")
+
+
+def test_first_layer_groups_of_four_and_three_images():
+    """7 images in chunks of 2 under first-layer groups of 4 (group_cases.py), on
+    a model that has run nothing: four score_kernel launches, none layer-wise;
+    every term and probs within the bars; bit for bit the same call with the
+    default group size (the chunks are the same, only the first layer's rows
+    come from a launch over 4 or 3 images instead of 7)."""
+    name = GC.GROUP_CASE
+    _, _, x, _ = R.case(name)
+    h, ref = _f32(R.latents(name, "off")), R.reference(name, "off")
+    m = fresh_group_model()
+    out, one_group, d = GC.groups_then_one_group(m, (23, 24), lambda: m.score(_f32(x), h, want=ALL, chunk=GC.CHUNK))
+    assert d == [4, 0], d                                 # chunks [0,2) [2,4) | [4,6) [6,7)
+    _check_terms(out, ref, "[G7 off auto group 4]")
+    np.testing.assert_allclose(out["probs"].cpu().numpy(), ref["probs"], **PROBS_TOL)
+    for n in one_group:
+        np.testing.assert_array_equal(out[n].cpu().numpy(), one_group[n].cpu().numpy(), err_msg=n)
 
 
 # --------------------------------------------------------- 7. row independence

@@ -19,10 +19,11 @@ import ctypes
 import numpy as np
 import pytest
 
+import group_cases as GC
 import score_ref as R
 import scoregrad_ref as G
 from test_gpu_parity import make_model
-from test_gpu_score import _check_terms, _f32, _model
+from test_gpu_score import _check_terms, _f32, _model, fresh_group_model
 
 pytestmark = pytest.mark.gpu
 
@@ -182,6 +183,31 @@ def test_chunks_do_not_change_a_bit(path):
             np.testing.assert_array_equal(u, v, err_msg=f"chunk {chunk} grad")
         for n in want[1:]:
             np.testing.assert_array_equal(out[n].cpu().numpy(), whole[n].cpu().numpy(), err_msg=f"chunk {chunk} {n}")
+
+
+def test_first_layer_groups_of_four_and_three_images():
+    """7 images in chunks of 2 under first-layer groups of 4 (group_cases.py), on
+    a model that has run nothing: four sg_kernel launches, none layer-wise, none
+    of iwae_score's; the gradient of log w and the three values within the bars;
+    bit for bit the same call with the default group size."""
+    name = GC.GROUP_CASE
+    _, _, x, _ = R.case(name)
+    h = _f32(R.latents(name, "off"))
+    ref, vref = G.reference(name, "off"), R.reference(name, "off")
+    m = fresh_group_model()
+    want, coef = ("grad", "log_q", "log_ph", "log_px"), (-1.0, 1.0, 1.0)
+    out, one_group, d = GC.groups_then_one_group(
+        m, (25, 26, 23, 24, 3), lambda: m.score_grad(_f32(x), h, coef=coef, want=want, chunk=GC.CHUNK))
+    assert d == [4, 0, 0, 0, 0], d                        # chunks [0,2) [2,4) | [4,6) [6,7)
+    tot, scale = G.combine(ref, coef)
+    errs = _layer_errors(_np(out["grad"]), tot, scale)
+    print(f"[G7 off auto group 4] (-1, 1, 1): {max(errs):.2e} of sum |c_t| ||g_t||")
+    assert max(errs) <= BAR, errs
+    _check_terms(out, vref, "[G7 off auto group 4]")
+    for u, v in zip(_np(out["grad"]), _np(one_group["grad"])):
+        np.testing.assert_array_equal(u, v, err_msg="grad")
+    for n in want[1:]:
+        np.testing.assert_array_equal(out[n].cpu().numpy(), one_group[n].cpu().numpy(), err_msg=n)
 
 
 # --------------------------------------------------------- 5. row independence

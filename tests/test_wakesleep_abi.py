@@ -97,7 +97,7 @@ def test_no_new_loss_id_or_knob():
     from iwae_replication_project_amd import _lib
     assert _lib.LOSS_IDS == {"VAE": 0, "IWAE": 1, "VAE_V1": 2, "L_alpha": 3, "L_power_p": 4, "L_median": 5, "CIWAE": 6,
                              "MIWAE": 7, "PIWAE": 8, "IWAE_STL": 9, "IWAE_DREG": 10}
-    assert len(_lib.KNOBS) == 36 and sorted(_lib.KNOBS.values()) == list(range(1, 10)) + list(range(11, 36)) + [41, 42]
+    assert len(_lib.KNOBS) == 37 and sorted(_lib.KNOBS.values()) == list(range(1, 10)) + list(range(11, 36)) + [41, 42, 43]
     src = open(HEADER).read()
     assert not re.search(r"IWAE_(KNOB|LOSS)_\w*(WAKE|SLEEP|RWS|DREAM)", src)
     m = re.search(r"typedef\s+struct\s+iwae_loss_config\s*\{(.*?)\}", _code(), flags=re.S)
