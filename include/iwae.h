@@ -918,6 +918,79 @@ int iwae_encode(iwae_handle* h, const float* x, int N, int k, int chunk,
                 const float* const* eps, int n_eps,
                 float* const* lat_out, int n_lat, float* log_q,
                 float* loc_top, float* scale_top);
+/* The aggregate posterior q(h_1) = 1/M sum_m q(h_1 | x_m) (Hoffman & Johnson
+ * 2016) at R query latents lat1 [R][d_1] [dev].  Only the first stochastic
+ * layer is pairwise: q(h_1..h_L) = q(h_1) prod_i q(h_{i+1} | h_i), so this one
+ * entry serves every depth; the other terms are iwae_encode's and iwae_score's.
+ * Reference components (mu_m, s_m), m < M:
+ *  - x_ref [M][x_dim] [dev] given: the first encoder layer's parameters of
+ *    image m, s = exp(zs) + 1e-6, from the layer-0 launches the layer-wise
+ *    encoder makes on image rows (l1, l2, head); nothing is sampled, no later
+ *    layer and no decoder work runs.  The walk is the evaluation entries' chunk
+ *    walker with k = 1 and chunk images per pass (0: automatic).  loc / scale
+ *    [M][d_1] [dev], if non-NULL, receive the parameters; for L = 1 they are the
+ *    bits iwae_encode returns as loc_top / scale_top for the same x, path and
+ *    precision.
+ *  - x_ref NULL: loc and scale are required inputs (the aggregate of any
+ *    diagonal-Gaussian family, e.g. iwae_refine's q* with scale =
+ *    exp(logstd)); chunk is ignored.  A scale <= 0 or not finite gives
+ *    non-finite results for the rows it touches; it is not checked on the host.
+ * Float32, in difference form (never h^2 a - 2 h b + c, which cancels at the
+ * small scales of a trained encoder):
+ *   t(r,m,j) = -1/2 z^2 - log s_mj - 1/2 log 2 pi,  z = (h_rj - mu_mj) (1 / s_mj)
+ *   J(r,m)   = sum_j t(r,m,j), in column order
+ *   log_q_agg[r]    = logsumexp_m J(r,m) - log M            [R]
+ *   log_q_dim[r][j] = logsumexp_m t(r,m,j) - log M          [R][d_1]
+ * and with own_period = P > 0 row r's own image is o = r mod P (sample-major
+ * [k][N][d_1] latents with x_ref = x: P = N):
+ *   log_q_own[r] = J(r,o) [R],  log_q_own_dim[r][j] = t(r,o,j) [R][d_1];
+ * P = 0: the two own outputs must be NULL.  Every output is optional, not all
+ * of them NULL.  1 / s and log s are formed once per call by a prep launch
+ * into [M][d_1] workspace.  Launches: agg_joint_kernel for log_q_agg,
+ * agg_dim_kernel (the expensive one: one exp per (r, m, j)) only for
+ * log_q_dim, one own-term launch.  When the query rows are too few to fill the
+ * device the references are split into segments: with W the workgroups one
+ * pass over all references takes (ceil(R / 64) joint; ceil(ceil(R / 4)
+ * min(d_1, 256) / 256) ceil(d_1 / 256) per unit) and T the references per tile
+ * (64 joint; min(128, 4096 / min(d_1, 256)) per unit), W >= 1024 gives one
+ * segment, else ceil(1024 / W) segments, at most 1024 and at most one per
+ * tile, of equal length rounded up to whole tiles; each writes (max, sum)
+ * partials and a merge launch combines them in segment order, M* = max m, S =
+ * sum s exp(m - M*) (iwae_nll_partials' rule).  The partial workspace is
+ * bounded by the rule itself, so R needs no slicing: a split call has W < 1024
+ * workgroups of at most 64 rows (joint) or 1024 (row, unit) pairs (per unit)
+ * and fewer than 1024 / W + 1 segments, so its partials (2 segments floats per
+ * row joint, 2 segments d_1 per row per unit) stay below 2^18 floats (1 MiB)
+ * and 2^22 floats (16 MiB); an unsplit call writes none.  The split is a
+ * function of (R, M, d_1) alone, so two calls with different R need not agree
+ * to the last bit; one call is deterministic run to run and its result does
+ * not depend on chunk, bit for bit.  No float atomics, every output element
+ * has one writer, every reduction a fixed order.  Rows are independent: a
+ * non-finite latent poisons its own row only.  A float4 path serves d_1 % 4 ==
+ * 0 with 16-byte aligned lat1 and loc, a scalar path with the same bits
+ * everything else, down to d_1 = 1.
+ * Everything is enqueued on the handle's stream with no host synchronisation
+ * unless a workspace has to grow.  Nothing is drawn and the noise position
+ * stays; weights, Adam state, captured graphs and engine plans are untouched
+ * (as for iwae_encode, an x_ref call whose chunk outgrows the handle's
+ * activation workspace regrows it, and the next train step re-captures; its
+ * result is the same).
+ * IWAE_EINVAL, nothing launched (after the sticky iwae_status error, returned
+ * first): every output NULL; lat1 NULL; R < 1 or R > 2^30; M < 1 or M > 2^24;
+ * x_ref NULL with loc or scale NULL; P < 0 or P > M; P = 0 with an own output
+ * asked for.
+ * Out of scope: pixel masks (an x_ref with a mask), sharding M over GPUs, and
+ * minibatch-weighted / stratified estimators for an x_ref that subsamples a
+ * larger data set. */
+int iwae_aggregate(iwae_handle* h,
+                   const float* x_ref, int M, int chunk,
+                   float* loc, float* scale,
+                   const float* lat1, long long R,
+                   int own_period,
+                   float* log_q_agg,
+                   float* log_q_dim,
+                   float* log_q_own,
+                   float* log_q_own_dim);
 /* get_NLL_without_inactive_units (F:466-F:494): like iwae_nll / iwae_nll_eps
  * with every sampled h_i multiplied by masks[i] ([dev], d_i floats of 0/1). */
 int iwae_nll_masked(iwae_handle* h, const float* x, int N, int k, const float* const* eps,
@@ -1045,8 +1118,10 @@ double iwae_workspace_bytes(const iwae_handle* h);
  * enqueued work, 36 GM_FIT jobs issued on rb_bwd_kernel (one per encoder
  * layer of a row-block call), 37 GM_FIT launches of gauss_bwd_enc_kernel (one
  * per encoder layer of a layer-wise call), 38 dream generations the step ran
- * itself (also counted under 10 where gen_kernel ran them); -1 for an unknown
- * id. */
+ * itself (also counted under 10 where gen_kernel ran them); iwae_aggregate: 39
+ * calls that enqueued work, 40 agg_joint_kernel launches (one per call that
+ * asks for log_q_agg), 41 agg_dim_kernel launches (one per call that asks for
+ * log_q_dim); -1 for an unknown id. */
 long long iwae_debug_count(const iwae_handle* h, int what);
 /* Live kernel timing: bracket every launch of one kernel class with HIP events
  * on the handle's stream -- a GEMM class (kind: 0 forward, 1 backward-data,

@@ -135,6 +135,7 @@ SIGNATURES = {
     "iwae_refine_masked": (c_int, [H, FP, FP, c_int, c_int, c_int, FPP, FPP, c_int, POINTER(IwaeRefineConfig), FPP, c_int,
                                    FPP, c_int, FP, FPP, c_int, FP, FP, FP]),
     "iwae_encode": (c_int, [H, FP, c_int, c_int, c_int, FPP, c_int, FPP, c_int, FP, FP, FP]),
+    "iwae_aggregate": (c_int, [H, FP, c_int, c_int, FP, FP, FP, c_longlong, c_int, FP, FP, FP, FP]),
     "iwae_train_step_masked": (c_int, [H, POINTER(IwaeLossConfig), FP, FP, c_int, FPP, c_int, FP]),
     "iwae_forward_backward_masked": (c_int, [H, POINTER(IwaeLossConfig), FP, FP, c_int, FPP, c_int, FP]),
     "iwae_bound_masked": (c_int, [H, POINTER(IwaeLossConfig), FP, FP, c_int, FPP, c_int, FP]),

@@ -1192,4 +1192,60 @@ hipError_t launch_refine_step(hipStream_t st, const RefineArgs& a);
 hipError_t launch_refine_end(hipStream_t st, const RefineArgs& a);
 hipError_t launch_refine_finish(hipStream_t st, const RefineArgs& a);
 
+// ----------------------------------------------- aggregate posterior ----
+// iwae_aggregate's kernels (iwae_aggregate.hip).  R query
+// rows lat [R][d] against M reference components given as mu, rs = 1 / s and
+// lc = -(log s + 1/2 log 2 pi), [M][d] each (launch_agg_prep forms the last two
+// from the scales).  The references are walked in nseg segments of seg_len
+// (the last one shorter); nseg == 1 writes out = logsumexp - log_m directly,
+// else each segment writes its (max, sum) to part ([R][nseg][2] joint,
+// [R][d][nseg][2] per unit) and launch_agg_merge combines them in segment
+// order.  vec: d % 4 == 0 and lat, mu, rs, lc 16-byte aligned (float4 loads;
+// the scalar path gives the same bits).
+constexpr int kAggJointRows = 64;    // query rows per workgroup of agg_joint_kernel
+constexpr int kAggJointRefs = 64;    // references per tile
+constexpr int kAggJointCols = 32;    // most columns per LDS pass
+constexpr int kAggDimTile = 4096;    // agg_dim_kernel: floats per LDS array (references per tile x units per chunk)
+constexpr int kAggDimUnits = 256;    // ... most units per chunk
+constexpr int kAggWgs = 1024;        // workgroups below which the references are split
+constexpr int kAggMaxSeg = 1024;     // most segments
+struct AggArgs {
+  const float* lat; long long R;
+  const float *mu, *rs, *lc;
+  int M, d, vec;
+  int seg_len, nseg;
+  int uw, tm;                        // agg_dim_kernel: units per chunk, references per tile (uw tm <= kAggDimTile)
+  float log_m;
+  float* out;
+  float* part;
+};
+// The split rule: wgs workgroups would walk all M references in tiles of
+// `tile`.  At kAggWgs or more: one segment.  Below: ceil(kAggWgs / wgs)
+// segments, at most kAggMaxSeg and at most one per tile, of equal length
+// rounded up to whole tiles.  A function of (R, M, d) alone.  A split launch
+// has wgs < kAggWgs workgroups of at most 64 rows (joint) or 1024 (row, unit)
+// pairs (per unit) and fewer than kAggWgs / wgs + 1 segments, so its partials
+// stay below 2 * 64 * 2 kAggWgs = 2^18 and 2 * 1024 * 2 kAggWgs = 2^22 floats.
+inline void agg_split(long long wgs, int M, int tile, int& seg_len, int& nseg) {
+  long long n = wgs >= kAggWgs ? 1 : (kAggWgs + wgs - 1) / wgs;
+  const long long tiles = ((long long)M + tile - 1) / tile;
+  if (n > tiles) n = tiles;
+  if (n > kAggMaxSeg) n = kAggMaxSeg;
+  const long long per = (tiles + n - 1) / n;
+  seg_len = (int)(per * tile);
+  nseg = (int)((tiles + per - 1) / per);
+}
+inline int agg_dim_units(int d) { return d < kAggDimUnits ? d : kAggDimUnits; }
+inline int agg_dim_refs(int d) { const int t = kAggDimTile / agg_dim_units(d); return t < 128 ? t : 128; }
+inline long long agg_joint_wgs(long long R) { return (R + kAggJointRows - 1) / kAggJointRows; }
+inline long long agg_dim_wgs(long long R, int d) {
+  const int uw = agg_dim_units(d);
+  return (((R + 3) / 4) * uw + 255) / 256 * ((d + uw - 1) / uw);
+}
+hipError_t launch_agg_prep(hipStream_t st, const float* scale, long long n, float* rs, float* lc);
+hipError_t launch_agg_joint(hipStream_t st, const AggArgs& a);
+hipError_t launch_agg_dim(hipStream_t st, const AggArgs& a);
+hipError_t launch_agg_merge(hipStream_t st, const float* part, long long n, int nseg, float log_m, float* out);
+hipError_t launch_agg_own(hipStream_t st, const AggArgs& a, int period, float* own, float* own_dim);
+
 }  // namespace iwae

@@ -225,6 +225,8 @@ struct Counters {
   long long ws = 0;                      // 35: wake-sleep calls that enqueued work
   long long ws_rb = 0, ws_gauss = 0;     // 36, 37: GM_FIT jobs issued on rb_bwd_kernel / GM_FIT launches of gauss_bwd_enc_kernel
   long long ws_dream = 0;                // 38: dream generations a wake-sleep step ran itself
+  long long agg = 0;                     // 39: iwae_aggregate calls that enqueued work
+  long long agg_joint = 0, agg_dim = 0;  // 40, 41: agg_joint_kernel / agg_dim_kernel launches
 };
 
 // row-chain train engine plan (device resident, per shape; iwae_train.hip)
@@ -341,6 +343,8 @@ struct iwae_handle {
                                      // the weights, and the Adam moments the caller did not give)
   GrowWs ws_ws;                      // iwae_wake_sleep_step's own dreams (pixels [n][r4(x_dim)], then h_1 .. h_L
                                      // [n][d_i]) and its three values when the caller wants none
+  GrowWs agg_ws;                     // iwae_aggregate's reference components ([M][d_1]: 1 / s and the log term, and
+                                     // mu / s where the caller takes none) and its split partials
   float* loss_slots = nullptr;       // multi-step graphs: step j's loss (kGraphSteps floats), then
                                      // [kGraphSteps, 2 kGraphSteps): where a graph's copy node writes
                                      // when the call wants no losses
@@ -3604,7 +3608,7 @@ void iwae_destroy(iwae_handle* h) {
   if (h->tcu_ctr) (void)hipFree(h->tcu_ctr);
   if (h->err_host) (void)hipHostFree(h->err_host);
   if (h->loss_slots) (void)hipFree(h->loss_slots);
-  for (GrowWs* w : {&h->post_ws, &h->sg_ws, &h->ais_ws, &h->refine_ws, &h->ws_ws})
+  for (GrowWs* w : {&h->post_ws, &h->sg_ws, &h->ais_ws, &h->refine_ws, &h->ws_ws, &h->agg_ws})
     if (w->p) (void)hipFree(w->p);
   if (h->nr_units) (void)hipFree(h->nr_units);
   if (h->nrb_units) (void)hipFree(h->nrb_units);
@@ -5730,6 +5734,85 @@ int iwae_encode(iwae_handle* h, const float* x, int N, int k, int chunk, const f
   return IWAE_OK;
 }
 
+// The aggregate posterior q(h_1) = 1/M sum_m q(h_1 | x_m) at R query latents
+// (DESIGN.md 3.4.12).  The reference components are the first encoder layer's
+// (mu, s) of x_ref -- walk_step's layer-0 launches on image rows, k = 1, no
+// sampling, no later layer -- or the caller's; one prep launch forms 1 / s and
+// the log term, then the joint and per-unit kernels run over the query rows.
+int iwae_aggregate(iwae_handle* h, const float* x_ref, int M, int chunk, float* loc, float* scale, const float* lat1,
+                   long long R, int own_period, float* log_q_agg, float* log_q_dim, float* log_q_own,
+                   float* log_q_own_dim) {
+  if (!h) return IWAE_EINVAL;
+  CHK(kernel_status(h));
+  if (!log_q_agg && !log_q_dim && !log_q_own && !log_q_own_dim) return fail(h, IWAE_EINVAL, "every output is NULL");
+  if (!lat1) return fail(h, IWAE_EINVAL, "lat1 is NULL");
+  if (R < 1 || R > (1LL << 30)) return fail(h, IWAE_EINVAL, "R must be in [1, 2^30]");
+  if (M < 1 || M > (1 << 24)) return fail(h, IWAE_EINVAL, "M must be in [1, 2^24]");
+  if (!x_ref && (!loc || !scale)) return fail(h, IWAE_EINVAL, "without x_ref both loc and scale are required");
+  if (own_period < 0 || own_period > M) return fail(h, IWAE_EINVAL, "own_period must be in [0, M]");
+  if (own_period == 0 && (log_q_own || log_q_own_dim))
+    return fail(h, IWAE_EINVAL, "log_q_own / log_q_own_dim need own_period > 0");
+  const int d = h->enc[0].d;
+  int imgs = 0;
+  if (x_ref) {
+    imgs = chunk_images(h, M, 1, chunk);
+    if (!imgs) return IWAE_EINVAL;
+  }
+  // the split of the references, from (R, M, d) alone
+  AggArgs J{}, D{};
+  J.M = D.M = M; J.d = D.d = d;
+  J.log_m = D.log_m = logf((float)M);
+  J.lat = D.lat = lat1; J.R = D.R = R;
+  agg_split(agg_joint_wgs(R), M, kAggJointRefs, J.seg_len, J.nseg);
+  D.uw = agg_dim_units(d); D.tm = agg_dim_refs(d);
+  agg_split(agg_dim_wgs(R, d), M, D.tm, D.seg_len, D.nseg);
+  const size_t md = (size_t)M * d;
+  WsLayout lay;
+  const size_t o_rs = lay.take(md), o_lc = lay.take(md);
+  const size_t o_mu = lay.take(x_ref && !loc ? md : 0), o_sc = lay.take(x_ref && !scale ? md : 0);
+  // split partials: a split call has fewer than kAggWgs workgroups of at most 64 rows / 1024 (row, unit)
+  // pairs, so these stay below 2^18 and 2^22 floats (agg_split)
+  const size_t o_pj = lay.take(log_q_agg && J.nseg > 1 ? (size_t)R * J.nseg * 2 : 0);
+  const size_t o_pd = lay.take(log_q_dim && D.nseg > 1 ? (size_t)R * d * D.nseg * 2 : 0);
+  if (x_ref) {
+    CHK(ensure_capacity(h, imgs, imgs, false));
+    if (h->x3) CHK(ensure_wsplit(h));
+  }
+  CHK(h->agg_ws.reserve(h, lay.floats));
+  float* ws = h->agg_ws.p;
+  float* mu = loc ? loc : ws + o_mu;
+  float* sc = scale ? scale : ws + o_sc;
+  if (x_ref) {
+    for (ChunkWalk W(h, M, 1, imgs, false, x_ref, nullptr, true); W.i0 < M; W.i0 += imgs) {
+      CHK(walk_step(h, W));
+      const Mat& P0 = h->eb[0].P;
+      ScRelayout G{};
+      G.n = W.n; G.k = 1; G.N = M; G.i0 = W.i0; G.gather = 0;
+      G.seg[G.nseg++] = ScSeg{P0.p, P0.ld, 0, d, mu, 0, 1};
+      G.seg[G.nseg++] = ScSeg{P0.p, P0.ld, d, d, sc, 1, 1};
+      HIPCHK(launch_score_relayout(h->stream, G));
+    }
+  }
+  HIPCHK(launch_agg_prep(h->stream, sc, (long long)md, ws + o_rs, ws + o_lc));
+  J.mu = D.mu = mu; J.rs = D.rs = ws + o_rs; J.lc = D.lc = ws + o_lc;
+  J.vec = D.vec = (d % 4 == 0 && (((uintptr_t)lat1 | (uintptr_t)mu) & 15) == 0) ? 1 : 0;
+  if (log_q_agg) {
+    J.part = ws + o_pj; J.out = log_q_agg;
+    HIPCHK(launch_agg_joint(h->stream, J));
+    ++h->count.agg_joint;
+    if (J.nseg > 1) HIPCHK(launch_agg_merge(h->stream, J.part, R, J.nseg, J.log_m, J.out));
+  }
+  if (log_q_dim) {
+    D.part = ws + o_pd; D.out = log_q_dim;
+    HIPCHK(launch_agg_dim(h->stream, D));
+    ++h->count.agg_dim;
+    if (D.nseg > 1) HIPCHK(launch_agg_merge(h->stream, D.part, R * d, D.nseg, D.log_m, D.out));
+  }
+  if (log_q_own || log_q_own_dim) HIPCHK(launch_agg_own(h->stream, J, own_period, log_q_own, log_q_own_dim));
+  ++h->count.agg;
+  return IWAE_OK;
+}
+
 // get_NLL_without_inactive_units (F:466-F:494): k-sample log p(x) with every
 // sampled h_i multiplied by its 0/1 active-unit mask masks[i] ([dev], d_i).
 int iwae_nll_masked(iwae_handle* h, const float* x, int N, int k, const float* const* eps, int n_eps,
@@ -6086,6 +6169,9 @@ long long iwae_debug_count(const iwae_handle* h, int what) {
     case 36: return h->count.ws_rb;
     case 37: return h->count.ws_gauss;
     case 38: return h->count.ws_dream;
+    case 39: return h->count.agg;
+    case 40: return h->count.agg_joint;
+    case 41: return h->count.agg_dim;
     default: return -1;
   }
 }

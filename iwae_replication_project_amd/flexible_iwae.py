@@ -158,6 +158,51 @@ def ais_schedule(n_temps, kind="sigmoid", rad=4.0):
 
 
 # --------------------------------------------------------------- optimizer
+AGGREGATE_OUTPUTS = ("log_q_agg", "log_q_dim", "log_q_own", "log_q_own_dim", "loc", "scale")
+
+
+def check_aggregate_args(h1_shape, d1, have_x_ref, components, M, own_period, want):
+    """``log_q_aggregate``'s argument rules, on shapes alone: ``h1_shape`` [R, d1]
+    or [k, N, d1]; ``components``: the shapes of the loc / scale given (both, each
+    [M, d1], or neither); exactly one of x_ref and (loc, scale); 0 <= own_period
+    <= M, the own outputs only with own_period > 0.  Returns (R, want)."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    bad = [w for w in want if w not in AGGREGATE_OUTPUTS]
+    if bad or not [w for w in want if w not in ("loc", "scale")]:
+        raise ValueError(f"want must name some of {AGGREGATE_OUTPUTS[:4]} (and may add 'loc', 'scale'), got {want}")
+    if len(h1_shape) not in (2, 3) or h1_shape[-1] != d1:
+        raise ValueError(f"h1 must be [R, d1={d1}] or [k, N, d1={d1}], got {tuple(h1_shape)}")
+    R = int(np.prod(h1_shape[:-1]))
+    if R < 1:
+        raise ValueError("h1 has no rows")
+    if have_x_ref == bool(components):
+        raise ValueError("give exactly one of x_ref and (loc, scale)")
+    if not have_x_ref and (len(components) != 2 or any(tuple(c) != (M, d1) for c in components)):
+        raise ValueError(f"loc and scale must both be given, [M, d1={d1}] each, got {components}")
+    if M < 1:
+        raise ValueError("no reference components")
+    if own_period < 0 or own_period > M:
+        raise ValueError(f"own_period must be in [0, M={M}], got {own_period}")
+    if own_period == 0 and ("log_q_own" in want or "log_q_own_dim" in want):
+        raise ValueError("log_q_own / log_q_own_dim need own_period > 0")
+    return R, want
+
+
+def aggregate_split(R, M, d1):
+    """(segments of the joint kernel, segments of the per-unit kernel) into which
+    iwae_aggregate splits M references for R query rows of d1 units: the rule
+    include/iwae.h documents, restated."""
+    def split(wgs, tile):
+        n = 1 if wgs >= 1024 else -(-1024 // wgs)
+        tiles = -(-M // tile)
+        n = min(n, tiles, 1024)
+        per = -(-tiles // n)
+        return -(-tiles // per)
+    uw = min(d1, 256)
+    dim_wgs = -(-(-(-R // 4) * uw) // 256) * -(-d1 // uw)
+    return split(-(-R // 64), 64), split(dim_wgs, min(128, 4096 // uw))
+
+
 class Adam:
     """Keras ``tf.keras.optimizers.Adam`` knobs used by E:36-E:40 (defaults are
     Keras' own).  Setting ``learning_rate`` (E:76) updates every compiled model."""
@@ -1536,6 +1581,90 @@ class Flexible_Model:
             lq = lq.t().contiguous()
         self._stream.synchronize()
         return hs, lq, _Normal(loc, scale)
+
+    # ------------------------------------------------- aggregate posterior
+    def log_q_aggregate(self, h1, x_ref=None, loc=None, scale=None, own_period=0, want=("log_q_agg",), chunk=0):
+        """The aggregate posterior q(h_1) = 1/M sum_m q(h_1 | x_m) at the latents
+        ``h1`` ([R, d1] or [k, N, d1]; iwae_aggregate).  The M components are the
+        first encoder layer's Gaussians of ``x_ref`` [M, x_dim], or the caller's
+        ``loc`` / ``scale`` [M, d1] (exactly one of the two forms).  Returns a
+        dict of device tensors with the entries named in ``want``, shaped like
+        ``h1`` without (log_q_agg, log_q_own) or with (log_q_dim, log_q_own_dim)
+        its last axis; ``"loc"`` / ``"scale"`` [M, d1]: the components used.
+        ``own_period`` P > 0: row r's own image is r mod P (for [k, N, d1]
+        latents of x_ref itself: P = N).  Nothing is drawn."""
+        d1 = self.n_latent_encoder[0]
+        with torch.cuda.stream(self._stream):
+            ht = torch.as_tensor(h1).to(device=self.device, dtype=torch.float32, non_blocking=True).contiguous()
+            lt = st = None
+            if loc is not None:
+                lt = torch.as_tensor(loc).to(device=self.device, dtype=torch.float32, non_blocking=True).contiguous()
+            if scale is not None:
+                st = torch.as_tensor(scale).to(device=self.device, dtype=torch.float32, non_blocking=True).contiguous()
+        xd = self._x(x_ref) if x_ref is not None else None
+        comp = [tuple(t.shape) for t in (lt, st) if t is not None]
+        M = int(xd.shape[0]) if xd is not None else (comp[0][0] if comp and len(comp[0]) == 2 else 0)
+        R, want = check_aggregate_args(tuple(ht.shape), d1, xd is not None, comp, M, own_period, want)
+        lead = tuple(ht.shape[:-1])
+        with torch.cuda.stream(self._stream):
+            if xd is not None:
+                lt = torch.empty(M, d1, device=self.device) if "loc" in want else None
+                st = torch.empty(M, d1, device=self.device) if "scale" in want else None
+            out = {n: torch.empty(*lead, device=self.device) for n in ("log_q_agg", "log_q_own") if n in want}
+            out.update({n: torch.empty(*lead, d1, device=self.device) for n in ("log_q_dim", "log_q_own_dim") if n in want})
+        self._call(self._lib.iwae_aggregate(
+            self._h, _lib.fptr(xd), M, int(chunk), _lib.fptr(lt), _lib.fptr(st), _lib.fptr(ht), R, int(own_period),
+            _lib.fptr(out.get("log_q_agg")), _lib.fptr(out.get("log_q_dim")), _lib.fptr(out.get("log_q_own")),
+            _lib.fptr(out.get("log_q_own_dim"))))
+        if "loc" in want:
+            out["loc"] = lt
+        if "scale" in want:
+            out["scale"] = st
+        self._stream.synchronize()
+        return out
+
+    def aggregate_posterior(self, x, k, x_ref=None, eps=None, chunk=0, per_unit=False):
+        """k samples per image of q(h|x) (``model.encoder``'s draw: the samples a
+        layer-wise ``get_log_weights`` of the same seed weighs) scored under the
+        aggregate posterior of ``x_ref`` (default: x itself, and then also under
+        each row's own image).  Returns a dict of device tensors, image-major
+        [N, k]: ``log_q`` = log q(h|x), ``log_ph`` = log p(h), ``log_q_agg`` =
+        log q(h_1), with x_ref None ``log_q_own`` = log q(h_1|x); ``per_unit``
+        adds ``log_q_dim`` (and ``log_q_own_dim``) [N, k, d1]; ``h``: the latents,
+        L tensors [k, N, d_i]."""
+        hs, lq, _ = self._encode(x, k, eps=eps, chunk=chunk)
+        N = int(hs[0].shape[1])
+        lp = self._score(None, None, hs, ("log_ph",), chunk)["log_ph"]
+        own = x_ref is None
+        want = ["log_q_agg"] + (["log_q_own"] if own else [])
+        if per_unit:
+            want += ["log_q_dim"] + (["log_q_own_dim"] if own else [])
+        agg = self.log_q_aggregate(hs[0], x_ref=x if own else x_ref, own_period=N if own else 0, want=want, chunk=chunk)
+        with torch.cuda.stream(self._stream):
+            out = {"log_q": lq.t().contiguous(), "log_ph": lp.t().contiguous()}
+            out.update({n: t.transpose(0, 1).contiguous() for n, t in agg.items()})
+        out["h"] = hs
+        self._stream.synchronize()
+        return out
+
+    def information_statistics(self, x, k, eps=None, chunk=0, per_unit=True):
+        """ELBO surgery (Hoffman & Johnson 2016) over the data set x with k
+        samples per image; means over all N k rows, accumulated in float64 on
+        the host:  ``kl`` = mean(log q(h|x) - log p(h));  ``mi`` = mean(log
+        q(h_1|x) - log q(h_1)), the full-batch estimate of I_q(x; h), at most
+        log N;  ``marginal_kl`` = mean(log q(h|x) - log q(h_1|x) + log q(h_1) -
+        log p(h)) = KL(q(h) || p(h)), so mi + marginal_kl == kl;  with
+        ``per_unit`` ``total_correlation`` = mean(log q(h_1) - sum_j log
+        q_j(h_1j)) and ``mi_per_unit`` [d1] (Chen et al. 2018)."""
+        a = self.aggregate_posterior(x, k, eps=eps, chunk=chunk, per_unit=per_unit)
+        f = {n: t.double().cpu().numpy() for n, t in a.items() if n != "h"}
+        res = dict(kl=float((f["log_q"] - f["log_ph"]).mean()),
+                   mi=float((f["log_q_own"] - f["log_q_agg"]).mean()),
+                   marginal_kl=float((f["log_q"] - f["log_q_own"] + f["log_q_agg"] - f["log_ph"]).mean()))
+        if per_unit:
+            res["total_correlation"] = float((f["log_q_agg"] - f["log_q_dim"].sum(-1)).mean())
+            res["mi_per_unit"] = (f["log_q_own_dim"] - f["log_q_dim"]).mean((0, 1))
+        return res
 
     def reconstructed_x_probs_iw(self, x, k, eps=None):
         """Importance-weighted reconstruction [N, x_dim]: sum_s w~_s p(x | h_{1,s})
