@@ -1059,6 +1059,79 @@ int iwae_wake_sleep_grad(iwae_handle* h, const iwae_ws_config* cfg, const float*
                          const float* dream_x, const float* const* dream_lat, int n_dream_lat,
                          float* values_dev);
 
+/* --- thermodynamic variational objective ----------------------------------- */
+/* Thermodynamic variational objective (TVO; Masrani, Le & Wood 2019): k samples
+ * per image and a partition of n_part temperature intervals. */
+typedef struct iwae_tvo_config { int k; int n_part; } iwae_tvo_config;
+/* One TVO step on x [B][x_dim] [dev].  betas [host], n_part + 1 floats: the
+ * partition 0 = betas[0] < betas[1] < ... < betas[n_part] = 1, 1 <= n_part <=
+ * 64; it travels in the launch's arguments (no device copy).  Wake forward:
+ * iwae_log_weights' pass with k samples (device noise: eps NULL, n_eps 0; or
+ * injected eps[i] [k][B][d_i], n_eps = L, as iwae_train_step takes them),
+ * giving h_i and lw_s = log p(h) + log p(x | h_1) - log q(h | x) per image.
+ * With D_j = betas[j+1] - betas[j], wn^(j) = softmax_s(betas[j] lw_s) (taken
+ * after subtracting betas[j] max_s lw) and m_j = sum_s wn^(j)_s lw_s,
+ * j = 0 .. n_part, per image:
+ *   lower = sum_{j<n_part} D_j m_j        (left Riemann sum: the TVO),
+ *   upper = sum_{j<n_part} D_j m_{j+1}    (right Riemann sum),
+ *   iwae  = logsumexp_s lw_s - log k,     lower <= iwae <= upper,
+ *   a_theta_s = sum_{j<n_part} D_j wn^(j)_s [1 + betas[j] (lw_s - m_j)]
+ *             = d lower / d lw_s,                          sum_s a_theta_s = 1,
+ *   a_phi_s   = sum_{j<n_part} D_j wn^(j)_s [(1 - betas[j]) (lw_s - m_j) - 1],
+ *                                                          sum_s a_phi_s = -1
+ * (a_phi: the covariance estimator of the paper's eq. 9-10 at fixed samples;
+ * it needs no reparameterisation and can be negative).  n_part = 1 makes lower
+ * the k-sample ELBO mean_s lw and a_theta = 1 / k; k = 1 gives a_theta = 1,
+ * a_phi = -1.  Three values, float32, the negated batch means:
+ *   L_tvo = -(1/B) sum_b lower_b >= L_iwae = -(1/B) sum_b iwae_b
+ *                                >= L_upper = -(1/B) sum_b upper_b.
+ * Gradient buffer, of L_tvo at fixed samples: the decoder's parameters get
+ * -(1/B) sum_bs a_theta_bs grad [log p(h_bs) + log p(x_b | h_1,bs)] (the row
+ * weight -a_theta / B where an IWAE step has dL/dlw and dpx; no dL/dh
+ * stages); the encoder's get the gradient of -(1/B) sum_bs a_phi_bs
+ * log q(h_bs | x_b) with a_phi and h constants: per head -a z/s on mu and
+ * -a (z^2 - 1)(s - 1e-6)/s on zs with row weight a = a_phi_bs / B, the GM_FIT
+ * regression of iwae_wake_sleep_step (linear in a, of either sign), per layer
+ * into that layer's weight gradients only.
+ * values_dev [dev], 3 floats (L_tvo, L_upper, L_iwae), may be NULL.
+ * iwae_tvo_step then applies the handle's Adam to the whole buffer;
+ * iwae_tvo_grad leaves the gradient in the buffer (iwae_get_grads,
+ * iwae_apply_adam) and the Adam state untouched.  The noise position advances
+ * once.
+ * Launches: the wake forward, tvo_kernel (one wave per image, fixed reduction
+ * orders, no float atomics: the values, both sets of row weights, the noise
+ * position and Adam's tick in one launch), the decoder backward and its weight
+ * gradients, one GM_FIT backward per encoder layer and their weight gradients,
+ * Adam.  Paths: chosen as iwae_wake_sleep_step's are, over B k rows: the f32
+ * row-block kernels, else the layer-wise GEMMs, never an error; never the
+ * bf16x3 engine, the fused update or the weight ring.  iwae_set_graphs does not
+ * apply: every launch is enqueued on the handle's stream, with no host
+ * synchronisation unless the workspace grows (before anything is enqueued);
+ * captured train-step graphs and engine plans survive a call that does not
+ * grow it.  Deterministic.
+ * IWAE_EINVAL, nothing launched and the noise position untouched (after the
+ * sticky iwae_status error, returned first): cfg, betas or x NULL; k < 1 or
+ * B < 1; n_part outside [1, 64]; a beta not finite, betas not strictly
+ * ascending, betas[0] != 0 or betas[n_part] != 1; a wrong n_eps or a NULL
+ * eps[i]; B k above 2^30; a data-parallel world > 1. */
+int iwae_tvo_step(iwae_handle* h, const iwae_tvo_config* cfg, const float* betas,
+                  const float* x, int B, const float* const* eps, int n_eps, float* values_dev);
+int iwae_tvo_grad(iwae_handle* h, const iwae_tvo_config* cfg, const float* betas,
+                  const float* x, int B, const float* const* eps, int n_eps, float* values_dev);
+/* The same kernel on caller log weights lw [N][k] [dev] (iwae_log_weights',
+ * iwae_ais' or iwae_refine's, say): per image lower, upper, iwae [N] [dev] and
+ * per row a_theta, a_phi [N][k] [dev] as defined above, unscaled; each output
+ * may be NULL, not all.  betas [host], n_part + 1 floats.  k <= 2^20 (staged
+ * in LDS up to 1024, re-read beyond), N k <= 2^30.  One tvo_kernel launch on
+ * the handle's stream; nothing is drawn; weights, Adam state, graphs, plans
+ * and the noise position are untouched.  An image whose lw holds a NaN or an
+ * infinity gets NaN in each of its outputs; its neighbours are untouched.
+ * IWAE_EINVAL, nothing launched (after the sticky iwae_status error): lw or
+ * betas NULL; N < 1; k outside [1, 2^20]; n_part or betas as above; N k above
+ * 2^30; every output NULL. */
+int iwae_tvo_weights(iwae_handle* h, const float* lw, int N, int k, const float* betas, int n_part,
+                     float* lower, float* upper, float* iwae, float* a_theta, float* a_phi);
+
 /* --- diagnostics ---------------------------------------------------------- */
 /* C[M][N] = A[M][K] @ B[K][N] (all [dev], row-major, leading dims given) via
  * the f32 MFMA GEMM used on the hot path (unit-test entry). */
@@ -1121,7 +1194,10 @@ double iwae_workspace_bytes(const iwae_handle* h);
  * itself (also counted under 10 where gen_kernel ran them); iwae_aggregate: 39
  * calls that enqueued work, 40 agg_joint_kernel launches (one per call that
  * asks for log_q_agg), 41 agg_dim_kernel launches (one per call that asks for
- * log_q_dim); -1 for an unknown id. */
+ * log_q_dim); TVO: 42 iwae_tvo_step / iwae_tvo_grad calls that enqueued work,
+ * 43 tvo_kernel launches (one per step, grad or iwae_tvo_weights call; a
+ * step's GM_FIT launches also count under 36 / 37, one per encoder layer);
+ * -1 for an unknown id. */
 long long iwae_debug_count(const iwae_handle* h, int what);
 /* Live kernel timing: bracket every launch of one kernel class with HIP events
  * on the handle's stream -- a GEMM class (kind: 0 forward, 1 backward-data,

@@ -6,8 +6,8 @@ include/iwae.h.  This package is the host-side mirror of the reference's
 Python API; see DESIGN.md.
 """
 from .flexible_iwae import (Adam, Flexible_Model, LOSSES, ais_schedule, architecture, glorot_weights,  # noqa: F401
-                            loss_config, output_bias, resolve_dataset_bias, weight_shapes)
+                            loss_config, output_bias, resolve_dataset_bias, tvo_schedule, weight_shapes)
 from . import data  # noqa: F401,E402  (local-file loaders, LR-stage driver)
 
 __all__ = ["Adam", "Flexible_Model", "LOSSES", "ais_schedule", "architecture", "glorot_weights", "loss_config",
-           "output_bias", "resolve_dataset_bias", "weight_shapes"]
+           "output_bias", "resolve_dataset_bias", "tvo_schedule", "weight_shapes"]

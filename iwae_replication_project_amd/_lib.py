@@ -68,6 +68,10 @@ class IwaeWsConfig(ctypes.Structure):
     _fields_ = [("k", c_int), ("n_dream", c_int), ("c_wake", c_float), ("c_sleep", c_float)]
 
 
+class IwaeTvoConfig(ctypes.Structure):
+    _fields_ = [("k", c_int), ("n_part", c_int)]
+
+
 FP = POINTER(c_float)
 FPP = POINTER(FP)
 H = c_void_p
@@ -146,6 +150,9 @@ SIGNATURES = {
     "iwae_profile_gemm": (c_int, [H, c_int, c_int]),
     "iwae_profile_read": (c_int, [H, POINTER(c_double), POINTER(c_double), POINTER(c_longlong)]),
     "iwae_profile_replay": (c_int, [H, c_int, POINTER(c_double), POINTER(c_double)]),
+    "iwae_tvo_step": (c_int, [H, POINTER(IwaeTvoConfig), FP, FP, c_int, FPP, c_int, FP]),
+    "iwae_tvo_grad": (c_int, [H, POINTER(IwaeTvoConfig), FP, FP, c_int, FPP, c_int, FP]),
+    "iwae_tvo_weights": (c_int, [H, FP, c_int, c_int, FP, c_int, FP, FP, FP, FP, FP]),
     "iwae_wake_sleep_step": (c_int, [H, POINTER(IwaeWsConfig), FP, c_int, FPP, c_int, FP, FPP, c_int, FP]),
     "iwae_wake_sleep_grad": (c_int, [H, POINTER(IwaeWsConfig), FP, c_int, FPP, c_int, FP, FPP, c_int, FP]),
 }

@@ -337,6 +337,39 @@ struct BoundArgs {
 hipError_t launch_bound(hipStream_t st, const BoundArgs& a);
 int bound_grid(const BoundArgs& a);    // its workgroups
 
+// ------------------------------------------ thermodynamic variational objective
+// tvo_kernel (iwae_tvo.hip): per image, over its kS log
+// weights and the partition beta[0 .. J] (beta[0] = 0 < ... < beta[J] = 1), with
+// D_j = beta[j + 1] - beta[j], wn^(j) = softmax_s(beta[j] lw_s) and
+// m_j = sum_s wn^(j)_s lw_s:
+//   lower = sum_{j<J} D_j m_j,  upper = sum_{j<J} D_j m_{j+1},
+//   iwae  = logsumexp_s lw_s - log kS,
+//   a_theta_s = sum_{j<J} D_j wn^(j)_s [1 + beta[j] (lw_s - m_j)],
+//   a_phi_s   = sum_{j<J} D_j wn^(j)_s [(1 - beta[j]) (lw_s - m_j) - 1].
+// One wave per image, bound_kernel's discipline: fixed butterflies over lanes,
+// a lane's samples in sample order, j ascending; no float atomics, one writer
+// per element.  An image with a NaN or an infinity among its log weights gets
+// NaN in every output of its own, and in the batch values it is summed into.
+constexpr int kTvoMaxPart = 64;
+struct TvoArgs {
+  // the log weights: lw_in [Bimg][kS] when given, else composed per row as
+  // bound_kernel does from logp / the Bernoulli partials / logq and stored to lw_out
+  const float* lw_in;
+  const float* part; int ldpart, npart; const float* logp; const float* logq;
+  float* lw_out;
+  int kS, Bimg, J;
+  float beta[kTvoMaxPart + 1];
+  float* a_theta; float* a_theta2; float s_theta;   // s_theta a_theta per row, to both (each may be null)
+  float* a_phi; float s_phi;                        // s_phi a_phi per row (may be null)
+  float* lower; float* upper; float* iwae;          // per image (each may be null; all three given with `values`)
+  // step mode (values != null): values[0 .. 2] = -(1/Bimg) sum_b (lower, upper,
+  // iwae), the advance of the noise position and Adam's tick, as bound_finalize
+  float* values;
+  unsigned* ticket; uint64_t* rng_base; long long* adam_step;
+};
+hipError_t launch_tvo(hipStream_t st, const TvoArgs& a);
+int tvo_grid(const TvoArgs& a);        // its workgroups (bound_grid's rule)
+
 // per-image LSE over this chunk's rows merged into running (m, s)
 struct LseArgs {
   const float* part; int ldpart, npart; const float* logp; const float* logq;

@@ -227,6 +227,7 @@ struct Counters {
   long long ws_dream = 0;                // 38: dream generations a wake-sleep step ran itself
   long long agg = 0;                     // 39: iwae_aggregate calls that enqueued work
   long long agg_joint = 0, agg_dim = 0;  // 40, 41: agg_joint_kernel / agg_dim_kernel launches
+  long long tvo = 0, tvo_launch = 0;     // 42, 43: TVO step / grad calls that enqueued work / tvo_kernel launches (weights calls too)
 };
 
 // row-chain train engine plan (device resident, per shape; iwae_train.hip)
@@ -6108,6 +6109,112 @@ int iwae_wake_sleep_grad(iwae_handle* h, const iwae_ws_config* cfg, const float*
   return do_wake_sleep(h, cfg, x, B, eps, n_eps, dream_x, dream_lat, n_dream_lat, values_dev, false);
 }
 
+// ------------------------------------------ thermodynamic variational objective
+// iwae_tvo_step / _grad / _weights.  A sibling of the
+// wake-wake step above: the same wake forward, decoder backward without dL/dh
+// and GM_FIT encoder regression over the wake rows, with tvo_kernel in place of
+// the bound launch and of the ws_weights / ws_values launches: it writes the
+// decoder's row weight -a_theta / B where an IWAE step has dL/dlw and dpx, and
+// the regression's row weight a_phi / B (of either sign: the GM_FIT partials
+// are linear in it) into dlw2's rows.
+static int tvo_partition(iwae_handle* h, const float* betas, int n_part, TvoArgs& t) {
+  if (!betas) return fail(h, IWAE_EINVAL, "betas is NULL");
+  if (n_part < 1 || n_part > kTvoMaxPart)
+    return fail(h, IWAE_EINVAL, "n_part must be in [1, " + std::to_string(kTvoMaxPart) + "]");
+  for (int j = 0; j <= n_part; ++j) {
+    if (!std::isfinite(betas[j])) return fail(h, IWAE_EINVAL, "betas must be finite");
+    if (j > 0 && !(betas[j] > betas[j - 1])) return fail(h, IWAE_EINVAL, "betas must be strictly ascending");
+    t.beta[j] = betas[j];
+  }
+  if (betas[0] != 0.f || betas[n_part] != 1.f) return fail(h, IWAE_EINVAL, "betas must run from 0 to 1");
+  t.J = n_part;
+  return IWAE_OK;
+}
+
+static int do_tvo(iwae_handle* h, const iwae_tvo_config* cfg, const float* betas, const float* x, int B,
+                  const float* const* eps, int n_eps, float* values_dev, bool adam) {
+  if (!h) return IWAE_EINVAL;
+  CHK(kernel_status(h));
+  if (!cfg) return fail(h, IWAE_EINVAL, "TVO config is NULL");
+  if (!x) return fail(h, IWAE_EINVAL, "x is NULL");
+  if (cfg->k < 1) return fail(h, IWAE_EINVAL, "k must be positive");
+  if (B < 1) return fail(h, IWAE_EINVAL, "batch must be positive");
+  TvoArgs t{};
+  CHK(tvo_partition(h, betas, cfg->n_part, t));
+  if ((long long)B * cfg->k > (1LL << 30)) return fail(h, IWAE_EINVAL, "B * k exceeds 2^30 rows");
+  if (h->dp_world > 1) return fail(h, IWAE_EINVAL, "TVO steps are not built for data parallelism (world > 1)");
+  iwae_loss_config lc{IWAE_LOSS_IWAE, cfg->k, 1.f, 1.f, 0.5f, 0, 0};
+  Plan P;
+  CHK(make_plan(h, &lc, B, P));
+  EpsSet E;
+  CHK(parse_eps(h, P, eps, n_eps, E));
+  const int M = B * P.kS;
+  const bool fusedp = ws_use_fused(h, M);
+  // the workspace at its size before anything is enqueued
+  CHK(ensure_capacity(h, B, M, true));
+  const bool direct = fusedp && smallm_ok(h, P.Bimg);
+  if (!direct) CHK(copy_x(h, P, x));
+  StepScope scope{h};
+  h->step.x_user = direct ? x : nullptr;
+  h->step.in_train_step = true;
+  h->step.out_x3 = h->x3 && h->tune.out_x3_rows > 0 && (long long)M >= h->tune.out_x3_rows;
+  if (h->step.out_x3) CHK(run_wsplit_seg(h, h->o3));
+  h->count.tvo++;
+  if (fusedp) CHK(fused_forward(h, P, E, true));
+  else CHK(layerwise_forward(h, P, E, true));
+  // the three values, both sets of row weights, the noise position and Adam's tick
+  t.part = h->part; t.ldpart = h->ldpart; t.npart = h->npart;
+  t.logp = h->logp; t.logq = h->logq; t.lw_out = h->lw;
+  t.kS = P.kS; t.Bimg = B;
+  t.a_theta = h->dlw; t.a_theta2 = h->dpx; t.s_theta = -1.f / (float)B;
+  t.a_phi = h->dlw2; t.s_phi = 1.f / (float)B;
+  // (per-image scratch of the train step's arena that no launch of this step reads)
+  t.lower = h->contrib; t.upper = h->run_m; t.iwae = h->run_s;
+  t.values = values_dev ? values_dev : &h->ds->scalars[4];
+  t.ticket = &h->ds->tickets[0]; t.rng_base = &h->ds->rng[0];
+  t.adam_step = adam ? &h->ds->adam.t : nullptr;
+  HIPCHK(launch_tvo(h->stream, t));
+  h->count.tvo_launch++;
+  if (fusedp) {
+    CHK(fused_decoder_bwd(h, P, h->dlw, h->dpx, false));
+    CHK(weight_grads(h, P, WG_DECODER));
+  } else {
+    CHK(decoder_bwd(h, P, h->dlw, h->dpx, true, false));
+  }
+  CHK(ws_encoder_fit(h, P, 0, true, h->dlw2, fusedp));
+  return finish_step(h, P, adam);
+}
+
+int iwae_tvo_step(iwae_handle* h, const iwae_tvo_config* cfg, const float* betas, const float* x, int B,
+                  const float* const* eps, int n_eps, float* values_dev) {
+  return do_tvo(h, cfg, betas, x, B, eps, n_eps, values_dev, true);
+}
+
+int iwae_tvo_grad(iwae_handle* h, const iwae_tvo_config* cfg, const float* betas, const float* x, int B,
+                  const float* const* eps, int n_eps, float* values_dev) {
+  return do_tvo(h, cfg, betas, x, B, eps, n_eps, values_dev, false);
+}
+
+int iwae_tvo_weights(iwae_handle* h, const float* lw, int N, int k, const float* betas, int n_part, float* lower,
+                     float* upper, float* iwae, float* a_theta, float* a_phi) {
+  if (!h) return IWAE_EINVAL;
+  CHK(kernel_status(h));
+  if (!lw) return fail(h, IWAE_EINVAL, "lw is NULL");
+  if (N < 1) return fail(h, IWAE_EINVAL, "N must be positive");
+  if (k < 1 || k > (1 << 20)) return fail(h, IWAE_EINVAL, "k must be in [1, 2^20]");
+  TvoArgs t{};
+  CHK(tvo_partition(h, betas, n_part, t));
+  if ((long long)N * k > (1LL << 30)) return fail(h, IWAE_EINVAL, "N * k exceeds 2^30 log weights");
+  if (!lower && !upper && !iwae && !a_theta && !a_phi) return fail(h, IWAE_EINVAL, "every output is NULL");
+  t.lw_in = lw; t.kS = k; t.Bimg = N;
+  t.a_theta = a_theta; t.s_theta = 1.f;
+  t.a_phi = a_phi; t.s_phi = 1.f;
+  t.lower = lower; t.upper = upper; t.iwae = iwae;
+  HIPCHK(launch_tvo(h->stream, t));
+  h->count.tvo_launch++;
+  return IWAE_OK;
+}
+
 int iwae_debug_gemm(iwae_handle* h, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
                     int M, int N, int K) {
   if (!h) return IWAE_EINVAL;
@@ -6172,6 +6279,8 @@ long long iwae_debug_count(const iwae_handle* h, int what) {
     case 39: return h->count.agg;
     case 40: return h->count.agg_joint;
     case 41: return h->count.agg_dim;
+    case 42: return h->count.tvo;
+    case 43: return h->count.tvo_launch;
     default: return -1;
   }
 }

@@ -157,6 +157,24 @@ def ais_schedule(n_temps, kind="sigmoid", rad=4.0):
     return b
 
 
+def tvo_schedule(n_part, beta1=0.025):
+    """The J + 1 temperatures of a TVO partition of J = ``n_part`` intervals,
+    float32: beta_0 = 0, then beta_1 .. beta_J log-uniform from ``beta1`` to
+    exactly 1 (Masrani, Le & Wood 2019, section 6).  J = 1 gives [0, 1]."""
+    J = int(n_part)
+    if J < 1 or J > 64:
+        raise ValueError("n_part must be in [1, 64]")
+    if J > 1 and not 0.0 < float(beta1) < 1.0:
+        raise ValueError("beta1 must lie strictly between 0 and 1")
+    b = np.zeros(J + 1, dtype=np.float32)
+    b[1:] = np.logspace(np.log10(float(beta1)), 0.0, J) if J > 1 else 1.0
+    b[-1] = 1.0
+    return b
+
+
+TVO_OUTPUTS = ("lower", "upper", "iwae", "a_theta", "a_phi")
+
+
 # --------------------------------------------------------------- optimizer
 AGGREGATE_OUTPUTS = ("log_q_agg", "log_q_dim", "log_q_own", "log_q_own_dim", "loc", "scale")
 
@@ -701,6 +719,115 @@ class Flexible_Model:
         out = values.cpu().numpy()
         self._call(self._lib.iwae_status(self._h))
         return out
+
+    # --------------------------------------- thermodynamic variational objective
+    @staticmethod
+    def _betas(betas, n_part):
+        if betas is None:
+            return tvo_schedule(5 if n_part is None else n_part)
+        bt = np.ascontiguousarray(betas, dtype=np.float32).ravel()
+        if n_part is not None and int(n_part) != bt.size - 1:
+            raise ValueError(f"n_part = {n_part} but betas holds {bt.size} values")
+        if bt.size < 2:
+            raise ValueError("betas must hold at least two values")
+        return bt
+
+    def _tvo(self, xd, bt, k, eps, update, values):
+        """One iwae_tvo_step / _grad on the device batch xd; the three values
+        into the device tensor ``values`` (3 floats)."""
+        if self._dp is not None:
+            raise ValueError("tvo_step is not supported under data parallelism")
+        if self.optimizer is None:
+            self.compile()
+        B = int(xd.shape[0])
+        k = self.k if k is None else int(k)
+        arr, ne, keep = self._eps(eps, B, k)
+        cfg = _lib.IwaeTvoConfig(k, bt.size - 1)
+        fn = self._lib.iwae_tvo_step if update else self._lib.iwae_tvo_grad
+        self._call(fn(self._h, cfg, bt.ctypes.data_as(_lib.FP), _lib.fptr(xd), B, arr, ne, _lib.fptr(values)))
+        if update:
+            self.epoch += 1
+        return keep                          # alive until the caller has synchronised or moved on in stream order
+
+    def tvo_step(self, x, betas=None, n_part=None, k=None, eps=None, sync=True, update=True):
+        """One step on the thermodynamic variational objective (iwae_tvo_step;
+        Masrani, Le & Wood 2019): over the partition ``betas`` (default
+        ``tvo_schedule(n_part or 5)``) of [0, 1], the left Riemann sum of
+        m(beta) = E_softmax(beta log w)[log w] over a k-sample wake forward on
+        ``x``.  The decoder descends it at fixed samples, the encoder takes the
+        covariance-form gradient (no reparameterisation).  ``k`` defaults to
+        the model's; ``eps`` as for ``train_step``.  ``update=False`` leaves the
+        gradient in the buffer (``get_gradients``) and Adam untouched.  Returns
+        {"TVO": L_tvo, "TVO_upper": L_upper, "IWAE": L_iwae}, the negated batch
+        means of lower <= iwae <= upper (so TVO >= IWAE >= TVO_upper); device
+        scalars with ``sync=False``."""
+        xd = self._x(x)
+        bt = self._betas(betas, n_part)
+        with torch.cuda.stream(self._stream):
+            values = torch.empty(3, device=self.device)
+        keep = self._tvo(xd, bt, k, eps, update, values)
+        if not sync:
+            self._tvo_keep = (xd, keep)
+            return {"TVO": values[0], "TVO_upper": values[1], "IWAE": values[2]}
+        self._stream.synchronize()
+        v = values.cpu().numpy()
+        self._call(self._lib.iwae_status(self._h))
+        return {"TVO": float(v[0]), "TVO_upper": float(v[1]), "IWAE": float(v[2])}
+
+    def tvo_steps(self, x, batch_size, betas=None, n_part=None, k=None, sync=True):
+        """len(x) // batch_size consecutive TVO steps on the batches
+        x[i*batch_size:(i+1)*batch_size] with device noise, enqueued without
+        synchronising between them.  Returns the values [nsteps, 3] (TVO,
+        TVO_upper, IWAE per step; a device tensor with sync=False)."""
+        xd = self._x(x)
+        B = int(batch_size)
+        if B <= 0:
+            raise ValueError("batch_size must be positive")
+        bt = self._betas(betas, n_part)
+        n = xd.shape[0] // B
+        with torch.cuda.stream(self._stream):
+            values = torch.zeros(n, 3, device=self.device)
+        for i in range(n):
+            self._tvo(xd[i * B:(i + 1) * B], bt, k, None, True, values[i])
+        if not sync:
+            self._tvo_keep = (xd,)
+            return values
+        self._stream.synchronize()
+        out = values.cpu().numpy()
+        self._call(self._lib.iwae_status(self._h))
+        return out
+
+    def tvo_bounds(self, lw, betas, want=("lower", "upper", "iwae")):
+        """iwae_tvo_weights on log weights ``lw`` [N, k] (a numpy array or a
+        device tensor, image-major: ``get_log_weights(...).T``, ``ais``' or
+        ``refine``'s): per image the TVO sandwich lower <= iwae <= upper over
+        the partition ``betas``, and on request the per-sample coefficients
+        "a_theta" and "a_phi" [N, k].  Returns a dict of device tensors named
+        as in ``want``.  Nothing is drawn and no state changes."""
+        want = tuple(want)
+        if not want or any(w not in TVO_OUTPUTS for w in want):
+            raise ValueError(f"want must name some of {TVO_OUTPUTS}")
+        bt = self._betas(betas, None)
+        with torch.cuda.stream(self._stream):
+            lt = torch.as_tensor(lw).to(device=self.device, dtype=torch.float32, non_blocking=True).contiguous()
+            if lt.dim() != 2:
+                raise ValueError(f"lw must be [N, k], got {tuple(lt.shape)}")
+            N, k = int(lt.shape[0]), int(lt.shape[1])
+            out = {w: torch.empty((N, k) if w.startswith("a_") else (N,), device=self.device) for w in want}
+        self._call(self._lib.iwae_tvo_weights(self._h, _lib.fptr(lt), N, k, bt.ctypes.data_as(_lib.FP), bt.size - 1,
+                                              *[_lib.fptr(out.get(w)) for w in TVO_OUTPUTS]))
+        self._stream.synchronize()
+        return out
+
+    def get_L_TVO(self, x, k, betas=None, eps=None):
+        """The model's k log weights per image through ``tvo_bounds``: the batch
+        means (lower, upper, iwae), lower <= iwae <= upper (``betas`` default:
+        ``tvo_schedule(5)``)."""
+        lw = self.get_log_weights(x, k, eps=eps)
+        with torch.cuda.stream(self._stream):
+            lw = lw.t().contiguous()
+        out = self.tvo_bounds(lw, self._betas(betas, None))
+        return tuple(float(out[w].double().mean().item()) for w in ("lower", "upper", "iwae"))
 
     def graph_captures(self):
         """Train-step graphs captured so far (iwae_debug_count id 7)."""
